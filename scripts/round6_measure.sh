@@ -15,8 +15,8 @@ if [ -f $D/variants/libfloria_hip_prof.so ]; then
   cp /tmp/libfloria_hip_base.so $D/libfloria_hip.so
   sed -n '/^python - <<PY/,/^PY/p' scripts/traffic_streams.sh | sed '1d;$d' | sed "s/\$TAG/$TAG/g" > /tmp/ts.py && python /tmp/ts.py > $O/traffic_streams.log 2>&1
 fi
-for n in 250 500 1000; do python bench.py --contigs $n --steps 10 --warmup 3 --cpu-sample 0 --check 0 --pipeline 0 2>/dev/null | grep "^{" > $O/shard_$n.json; done
-python bench.py --steps 10 --warmup 3 2>/dev/null | grep "^{" > $O/bench_default.json
+for n in 250 500 1000; do python bench.py --full --contigs $n --steps 10 --warmup 3 --cpu-sample 0 --check 0 --pipeline 0 2>/dev/null | grep "^{" > $O/shard_$n.json; done
+python bench.py --full --steps 10 --warmup 3 2>/dev/null | grep "^{" > $O/bench_default.json
 scripts/occupancy_sweep.sh slab > $O/occupancy_sweep.txt 2>&1
 ls -la $O
 python -c "

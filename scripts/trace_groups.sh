@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for G in "$@"; do
   O=$R/gpurun_out/trace_G$G
   mkdir -p $O
-  FLORIA_HIP_GROUPS=$G rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python $R/bench.py --steps 1 --warmup 1 --cpu-sample 0 > $O/bench.log 2>&1
+  FLORIA_HIP_GROUPS=$G rocprofv3 --kernel-trace --output-format csv -d $O -o t -- python $R/bench.py --full --steps 1 --warmup 1 --cpu-sample 0 > $O/bench.log 2>&1
   python - <<PY
 import csv, glob
 f = glob.glob("$O/**/*kernel_trace.csv", recursive=True)[0]

@@ -11,7 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "1", "--warmup", "0", "--contigs", "64", "--cpu-sample", "0", "--check", "0", "--pipeline", "0"]
+COMMON = ["--steps", "1", "--warmup", "0", "--contigs", "64", "--cpu-sample", "0", "--check", "0", "--pipeline", "0", "--full"]
 
 
 def free_port():
