@@ -99,14 +99,8 @@ constexpr int slab_waves(int tp) { return (tp >= 2 && tp <= SLAB_LOW_P_MAX) ? SL
 // ARITH instances (the reference's running f64 sums, below): the distance terms of a step wait in LDS for the sequential folds — SLAB_TERM_CAP f64 per wave.
 // Measured on config 4 at eps 0.04 (scripts/arith_ab.sh, ms per call): 768 terms / two waves per SIMD 172.5-174.6, 512 / three 163.3-163.4, 384 / three 168.1-168.2,
 // 768 / three 167.2-167.4 -> 512 terms (five slabs of a 92-cell read per pass) and the register budget of three waves
-#ifndef FLORIA_TERM_CAP
-#define FLORIA_TERM_CAP 512
-#endif
-constexpr int SLAB_TERM_CAP = FLORIA_TERM_CAP;
-#ifndef FLORIA_ARITH_BEAM_WAVES
-#define FLORIA_ARITH_BEAM_WAVES 3
-#endif
-constexpr int SLAB_WAVES_ARITH = FLORIA_ARITH_BEAM_WAVES;
+constexpr int SLAB_TERM_CAP = 512;
+constexpr int SLAB_WAVES_ARITH = 3;
 template <int N> struct IC { static constexpr int value = N; };
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) { if constexpr (I < N) { f(IC<I>{}); static_for<I + 1, N>(f); } }
 // value of lane (segment base + J) for aligned segments of PS = 2 or 4 lanes: one DPP quad_perm move, no LDS crossbar round trip
@@ -235,11 +229,7 @@ __host__ __device__ inline SlabLds slab_lds_layout(uint32_t LM, uint32_t p, bool
 #ifdef FLORIA_PROF
 #define BEAM_TICK(ph) do { const unsigned long long _t = clock64(); t_acc[ph] += _t - t_last; t_last = _t; } while (0)
 #else
-#ifdef FLORIA_MARK
-#define BEAM_TICK(ph) asm volatile("; ====PHASE_END " #ph)
-#else
 #define BEAM_TICK(ph) do {} while (0)
-#endif
 #endif
 
 // TP / TB: ploidy and beam width as compile-time constants (0 = read them from the arguments): LDS offsets become immediates, the
@@ -803,14 +793,10 @@ void beam_slab_kernel(BeamArgs g) {
                             };
                             if (act) {
                                 const uint32_t U = div_small(RS + Gl - 1u, rcp_gl);             // rounds of Gl cells
-#if defined(FLORIA_ARITH_BATCH) && FLORIA_ARITH_BATCH == 4
-                                for (uint32_t u0 = 0; u0 < U; u0 += 4u) { if (U - u0 >= 3u) batch(IC<4>{}, u0); else batch(IC<2>{}, u0); }
-#else
                                 for (uint32_t u0 = 0; u0 < U; u0 += 8u) {
                                     const uint32_t r = U - u0;
                                     if (r >= 7u) batch(IC<8>{}, u0); else if (r >= 5u) batch(IC<6>{}, u0); else if (r >= 3u) batch(IC<4>{}, u0); else batch(IC<2>{}, u0);
                                 }
-#endif
                                 if (L < (uint32_t)SLAB_TILE) atomicAdd((uint32_t*)&r_qs[sidr], (uint32_t)qs);         // (< 256 cells of weight <= 2^24: the sum stays below 2^32)
                                 else atomicAdd((unsigned long long*)&r_qs[sidr], (unsigned long long)qs);
                             }
@@ -834,11 +820,7 @@ void beam_slab_kernel(BeamArgs g) {
                 // every lane walks ceil(nin / Gl) cells in batches of 2 / 4 / 6 / 8 independent byte loads chosen by the exact count, sums in 32 bits inside a
                 // batch, and the lanes of a slab combine through LDS atomics (3 instructions instead of a 4-stage DPP butterfly on three values)
                 for (uint32_t x = lane; x < nlive; x += 64) { const uint32_t sidr = live_id[x]; r_qs[sidr] = 0; r_qd[sidr] = 0; r_m[sidr] = 0; }
-#ifdef FLORIA_MW_A_SHIFT      // (experiment, profiles/r06_multiwave_ab.txt: phase A with 1 / 2^k of its lanes per slab - if the phase were bound by lanes, more waves per job would pay)
-                const uint32_t Gl = nlive <= 64u ? max(1u, div_small(64u, __builtin_amdgcn_rcpf((float)nlive)) >> FLORIA_MW_A_SHIFT) : 1u;
-#else
                 const uint32_t Gl = nlive <= 64u ? div_small(64u, __builtin_amdgcn_rcpf((float)nlive)) : 1u;
-#endif
                 const float rcp_gl = __builtin_amdgcn_rcpf((float)Gl);
                 for (uint32_t l0 = 0; l0 < nlive; l0 += 64u) {             // (one pass unless more than 64 slabs are live: then Gl == 1)
                     const uint32_t lsl = div_small(lane, rcp_gl), sub = lane - lsl * Gl, li = l0 + lsl;
@@ -959,11 +941,7 @@ void beam_slab_kernel(BeamArgs g) {
                     if (alone) min_margin = margin_alone < min_margin ? margin_alone : min_margin;
                     const bool far1 = alone || (asf > 0.f && (double)asf >= min_margin);     // false for NaN
                     pass = dsf > 0.f;
-#ifdef FLORIA_NO_BINOM_SCREEN
-                    if (true) {
-#else
                     if (__any(act && !far1)) {
-#endif
 #ifdef FLORIA_PROF
                         c_lvl2++;
 #endif
@@ -1020,7 +998,6 @@ void beam_slab_kernel(BeamArgs g) {
                         if (!__any(coll)) {
                             bulk = true;
                             b_h1 = ch1; b_h2 = ch2;
-#ifndef FLORIA_NO_FASTM
                             // STRUCTURE-PRESERVING step (6 steps in 10): every state has exactly one passing child and no child inherits a slab that another
                             // child extends.  Then every new version goes in place, every slab keeps its id, the live list and the states' slab tables carry
                             // over (a child's table is its parent's), and phase M needs no reference counts, no leader election by atomics, no free list and
@@ -1048,8 +1025,6 @@ void beam_slab_kernel(BeamArgs g) {
                                     }
                                 }
                             }
-#endif
-#ifndef FLORIA_NO_HEAPKEEP
                             // ... and when, on top of that, the children's scores still satisfy the heap property slot by slot (child of state a = entry a = pushed a-th,
                             // and s_a <= s_parent(a) for every a makes std's sift_up stop at once: global_clustering.rs:130, Appendix A), the new heap IS the children in
                             // their parents' slots: no scalar pushes, one lane-parallel comparison.  (Mirrored states tie before and after: `<=` holds.)
@@ -1069,7 +1044,6 @@ void beam_slab_kernel(BeamArgs g) {
 #endif
                                 }
                             }
-#endif
                             uint32_t r = 0;
                             while (passmask) {
                                 const uint32_t src = (uint32_t)__ffsll((unsigned long long)passmask) - 1;

@@ -25,6 +25,7 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/floria_hip.h"
@@ -74,6 +75,17 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T* as() const { return (T*)p; }
+};
+
+// A call's device arrays, carved out of one scratch buffer: segments in the order they are asked for, each starting on a 256-B boundary.
+struct Seg { size_t off, bytes; };
+struct Carve {
+    size_t cursor = 0;
+    char* base = nullptr;
+    Seg seg(size_t bytes) { const Seg s{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return s; }
+    int place(DevBuf& buf) { const int rc = buf.ensure(cursor + 256); base = buf.as<char>(); return rc; }      // (after the last seg())
+    template <class T = void> T* at(Seg s) const { return (T*)(base + s.off); }
+    hipError_t up(Seg s, const void* src, size_t bytes, hipStream_t st) const { return bytes ? hipMemcpyAsync(base + s.off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; }
 };
 
 // Pinned, device-mapped host memory for the small latency-critical transfers of a call (block counts down, offsets and job lists up): kernels read and
@@ -188,7 +200,7 @@ struct floria_hip_ctx {
     uint32_t user_slots = 0;
     Knobs knobs;
     int n_cu = 256;
-    // launch lanes (job group x position inside a ploidy stage): every lane has its own stream and scratch slice, see run_phase
+    // launch lanes (job group x position inside a ploidy stage): every lane has its own stream and scratch slice, see size_scratch / lane_streams
     static constexpr uint32_t MAX_GROUPS = 8;
     static constexpr uint32_t MAX_LANES = 32;
     hipStream_t gstream[MAX_LANES] = {};
@@ -398,32 +410,90 @@ struct PloidyPlan {
     uint32_t fx_lds_off = 0;      // reference-arithmetic mode: where the emulated position maps sit in the workgroup's LDS (0 = in HBM scratch)
 };
 
+// the blocks of an S1 call as the launch plan sees them
+struct PhaseShape {
+    fl::BlockSet bs{};
+    bool any_q0 = false;                // some cell has qual 0
+    uint32_t n_jobs = 0;                // non-empty blocks
+    uint64_t tot_reads = 0;             // reads of all blocks
+    uint32_t n_max = 1, span_max = 1;   // most reads / widest SNP span of one block
+};
+
+// s1_core's per-call device arrays that the launch loop reads and writes
+struct PhaseBufs {
+    const uint32_t* jobs;                                   // the non-empty blocks, group after group
+    uint8_t* planes;                                        // every read's partition, one plane per ploidy
+    uint8_t* beam_part;                                     // beam partitions, one plane per position in a stage (+1: the tail launch's, below)
+    double* mec; double* na; uint32_t* iters;               // per (block, ploidy)
+    uint8_t* done; uint32_t* best; uint32_t* tried;         // per block: the stop rule's state ...
+    uint32_t* stop; uint32_t* ready;                        // ... and what speculative stages publish of it
+    uint32_t* queue;                                        // persistent-grid queue heads: a pair per (lane, ploidy)
+    double* margin; uint32_t* diag; unsigned long long* steps;
+};
+
+// ---- runtime selector -> compile-time constant, for the two launchers below ---------------------------------------------------
+template <class F> auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// f(V) for the first V that equals v, the last V otherwise (the plan guarantees one of them)
+template <int V, int... Vs, class F> auto pick(uint32_t v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>{});
+    else return v == (uint32_t)V ? f(std::integral_constant<int, V>{}) : pick<Vs...>(v, f);
+}
+
+// The one place where a ploidy's plan becomes a beam-search kernel instance:
+//   beam_slab_kernel<A, Q0, 0, 0, SPEC, ARITH>, and <2, false, p = 2..5, 10, SPEC, ARITH> where the plan says beam_spec (biallelic, no q = 0 cell, beam 10);
+//   beam_wide_kernel<A, Q0, ARITH>; beam_kernel<A, ARITH> (the generic kernel).
+// spec: the launch may drop jobs (a speculative stage, or the tail launch that waits for the stop rule): only the SPEC instances carry those checks.
 template <int A>
-int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const std::vector<uint32_t>& jobs, const std::vector<uint32_t>& group_off,
-              const uint32_t* d_jobs, uint64_t tot_reads, uint32_t n_max, uint32_t span_max, const floria_params* prm, uint8_t* d_planes,
-              uint8_t* d_beam_part, const std::vector<std::vector<uint32_t>>& stages, hipEvent_t* chunk_ev, double* d_mec, double* d_na, uint32_t* d_iters, uint8_t* d_done, uint32_t* d_best,
-              uint32_t* d_tried, uint32_t* d_queue, double* d_margin, uint32_t* d_diag,
-              unsigned long long* d_steps, EventTimer& T, bool& p1_shortcut, uint32_t* d_stop, uint32_t* d_ready) {
+hipError_t launch_beam(const PloidyPlan& q, bool arith, bool any_q0, bool spec, uint32_t slots, hipStream_t st, const fl::BeamArgs& a) {
+    auto go = [&](auto kern, uint32_t lds, bool big_lds) -> hipError_t {      // (the wide and the generic kernel may ask for more than 48 KB of LDS)
+        if (big_lds && lds > 48 * 1024) { const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; }
+        hipLaunchKernelGGL(kern, dim3(slots), dim3(64), lds, st, a);
+        return hipGetLastError();
+    };
+    return with_bool(arith, [&](auto AR) {
+        if (q.slab) return with_bool(spec, [&](auto SP) {
+            if (q.beam_spec) return pick<2, 3, 4, 5>(q.p, [&](auto TP) { return go(fl::beam_slab_kernel<2, false, TP, 10, SP, AR>, q.SL.total, false); });
+            return with_bool(any_q0, [&](auto Q0) { return go(fl::beam_slab_kernel<A, Q0, 0, 0, SP, AR>, q.SL.total, false); });
+        });
+        if (q.wide) return with_bool(any_q0, [&](auto Q0) { return go(fl::beam_wide_kernel<A, Q0, AR>, q.WL.total, true); });
+        return go(fl::beam_kernel<A, AR>, q.LY.total, true);
+    });
+}
+
+// The one place where a ploidy's plan becomes an optimise kernel instance:
+//   optimize_kernel<A, HL, THREADS = 128 | 512 | 1024>, and <2, true, 512 | 1024, p = 1..5> where the plan says opt_spec;
+//   reference arithmetic: <A, HL, THREADS, 0, true>, <A, true, 512, 0, true, 4>, and <2, true, 512, p = 1..5, true, 0 | 4> (biallelic, histogram in LDS, ploidy <= 5).
+template <int A>
+hipError_t launch_optimize(const PloidyPlan& q, const Knobs& K, uint32_t slots, hipStream_t st, const fl::OptArgs& a) {
+    auto go = [&](auto kern) -> hipError_t {
+        if (q.opt_lds > 48 * 1024) { const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.opt_lds); if (e != hipSuccess) return e; }
+        hipLaunchKernelGGL(kern, dim3(slots), dim3(q.threads), q.opt_lds, st, a);
+        return hipGetLastError();
+    };
+    if (K.arith) {
+        // (LDS allows two workgroups per CU: four waves per SIMD, 128 VGPRs)
+        const bool two_wg = q.hl && q.threads == 512 && std::min<size_t>((156 * 1024) / (q.opt_lds + 8 * 1024), 2048 / q.threads) <= 2 && !K.arith_ow6;
+        // reference arithmetic, 512 threads, histogram in LDS, biallelic, ploidy <= 5 (every BASELINE config at the CLI's defaults): ploidy-specialised instances
+        // (round 6: the per-partition loops unroll, `pair / p` is a multiplication); four waves per SIMD (128 VGPRs) where LDS allows two workgroups per CU anyway
+        if (q.hl && q.threads == 512 && A == 2 && q.p <= 5 && !K.no_specialized)
+            return with_bool(two_wg, [&](auto TW) { return pick<1, 2, 3, 4, 5>(q.p, [&](auto TP) { return go(fl::optimize_kernel<2, true, 512, TP, true, TW ? 4 : 0>); }); });
+        if (two_wg) return go(fl::optimize_kernel<A, true, 512, 0, true, 4>);
+        return with_bool(q.hl, [&](auto HL) { return pick<1024, 512, 128>(q.threads, [&](auto T) { return go(fl::optimize_kernel<A, HL, T, 0, true>); }); });
+    }
+    if (q.opt_spec) return pick<1024, 512>(q.threads, [&](auto T) { return pick<1, 2, 3, 4, 5>(q.p, [&](auto TP) { return go(fl::optimize_kernel<2, true, T, TP>); }); });
+    return with_bool(q.hl, [&](auto HL) { return pick<1024, 512, 128>(q.threads, [&](auto T) { return go(fl::optimize_kernel<A, HL, T>); }); });
+}
+
+// ---- plan every ploidy once: kernel choice, grid, scratch per slot (host only) ---------------------------------------------------
+template <int A>
+int plan_ploidies(const floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S, uint32_t nj_max, std::vector<PloidyPlan>& plan) {
     const uint32_t P = prm->max_ploidy, B = prm->beam;
     const Knobs& K = ctx->knobs;
-    p1_shortcut = false;
-    const uint32_t n_jobs = (uint32_t)jobs.size();
-    const uint32_t G = (uint32_t)group_off.size() - 1;
-    if (n_jobs == 0) return 0;
-    uint32_t W = 1;                                        // widest stage
-    for (auto& st : stages) W = std::max<uint32_t>(W, (uint32_t)st.size());
-    const uint32_t n_lanes = G * W;
-    if (n_lanes > floria_hip_ctx::MAX_LANES) return fail(FLORIA_E_INVALID, "internal: too many launch lanes");
-    uint32_t nj_max = 0;
-    for (uint32_t g = 0; g < G; ++g) nj_max = std::max(nj_max, group_off[g + 1] - group_off[g]);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const double cutoff = std::log(PROB_CUTOFF);      // graph_processing.rs:146
-
-    // ---- plan every ploidy once: kernel choice, grid, scratch per slot -------------------------------------------------------
-    std::vector<PloidyPlan> plan(P + 1);
-    const uint64_t fx_ctrl = fl::fx_ctrl_bytes(span_max + 1), fx_slot = fl::fx_slot_bytes(span_max + 1), fx_bytes = fx_ctrl + fx_slot;       // (+1: slack)
-    const uint32_t mean_n = (uint32_t)(tot_reads / std::max<uint32_t>(1, n_jobs));
+    const bool any_q0 = S.any_q0;
+    const uint32_t n_max = S.n_max, span_max = S.span_max;
+    plan.assign(P + 1, PloidyPlan{});
+    const uint64_t fx_ctrl = fl::fx_ctrl_bytes(span_max + 1);       // (+1: slack)
+    const uint32_t mean_n = (uint32_t)(S.tot_reads / std::max<uint32_t>(1, S.n_jobs));
     for (uint32_t p = 1; p <= P; ++p) {
         PloidyPlan& q = plan[p];
         q.p = p; q.LM = p * B;
@@ -520,7 +590,19 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
         per_cu = std::min<uint32_t>(per_cu, 8);
         q.opt_slots = std::min<uint32_t>((uint32_t)ctx->n_cu * per_cu, nj_max);
     }
-    // ---- scratch: one fixed slice per lane, sized for the largest ploidy -----------------------------------------------------
+    return 0;
+}
+
+// ---- scratch: one fixed slice per lane, sized for the largest ploidy -------------------------------------------------------------
+struct LaneScratch { uint64_t state = 0, hist = 0, ohist = 0, odist = 0, ogain = 0, okey = 0, omoves = 0, arith = 0; };      // bytes of a lane's slice of each pool
+uint64_t sort_cap_of(uint32_t p, uint32_t span_max) { uint64_t c = 1; while (c < (uint64_t)p * span_max) c <<= 1; return c; }
+
+template <int A>
+int size_scratch(floria_hip_ctx* ctx, const PhaseShape& S, uint32_t n_lanes, std::vector<PloidyPlan>& plan, LaneScratch& sl) {
+    const uint32_t P = (uint32_t)plan.size() - 1, n_max = S.n_max, span_max = S.span_max;
+    const uint64_t fx_bytes = fl::fx_ctrl_bytes(span_max + 1) + fl::fx_slot_bytes(span_max + 1);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
     const uint64_t budget = (uint64_t)((double)(free_b + ctx->state_pool.cap + ctx->hist_pool.cap) * 0.6);
     for (;;) {
         uint64_t need = 0;
@@ -530,35 +612,36 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
         for (uint32_t p = 1; p <= P; ++p) if (!plan[p].shortcut && (plan[p].state_bytes + plan[p].hist_stride * 4) * plan[p].beam_slots == need && plan[p].beam_slots > 1) { plan[p].beam_slots /= 2; shrunk = true; }
         if (!shrunk) break;
     }
-    uint64_t sl_state = 0, sl_hist = 0, sl_ohist = 0, sl_odist = 0, sl_ogain = 0, sl_okey = 0, sl_omoves = 0, sl_arith = 0;
-    auto sort_cap_of = [&](uint32_t p) { uint64_t c = 1; while (c < (uint64_t)p * span_max) c <<= 1; return c; };
     auto up256 = [](uint64_t x) -> uint64_t { return (x + 255) & ~(uint64_t)255; };
+    sl = LaneScratch{};
     for (uint32_t p = 1; p <= P; ++p) {
         const PloidyPlan& q = plan[p];
-        if (!q.shortcut) { sl_state = std::max(sl_state, up256(q.state_bytes * q.beam_slots)); sl_hist = std::max(sl_hist, up256(q.hist_stride * 4 * q.beam_slots)); }
-        sl_ohist = std::max(sl_ohist, up256((uint64_t)q.opt_slots * span_max * p * A * 8));
-        sl_odist = std::max(sl_odist, up256((uint64_t)q.opt_slots * n_max * p * 8));
-        sl_ogain = std::max(sl_ogain, up256((uint64_t)q.opt_slots * q.cand_cap * 8));
-        sl_okey = std::max(sl_okey, up256((uint64_t)q.opt_slots * q.cand_cap * 4));
-        sl_omoves = std::max(sl_omoves, up256((uint64_t)q.opt_slots * n_max * 4));
-        if (K.arith) sl_arith = std::max(sl_arith, up256((uint64_t)q.opt_slots * ((uint64_t)p * span_max * 8 + sort_cap_of(p) * 12 + (uint64_t)p * 2 * fx_bytes + 16 + (uint64_t)p * span_max * 8) + 64));
+        if (!q.shortcut) { sl.state = std::max(sl.state, up256(q.state_bytes * q.beam_slots)); sl.hist = std::max(sl.hist, up256(q.hist_stride * 4 * q.beam_slots)); }
+        sl.ohist = std::max(sl.ohist, up256((uint64_t)q.opt_slots * span_max * p * A * 8));
+        sl.odist = std::max(sl.odist, up256((uint64_t)q.opt_slots * n_max * p * 8));
+        sl.ogain = std::max(sl.ogain, up256((uint64_t)q.opt_slots * q.cand_cap * 8));
+        sl.okey = std::max(sl.okey, up256((uint64_t)q.opt_slots * q.cand_cap * 4));
+        sl.omoves = std::max(sl.omoves, up256((uint64_t)q.opt_slots * n_max * 4));
+        if (ctx->knobs.arith) sl.arith = std::max(sl.arith, up256((uint64_t)q.opt_slots * ((uint64_t)p * span_max * 8 + sort_cap_of(p, span_max) * 12 + (uint64_t)p * 2 * fx_bytes + 16 + (uint64_t)p * span_max * 8) + 64));
     }
-    {   // (a pool that has to grow is freed first: hipFree synchronises the device, and nothing of this call is in flight yet)
-        int rc = ctx->state_pool.ensure(sl_state * n_lanes); if (rc) return rc;
-        rc = ctx->hist_pool.ensure(sl_hist * n_lanes); if (rc) return rc;
-        rc = ctx->opt_hist.ensure(sl_ohist * n_lanes); if (rc) return rc;
-        rc = ctx->opt_dist.ensure(sl_odist * n_lanes); if (rc) return rc;
-        rc = ctx->opt_gain.ensure(sl_ogain * n_lanes); if (rc) return rc;
-        rc = ctx->opt_key.ensure(sl_okey * n_lanes); if (rc) return rc;
-        rc = ctx->opt_moves.ensure(sl_omoves * n_lanes); if (rc) return rc;
-        if (K.arith) { rc = ctx->arith_pool.ensure(sl_arith * n_lanes); if (rc) return rc; }
-    }
-    // ---- streams and events: lane (g, j) runs on its own stream; lane (0, 0) is the context's main stream ---------------------
-    hipStream_t ls[floria_hip_ctx::MAX_LANES];
+    // (a pool that has to grow is freed first: hipFree synchronises the device, and nothing of this call is in flight yet)
+    int rc = ctx->state_pool.ensure(sl.state * n_lanes); if (rc) return rc;
+    rc = ctx->hist_pool.ensure(sl.hist * n_lanes); if (rc) return rc;
+    rc = ctx->opt_hist.ensure(sl.ohist * n_lanes); if (rc) return rc;
+    rc = ctx->opt_dist.ensure(sl.odist * n_lanes); if (rc) return rc;
+    rc = ctx->opt_gain.ensure(sl.ogain * n_lanes); if (rc) return rc;
+    rc = ctx->opt_key.ensure(sl.okey * n_lanes); if (rc) return rc;
+    rc = ctx->opt_moves.ensure(sl.omoves * n_lanes); if (rc) return rc;
+    if (ctx->knobs.arith) { rc = ctx->arith_pool.ensure(sl.arith * n_lanes); if (rc) return rc; }
+    return 0;
+}
+
+// ---- streams and events: lane (g, j) runs on its own stream; lane (0, 0) is the context's main stream -----------------------------
+int lane_streams(floria_hip_ctx* ctx, uint32_t n_lanes, uint32_t W, bool spec_first, hipStream_t* ls) {
     for (uint32_t l = 0; l < n_lanes; ++l) {
         if (l == 0) { ls[0] = ctx->stream; continue; }
-        if (W > 1 && (l % W) >= (stages.front().size() > 1 ? 3u : 1u)) {      // ({1}{2}{3}{4..P}: the lanes of ploidy >= 5)        // a speculative stage's lanes of ploidy >= 4: lowest dispatch priority, so that the ploidies every
-                                                            // block needs get the wave slots first and the stop rule is known before most of these jobs start
+        if (W > 1 && (l % W) >= (spec_first ? 3u : 1u)) {      // ({1}{2}{3}{4..P}: the lanes of ploidy >= 5)        // a speculative stage's lanes of ploidy >= 4: lowest dispatch priority, so that the ploidies every
+                                                                // block needs get the wave slots first and the stop rule is known before most of these jobs start
             if (!ctx->gstream_low[l]) {
                 int least = 0, greatest = 0;
                 (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
@@ -575,9 +658,38 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
         ls[l] = ctx->gstream[l];
     }
     if (!ctx->ev_fork[0]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork[0], hipEventDisableTiming));
+    return 0;
+}
+
+// ---- the stage loop: every group's stages, each a beam -> optimise chain per ploidy, then the stop rule ---------------------------
+template <int A>
+int run_phase(floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S, const std::vector<uint32_t>& group_off, const std::vector<std::vector<uint32_t>>& stages,
+              hipEvent_t* chunk_ev, const PhaseBufs& D, EventTimer& T, bool& p1_shortcut) {
+    const uint32_t P = prm->max_ploidy, B = prm->beam;
+    const Knobs& K = ctx->knobs;
+    p1_shortcut = false;
+    const uint32_t G = (uint32_t)group_off.size() - 1;
+    if (S.n_jobs == 0) return 0;
+    const fl::BlockSet& bs = S.bs;
+    const uint64_t tot_reads = S.tot_reads;
+    const uint32_t n_max = S.n_max, span_max = S.span_max;
+    uint32_t W = 1;                                        // widest stage
+    for (auto& st : stages) W = std::max<uint32_t>(W, (uint32_t)st.size());
+    const uint32_t n_lanes = G * W;
+    if (n_lanes > floria_hip_ctx::MAX_LANES) return fail(FLORIA_E_INVALID, "internal: too many launch lanes");
+    uint32_t nj_max = 0;
+    for (uint32_t g = 0; g < G; ++g) nj_max = std::max(nj_max, group_off[g + 1] - group_off[g]);
+    const double cutoff = std::log(PROB_CUTOFF);      // graph_processing.rs:146
+    std::vector<PloidyPlan> plan;
+    int rc = plan_ploidies<A>(ctx, prm, S, nj_max, plan); if (rc) return rc;
+    LaneScratch sl;
+    rc = size_scratch<A>(ctx, S, n_lanes, plan, sl); if (rc) return rc;
+    hipStream_t ls[floria_hip_ctx::MAX_LANES];
+    rc = lane_streams(ctx, n_lanes, W, stages.front().size() > 1, ls); if (rc) return rc;
+    const uint64_t fx_ctrl = fl::fx_ctrl_bytes(span_max + 1), fx_slot = fl::fx_slot_bytes(span_max + 1), fx_bytes = fx_ctrl + fx_slot;       // (+1: slack)
     const int t_phase = T.begin(K_PHASE);
     // ploidy 1 (always position 0 of the first stage) without a search: its beam partition is all zeros, for every group's reads
-    if (plan[1].shortcut) { HIPCHK(hipMemsetAsync(d_beam_part, 0, tot_reads, ctx->stream)); p1_shortcut = true; }
+    if (plan[1].shortcut) { HIPCHK(hipMemsetAsync(D.beam_part, 0, tot_reads, ctx->stream)); p1_shortcut = true; }
     // fork: every group's first lane starts after what the main stream has queued so far (uploads, memsets, block_reads_kernel)
     if (G > 1) {
         HIPCHK(hipEventRecord(ctx->ev_fork[0], ctx->stream));
@@ -597,7 +709,7 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
         if (want && W == 1 && stages.size() >= 3 && P >= 3 && stages.back().size() == 1 && stages.back()[0] == P && stages[stages.size() - 2][0] == P - 1
             && plan[P].slab && !plan[P].wide && !plan[P].shortcut && !plan[P - 1].shortcut && !K.arith && ctx->hw_queues >= 5 && G <= floria_hip_ctx::MAX_GROUPS) tail_p = P;
     }
-    uint8_t* const tail_part = d_beam_part + (uint64_t)W * (tot_reads + 16);
+    uint8_t* const tail_part = D.beam_part + (uint64_t)W * (tot_reads + 16);
     // one beam launch of group g: ploidy p on stream st (scratch slice `lane`), partitions into lane_part.  wait_tried != 0: the launch of the last ploidy that runs
     // beside the optimise launch of ploidy wait_tried (per-block dataflow, below)
     auto beam_launch = [&](const std::vector<uint32_t>& stage, uint32_t g, uint32_t nj, const uint32_t* gjobs, uint32_t p, uint32_t lane, hipStream_t st, uint32_t* gqueue,
@@ -606,74 +718,30 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
         const uint32_t slots_full = std::min(q.beam_slots, nj);
         fl::BeamArgs a{};
         a.bs = bs; a.job_block = gjobs; a.n_jobs = nj; a.ploidy = p; a.beam = B; a.span_max = span_max; a.n_max = n_max;
-        a.queue_head = gqueue; a.blk_done = d_done; a.stop_at = stage.size() > 1 && !wait_tried ? d_stop : nullptr;
-        a.tried = d_tried; a.wait_tried = wait_tried; a.wait_ticks = 2000000u;      // (20 ms: longer than any optimise launch takes)
-        a.state_pool = (uint64_t*)(ctx->state_pool.as<char>() + sl_state * lane); a.state_stride = q.state_bytes;
-        a.hist_pool = (uint32_t*)(ctx->hist_pool.as<char>() + sl_hist * lane); a.hist_stride = q.hist_stride;
+        a.queue_head = gqueue; a.blk_done = D.done; a.stop_at = stage.size() > 1 && !wait_tried ? D.stop : nullptr;
+        a.tried = D.tried; a.wait_tried = wait_tried; a.wait_ticks = 2000000u;      // (20 ms: longer than any optimise launch takes)
+        a.state_pool = (uint64_t*)(ctx->state_pool.as<char>() + sl.state * lane); a.state_stride = q.state_bytes;
+        a.hist_pool = (uint32_t*)(ctx->hist_pool.as<char>() + sl.hist * lane); a.hist_stride = q.hist_stride;
         a.binom_tab = ctx->d_binom.as<double>(); a.binom_nmax = ctx->binom_nmax;
         a.eps = prm->epsilon; a.div_factor = DIV_FACTOR; a.cutoff = cutoff;
         a.ln_eps = (float)std::log(prm->epsilon); a.ln_1meps = (float)std::log(1.0 - prm->epsilon);
         a.Rq1 = H; a.Rp1 = H + ctx->hash_len; a.Rq2 = H + 2ull * ctx->hash_len; a.Rp2 = H + 3ull * ctx->hash_len;
-        a.part_out = lane_part; a.job_margin = d_margin; a.max_ploidy = P; a.diag = d_diag; a.steps_done = d_steps;
-        a.prof = (unsigned long long*)(d_diag + 4);
+        a.part_out = lane_part; a.job_margin = D.margin; a.max_ploidy = P; a.diag = D.diag; a.steps_done = D.steps;
+        a.prof = (unsigned long long*)(D.diag + 4);
         a.no_bulk = K.no_bulk;
         a.cell_ord = ctx->cur_ord; a.cell_ord_off = ctx->cur_ord_off;
-        auto big_lds = [&](const void* kern, uint32_t bytes) -> hipError_t {
-            return bytes > 48 * 1024 ? hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
-        };
         const bool gated = !wait_tried && stage.size() > 1 && ((stage[0] <= 2 && p >= 4) || (stage[0] == 4 && p >= 5));      // (ungated ploidy 4 / 5 measured worse: 24.3 against 22.5 ms for the 250-contig shard)
         // ... and with a smaller persistent grid: the optimise workgroups of the lower ploidies (whose results decide which of these
         // jobs are needed at all) find room on the chip, and jobs that are dequeued later are dropped more often
         const uint32_t slots = wait_tried ? std::max<uint32_t>(1, std::min(slots_full, (uint32_t)ctx->n_cu * K.tail_waves)) : gated ? std::max<uint32_t>(1, std::min(slots_full, std::max<uint32_t>((uint32_t)ctx->n_cu, slots_full / K.spec_gate_div))) : slots_full;
-        auto fire = [&](uint32_t slots) -> int {
-            if (K.arith && q.slab) {
-                const bool sp = a.stop_at != nullptr || wait_tried != 0;
-                auto L = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(slots), dim3(64), q.SL.total, st, a); };
-                if (any_q0) { if (sp) L(fl::beam_slab_kernel<A, true, 0, 0, true, true>); else L(fl::beam_slab_kernel<A, true, 0, 0, false, true>); }
-                else if (q.beam_spec && p == 2) { if (sp) L(fl::beam_slab_kernel<2, false, 2, 10, true, true>); else L(fl::beam_slab_kernel<2, false, 2, 10, false, true>); }
-                else if (q.beam_spec && p == 3) { if (sp) L(fl::beam_slab_kernel<2, false, 3, 10, true, true>); else L(fl::beam_slab_kernel<2, false, 3, 10, false, true>); }
-                else if (q.beam_spec && p == 4) { if (sp) L(fl::beam_slab_kernel<2, false, 4, 10, true, true>); else L(fl::beam_slab_kernel<2, false, 4, 10, false, true>); }
-                else if (q.beam_spec && p == 5) { if (sp) L(fl::beam_slab_kernel<2, false, 5, 10, true, true>); else L(fl::beam_slab_kernel<2, false, 5, 10, false, true>); }
-                else if (sp) L(fl::beam_slab_kernel<A, false, 0, 0, true, true>);
-                else L(fl::beam_slab_kernel<A, false, 0, 0, false, true>);
-            } else if (K.arith && q.wide) {
-                if (any_q0) { HIPCHK(big_lds((const void*)fl::beam_wide_kernel<A, true, true>, q.WL.total)); hipLaunchKernelGGL((fl::beam_wide_kernel<A, true, true>), dim3(slots), dim3(64), q.WL.total, st, a); }
-                else { HIPCHK(big_lds((const void*)fl::beam_wide_kernel<A, false, true>, q.WL.total)); hipLaunchKernelGGL((fl::beam_wide_kernel<A, false, true>), dim3(slots), dim3(64), q.WL.total, st, a); }
-            } else if (K.arith) {
-                HIPCHK(big_lds((const void*)fl::beam_kernel<A, true>, q.LY.total));
-                hipLaunchKernelGGL((fl::beam_kernel<A, true>), dim3(slots), dim3(64), q.LY.total, st, a);
-            } else if (q.wide) {
-                if (any_q0) { HIPCHK(big_lds((const void*)fl::beam_wide_kernel<A, true>, q.WL.total)); hipLaunchKernelGGL((fl::beam_wide_kernel<A, true>), dim3(slots), dim3(64), q.WL.total, st, a); }
-                else { HIPCHK(big_lds((const void*)fl::beam_wide_kernel<A, false>, q.WL.total)); hipLaunchKernelGGL((fl::beam_wide_kernel<A, false>), dim3(slots), dim3(64), q.WL.total, st, a); }
-            } else if (q.slab) {
-                const bool sp = a.stop_at != nullptr || wait_tried != 0;      // speculative stage: the instances that can drop a job
-                if (any_q0) { if (sp) hipLaunchKernelGGL((fl::beam_slab_kernel<A, true, 0, 0, true>), dim3(slots), dim3(64), q.SL.total, st, a);
-                              else hipLaunchKernelGGL((fl::beam_slab_kernel<A, true>), dim3(slots), dim3(64), q.SL.total, st, a); }
-                else if (q.beam_spec && p == 2) { if (sp) hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 2, 10, true>), dim3(slots), dim3(64), q.SL.total, st, a);
-                                                  else hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 2, 10>), dim3(slots), dim3(64), q.SL.total, st, a); }
-                else if (q.beam_spec && p == 3) { if (sp) hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 3, 10, true>), dim3(slots), dim3(64), q.SL.total, st, a);
-                                                  else hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 3, 10>), dim3(slots), dim3(64), q.SL.total, st, a); }
-                else if (q.beam_spec && p == 4) { if (sp) hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 4, 10, true>), dim3(slots), dim3(64), q.SL.total, st, a);
-                                                  else hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 4, 10>), dim3(slots), dim3(64), q.SL.total, st, a); }
-                else if (q.beam_spec && p == 5) { if (sp) hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 5, 10, true>), dim3(slots), dim3(64), q.SL.total, st, a);
-                                                  else hipLaunchKernelGGL((fl::beam_slab_kernel<2, false, 5, 10>), dim3(slots), dim3(64), q.SL.total, st, a); }
-                else if (sp) hipLaunchKernelGGL((fl::beam_slab_kernel<A, false, 0, 0, true>), dim3(slots), dim3(64), q.SL.total, st, a);
-                else hipLaunchKernelGGL((fl::beam_slab_kernel<A, false>), dim3(slots), dim3(64), q.SL.total, st, a);
-            } else {
-                HIPCHK(big_lds((const void*)fl::beam_kernel<A>, q.LY.total));
-                hipLaunchKernelGGL(fl::beam_kernel<A>, dim3(slots), dim3(64), q.LY.total, st, a);
-            }
-            return 0;
-        };
         if (gated) {          // ploidies few blocks need start when ploidy 2 has left the chip: by the time their jobs run, the stop rule of most
                               // blocks is known and the jobs are dropped at dequeue or within 64 reads
             if (!ctx->ev_gate[g]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_gate[g], hipEventDisableTiming));
             HIPCHK(hipStreamWaitEvent(st, ctx->ev_gate[g], 0));
         }
         const int t = T.begin(K_BEAM, st);
-        { const int frc = fire(slots); if (frc) return frc; }
+        HIPCHK(launch_beam<A>(q, K.arith != 0, S.any_q0, a.stop_at != nullptr || wait_tried != 0, slots, st, a));      // (a speculative stage or the tail launch: the instances that can drop a job)
         T.end(t);
-        HIPCHK(hipGetLastError());
         ctx->timing.beam_launches++;
         if (!wait_tried && stage.size() > 1 && ((stage[0] <= 2 && p == 2) || (stage[0] == 4 && p == 4))) {          // (the beam search of ploidy 2 opens the gate; ploidy 3 measured worse)
             if (!ctx->ev_gate[g]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_gate[g], hipEventDisableTiming));
@@ -686,7 +754,7 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
         for (uint32_t g = 0; g < G; ++g) {
             const uint32_t nj = group_off[g + 1] - group_off[g];
             if (nj == 0) continue;
-            const uint32_t* gjobs = d_jobs + group_off[g];
+            const uint32_t* gjobs = D.jobs + group_off[g];
             hipStream_t s0 = ls[g * W];
             if (stage.size() > 1) {                          // the stage's extra lanes start after the group's previous stop rule
                 HIPCHK(hipEventRecord(ctx->ev_fork[g * W], s0));
@@ -697,9 +765,9 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
                 const uint32_t p = stage[j], lane = g * W + j;
                 const PloidyPlan& q = plan[p];
                 hipStream_t st = ls[lane];
-                uint32_t* gqueue = d_queue + 2 * ((size_t)lane * P + (p - 1));     // [0] beam, [1] optimise: one counter pair per (lane, ploidy), zeroed once before the
+                uint32_t* gqueue = D.queue + 2 * ((size_t)lane * P + (p - 1));     // [0] beam, [1] optimise: one counter pair per (lane, ploidy), zeroed once before the
                                                                                     // loop (a memset between persistent launches is a fill KERNEL that waits for wave slots)
-                uint8_t* lane_part = d_beam_part + (uint64_t)j * (tot_reads + 16);
+                uint8_t* lane_part = D.beam_part + (uint64_t)j * (tot_reads + 16);
                 // ---- beam search -----------------------------------------------------------------------------------------
                 const bool tail_here = tail_p && p == tail_p;          // this ploidy's beam launch was queued with the stage below: join it
                 if (tail_here) { HIPCHK(hipStreamWaitEvent(st, ctx->ev_tail_join[g], 0)); lane_part = tail_part; }
@@ -711,61 +779,34 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
                 // ---- optimise + MEC stats ------------------------------------------------------------------------------
                 {
                     const uint32_t slots = std::min(q.opt_slots, nj);
-                    const uint32_t threads = q.threads;
-                    const size_t lds = q.opt_lds;
                     fl::OptArgs a{};
                     a.bs = bs; a.job_block = gjobs; a.n_jobs = nj; a.ploidy = p; a.max_ploidy = P; a.span_max = span_max; a.n_max = n_max;
-                    a.queue_head = gqueue + 1; a.blk_done = d_done; a.eps = prm->epsilon;
-                    a.part_in = lane_part; a.part_out = d_planes + (uint64_t)(p - 1) * tot_reads;
-                    a.hist_pool = (uint64_t*)(ctx->opt_hist.as<char>() + sl_ohist * lane); a.dist_pool = (double*)(ctx->opt_dist.as<char>() + sl_odist * lane);
-                    a.cand_gain_pool = (uint64_t*)(ctx->opt_gain.as<char>() + sl_ogain * lane); a.cand_key_pool = (uint32_t*)(ctx->opt_key.as<char>() + sl_okey * lane);
-                    a.moves_pool = (uint32_t*)(ctx->opt_moves.as<char>() + sl_omoves * lane); a.cand_cap = q.cand_cap;
-                    a.mec = d_mec; a.num_alleles = d_na; a.iters = d_iters;
-                    a.prof = (unsigned long long*)(d_diag + 4);
+                    a.queue_head = gqueue + 1; a.blk_done = D.done; a.eps = prm->epsilon;
+                    a.part_in = lane_part; a.part_out = D.planes + (uint64_t)(p - 1) * tot_reads;
+                    a.hist_pool = (uint64_t*)(ctx->opt_hist.as<char>() + sl.ohist * lane); a.dist_pool = (double*)(ctx->opt_dist.as<char>() + sl.odist * lane);
+                    a.cand_gain_pool = (uint64_t*)(ctx->opt_gain.as<char>() + sl.ogain * lane); a.cand_key_pool = (uint32_t*)(ctx->opt_key.as<char>() + sl.okey * lane);
+                    a.moves_pool = (uint32_t*)(ctx->opt_moves.as<char>() + sl.omoves * lane); a.cand_cap = q.cand_cap;
+                    a.mec = D.mec; a.num_alleles = D.na; a.iters = D.iters;
+                    a.prof = (unsigned long long*)(D.diag + 4);
                     a.fuse_select = stage.size() == 1 ? 1 : 0;
                     a.stopping_heuristic = prm->stopping_heuristic; a.mec_threshold = mec_threshold(prm, p);
-                    a.blk_done_w = d_done; a.best_ploidy = d_best; a.tried = d_tried;
+                    a.blk_done_w = D.done; a.best_ploidy = D.best; a.tried = D.tried;
                     a.release_tried = tail_p != 0 ? 1u : 0u;
                     a.pm_lds_off = q.pm_lds_off;
                     // (a plan with ANY speculative stage publishes ready bits and stop_at from every stage: a later stage's stop rule compares with these MEC values)
                     if (K.arith) {
                         a.cell_ord = ctx->cur_ord; a.cell_ord_off = ctx->cur_ord_off;
-                        char* base = ctx->arith_pool.as<char>() + sl_arith * lane;
-                        a.sort_cap = sort_cap_of(p); a.fx_ctrl = fx_ctrl; a.fx_slot = fx_slot; a.fx_lds_off = q.fx_lds_off; a.fx_tags = q.fx_tags; a.fx_replay = K.arith_replay; a.fk_lds_off = q.fk_lds_off;
+                        char* base = ctx->arith_pool.as<char>() + sl.arith * lane;
+                        a.sort_cap = sort_cap_of(p, span_max); a.fx_ctrl = fx_ctrl; a.fx_slot = fx_slot; a.fx_lds_off = q.fx_lds_off; a.fx_tags = q.fx_tags; a.fx_replay = K.arith_replay; a.fk_lds_off = q.fk_lds_off;
                         a.fk_pool = (uint64_t*)base; base += (uint64_t)slots * p * span_max * 8;
                         a.sk_pool = (uint64_t*)base; base += (uint64_t)slots * a.sort_cap * 8;
                         a.sp_pool = (uint32_t*)base; base += ((uint64_t)slots * a.sort_cap * 4 + 15) & ~(uint64_t)15;
                         a.fx_pool = (uint8_t*)base; base += (((uint64_t)slots * p * 2 * fx_bytes) + 15) & ~(uint64_t)15;
                         a.ol_pool = (uint32_t*)base;
                     }
-                    if (W > 1) { a.stop_at = d_stop; a.ready = d_ready; for (uint32_t q2 = 2; q2 <= P; ++q2) a.thresholds[q2] = mec_threshold(prm, q2); }
+                    if (W > 1) { a.stop_at = D.stop; a.ready = D.ready; for (uint32_t q2 = 2; q2 <= P; ++q2) a.thresholds[q2] = mec_threshold(prm, q2); }
                     int t = T.begin(K_OPT, st);
-                    auto launch = [&](auto kern) -> hipError_t {
-                        if (lds > 48 * 1024) { hipError_t e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e2 != hipSuccess) return e2; }
-                        hipLaunchKernelGGL(kern, dim3(slots), dim3(threads), lds, st, a);
-                        return hipGetLastError();
-                    };
-                    hipError_t le;
-                    // reference arithmetic, 512 threads, histogram in LDS, biallelic, ploidy <= 5 (every BASELINE config at the CLI's defaults): ploidy-specialised instances
-                    // (round 6: the per-partition loops unroll, `pair / p` is a multiplication); four waves per SIMD (128 VGPRs) where LDS allows two workgroups per CU anyway
-                    const bool arith_two_wg = K.arith && q.hl && threads == 512 && std::min<size_t>((156 * 1024) / (lds + 8 * 1024), 2048 / threads) <= 2 && !K.arith_ow6;
-                    if (K.arith && q.hl && threads == 512 && A == 2 && p <= 5 && !K.no_specialized) {
-                        if (arith_two_wg) le = p == 1 ? launch(fl::optimize_kernel<2, true, 512, 1, true, 4>) : p == 2 ? launch(fl::optimize_kernel<2, true, 512, 2, true, 4>) : p == 3 ? launch(fl::optimize_kernel<2, true, 512, 3, true, 4>)
-                                             : p == 4 ? launch(fl::optimize_kernel<2, true, 512, 4, true, 4>) : launch(fl::optimize_kernel<2, true, 512, 5, true, 4>);
-                        else le = p == 1 ? launch(fl::optimize_kernel<2, true, 512, 1, true>) : p == 2 ? launch(fl::optimize_kernel<2, true, 512, 2, true>) : p == 3 ? launch(fl::optimize_kernel<2, true, 512, 3, true>)
-                                : p == 4 ? launch(fl::optimize_kernel<2, true, 512, 4, true>) : launch(fl::optimize_kernel<2, true, 512, 5, true>);
-                    }
-                    else if (arith_two_wg) le = launch(fl::optimize_kernel<A, true, 512, 0, true, 4>);      // (LDS allows two workgroups per CU: four waves per SIMD, 128 VGPRs)
-                    else if (K.arith && q.hl) le = threads == 1024 ? launch(fl::optimize_kernel<A, true, 1024, 0, true>) : threads == 512 ? launch(fl::optimize_kernel<A, true, 512, 0, true>) : launch(fl::optimize_kernel<A, true, 128, 0, true>);
-                    else if (K.arith) le = threads == 1024 ? launch(fl::optimize_kernel<A, false, 1024, 0, true>) : threads == 512 ? launch(fl::optimize_kernel<A, false, 512, 0, true>) : launch(fl::optimize_kernel<A, false, 128, 0, true>);
-                    else if (q.opt_spec && threads == 1024)
-                        le = p == 1 ? launch(fl::optimize_kernel<2, true, 1024, 1>) : p == 2 ? launch(fl::optimize_kernel<2, true, 1024, 2>) : p == 3 ? launch(fl::optimize_kernel<2, true, 1024, 3>)
-                           : p == 4 ? launch(fl::optimize_kernel<2, true, 1024, 4>) : launch(fl::optimize_kernel<2, true, 1024, 5>);
-                    else if (q.opt_spec)
-                        le = p == 1 ? launch(fl::optimize_kernel<2, true, 512, 1>) : p == 2 ? launch(fl::optimize_kernel<2, true, 512, 2>) : p == 3 ? launch(fl::optimize_kernel<2, true, 512, 3>)
-                           : p == 4 ? launch(fl::optimize_kernel<2, true, 512, 4>) : launch(fl::optimize_kernel<2, true, 512, 5>);
-                    else if (q.hl) le = threads == 1024 ? launch(fl::optimize_kernel<A, true, 1024>) : threads == 512 ? launch(fl::optimize_kernel<A, true, 512>) : launch(fl::optimize_kernel<A, true, 128>);
-                    else    le = threads == 1024 ? launch(fl::optimize_kernel<A, false, 1024>) : threads == 512 ? launch(fl::optimize_kernel<A, false, 512>) : launch(fl::optimize_kernel<A, false, 128>);
+                    const hipError_t le = launch_optimize<A>(q, K, slots, st, a);
                     T.end(t);
                     if (le != hipSuccess) return fail(FLORIA_E_DEVICE, std::string("optimize_kernel launch: ") + hipGetErrorString(le));
                     ctx->timing.optimize_launches++;
@@ -774,7 +815,7 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
                     if (!ctx->tstream[g]) HIPCHK(hipStreamCreateWithFlags(&ctx->tstream[g], hipStreamNonBlocking));
                     if (!ctx->ev_tail_join[g]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_tail_join[g], hipEventDisableTiming));
                     HIPCHK(hipStreamWaitEvent(ctx->tstream[g], ctx->ev_tail[g], 0));
-                    const int brc = beam_launch(stages.back(), g, nj, gjobs, tail_p, lane, ctx->tstream[g], d_queue + 2 * ((size_t)lane * P + (tail_p - 1)), tail_part, p);
+                    const int brc = beam_launch(stages.back(), g, nj, gjobs, tail_p, lane, ctx->tstream[g], D.queue + 2 * ((size_t)lane * P + (tail_p - 1)), tail_part, p);
                     if (brc) return brc;
                     HIPCHK(hipEventRecord(ctx->ev_tail_join[g], ctx->tstream[g]));
                 }
@@ -786,7 +827,7 @@ int run_phase(floria_hip_ctx* ctx, bool any_q0, const fl::BlockSet& bs, const st
                 fl::SelectArgs s{};
                 s.job_block = gjobs; s.n_jobs = nj; s.ploidy = p; s.max_ploidy = P; s.stopping_heuristic = prm->stopping_heuristic; s.eps = prm->epsilon;
                 s.mec_threshold = mec_threshold(prm, p);
-                s.mec = d_mec; s.num_alleles = d_na; s.iters = d_iters; s.blk_done = d_done; s.best_ploidy = d_best; s.tried = d_tried;
+                s.mec = D.mec; s.num_alleles = D.na; s.iters = D.iters; s.blk_done = D.done; s.best_ploidy = D.best; s.tried = D.tried;
                 s.clear_from = (j + 1 == stage.size()) ? 1 : 0;      // last select of a speculative stage: forget the ploidies beyond `tried`
                 s.stage_last = stage.back();
                 int t = T.begin(K_SEL, s0);
@@ -1657,6 +1698,84 @@ struct Trace {
     void mark(const char* what) const { if (on) fprintf(stderr, "[floria_hip trace] %8.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what); }
 };
 
+// job groups (longest-first inside each group).  Resident inputs: dealt round-robin so every group sees the same size mix.
+// Chunked inputs (cells still arriving): group g = the blocks of chunk g, whose stream waits for the chunk's event (group_ev[g]).
+// Reorders jobs (longest first) group after group and returns where each group starts (G + 1 offsets).
+std::vector<uint32_t> job_groups(const floria_hip_ctx* ctx, const S1Contigs& SC, bool chunked, const std::vector<uint32_t>& bc, std::vector<uint32_t>& jobs,
+                                 hipEvent_t* group_ev) {
+    // (measured, config 4, resident: one group wins while a stage has less than three rounds of jobs — 750 / 1000 / 1500 contigs: 55 / 61.5 / 80.5 ms against
+    // 58.7 / 68 / 82 ms with two groups — two groups win from there: 2000 contigs 96.4 against 99.4 ms.  End of round 4 (profiles/r04_groups_ab.txt), ms per
+    // step with 1 / 2 / 3 / 4 groups: 7 249 blocks 51.6 / 55.2 / 51.4 / -, 10 875 blocks 67.8 / 66.7 / 65.3 / -, 14 503 blocks 81.6 / 78.8 / 75.9 or 79.3 / 78.4-79.1:
+    // three groups are 3.7 % faster in five runs of seven and level in the other two (the three chains interleave in one of two patterns); the pipelined call,
+    // which has its own three chunk groups, does not change.  Round 5 (profiles/r05_groups_ab.txt; box A, three interleaved runs): 2 groups 79.5 / 79.6 / 80.2,
+    // 3 groups 77.3 / 76.1 / 77.2, 4 groups with half-size grids 78.9 / 79.3 / 79.2, an equal share of the wave slots per group (3 x 1 366) 81.8-82.2; box B, in the
+    // default bench flow and resident-only: 2 groups 79.9-80.3 (six runs), 3 groups 80.3 / 80.7 / 79.8 / 79.8 / 77.5 / 78.3; 1500 contigs 64.5 against 67.8 (2) and
+    // 68.6 (1).  Three groups land on the level of two or 3 % below it, never above by more than the noise -> three from 40 x CUs blocks on (round 4 kept two for
+    // the per-launch roofline fraction, which is not what a step costs).  Unequal groups (dealing weights 10:8:6 .. 14:8:2) do not pin the good pattern (78.4-80.9).
+    uint32_t G = ctx->knobs.groups ? ctx->knobs.groups : (jobs.size() >= (size_t)ctx->n_cu * 40 ? 3 : 1);
+    G = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(G, floria_hip_ctx::MAX_GROUPS), (uint32_t)(jobs.size() / 1024)));
+    if (ctx->hw_queues < 5 && !ctx->knobs.groups) G = std::min<uint32_t>(G, 2);
+    // chunked: consecutive chunks may share a job group (SC.chunk_groups), which then starts when its LAST chunk has landed
+    std::vector<uint32_t> chunk_group;
+    if (chunked) {
+        const uint32_t nc = std::min<uint32_t>(SC.n_chunks, floria_hip_ctx::MAX_GROUPS);
+        G = SC.chunk_groups ? std::min<uint32_t>(SC.chunk_groups, nc) : nc;
+        if (ctx->hw_queues < 5) G = std::min<uint32_t>(G, 2);          // (groups on shared hardware queues serialise: two at most)
+        chunk_group.resize(SC.n_chunks);
+        for (uint32_t c = 0; c < SC.n_chunks; ++c) {
+            const uint32_t cc = std::min(c, nc - 1);
+            // ends_apart: the first chunk is a group of its own (it starts while the rest is still arriving and is too small to own every wave slot), so is the last
+            chunk_group[c] = SC.ends_apart && G == 3 && nc >= 3 ? (cc == 0 ? 0u : cc == nc - 1 ? 2u : 1u) : std::min<uint32_t>((uint32_t)((uint64_t)cc * G / nc), G - 1);
+            group_ev[chunk_group[c]] = SC.chunk_ev[cc];
+        }
+    }
+    std::vector<uint32_t> group_off(G + 1, 0);
+    if (chunked) {
+        std::vector<uint32_t> dealt; dealt.reserve(jobs.size());
+        for (uint32_t g = 0; g < G; ++g) { for (uint32_t b : jobs) if (chunk_group[SC.contig_chunk[bc[b]]] == g) dealt.push_back(b); group_off[g + 1] = (uint32_t)dealt.size(); }
+        jobs.swap(dealt);
+    } else if (G > 1) {
+        std::vector<uint32_t> dealt; dealt.reserve(jobs.size());
+        for (uint32_t g = 0; g < G; ++g) { for (size_t j = g; j < jobs.size(); j += G) dealt.push_back(jobs[j]); group_off[g + 1] = (uint32_t)dealt.size(); }
+        jobs.swap(dealt);
+    } else group_off[1] = (uint32_t)jobs.size();
+    return group_off;
+}
+
+// ploidy stages (run_phase): one ploidy per stage unless the batch is too small to fill the chip with (block, ploidy) jobs
+std::vector<std::vector<uint32_t>> ploidy_stages(const floria_hip_ctx* ctx, const floria_params* prm, size_t n_jobs, uint32_t G) {
+    const uint32_t P = prm->max_ploidy;
+    std::vector<std::vector<uint32_t>> stages;
+    int spec = ctx->knobs.speculate;
+    const bool slab_path = P * prm->beam <= 63 && !ctx->knobs.beam_path;          // the wide-beam kernels own whole CUs: nothing to gain there
+    // (measured on config-4 shards, resident, with the gated high ploidies and the early stop-rule flags of run_phase; ms for speculate = 0 / 1 / 2:
+    //   915 blocks 37.6 / 21.3 / 24.3   1822: 40.4 / 24.8 / 27.1   2724: 44.1 / 32.2 / 32.7   3636: 48.0 / 46.5 / 36.8   4543: 50.9 / 57.7 / 44.9
+    //   5455: 55.5 / 69.1 / 50.9   6348: 58.7 / 80.8 / 56.9   7249: 61.6 / - / 62.5   14503: 98.6 / 141-155 / 115.5)
+    // round 4, faster beam steps (scripts/shard_sweep.py, profiles/r04_shard_sweep.txt; ms for speculate = 0 / 1 / 2):
+    //   915: 32.7 / 19.8 / 26.6   1822: 36.1 / 23.0 / 29.5   2724: 40.6 / 31.3 / 34.9   3636: 43.2 / 36.1 / 39.5   4543: 46.6 / 42.2 / 44.2
+    //   5455: 50.4 / 50.3 / 48.9   6348: 52.7 / 56.0 / 53.3   7249: 56.8 / 63.7 / 58.1
+    // -> every ploidy at once up to 18 x CUs blocks, {1,2,3} then {4..P} up to 23 x CUs, one ploidy per stage above
+    if (spec < 0) spec = !(slab_path && P >= 3) ? 0 : n_jobs <= (size_t)ctx->n_cu * 18 ? 1 : (n_jobs <= (size_t)ctx->n_cu * 23 && P >= 4) ? 2 : 0;
+    if (P * G > floria_hip_ctx::MAX_LANES || P < 3) spec = 0;
+    // a speculative stage's lanes wait on each other's events: with more lanes than hardware queues (GPU_MAX_HW_QUEUES, 12 in our hosts, minus the main,
+    // copy and flatten streams) they share queues and the gates serialise the stage (measured: 250 contigs in 3 / 4 / 5 chunk groups 94 / 141 / 187 ms against 32)
+    // (floria_hip_create measured how many streams really run side by side: hw_queues; main, copy and flatten streams take up to three of them)
+    // With GPU_MAX_HW_QUEUES=12 the probe sees 6 spinning kernels side by side on an MI355X, and stages of up to 10 lanes measured fine (round 2: 250
+    // contigs 24-26 ms against 38 without); with the runtime's default of 4 queues it sees 4 or fewer, and there the gated lanes serialise (3-8x).
+    const uint32_t lanes_ok = ctx->hw_queues >= 5 ? 10u : (ctx->hw_queues > 1 ? ctx->hw_queues - 1 : 1u);
+    if (ctx->knobs.speculate < 0 && spec) { const uint32_t w = spec == 1 ? P : std::max<uint32_t>(std::min(3u, P), P > 3 ? P - 3 : 0); if (w * G > lanes_ok) spec = 0; }
+    if (spec == 3 && P >= 5) {          // {1}{2}{3}{4..P}: only the ploidies few blocks reach run side by side
+        for (uint32_t p = 1; p <= 3; ++p) stages.push_back({p});
+        stages.emplace_back(); for (uint32_t p = 4; p <= P; ++p) stages.back().push_back(p);
+    }
+    else if (spec == 1) { stages.emplace_back(); for (uint32_t p = 1; p <= P; ++p) stages.back().push_back(p); }
+    else if (spec == 2) { stages.emplace_back(); for (uint32_t p = 1; p <= std::min(3u, P); ++p) stages.back().push_back(p);
+                          if (P > 3) { stages.emplace_back(); for (uint32_t p = 4; p <= P; ++p) stages.back().push_back(p); } }
+    else for (uint32_t p = 1; p <= P; ++p) stages.push_back({p});
+    if (spec == 3 && P < 5) { stages.clear(); for (uint32_t p = 1; p <= P; ++p) stages.push_back({p}); }
+    return stages;
+}
+
 int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig, const uint32_t* blk_start, const uint32_t* blk_end,
             uint32_t n_blocks, const floria_params* prm, floria_block_result** out) {
     const uint32_t n_contigs = (uint32_t)SC.cdev.size();
@@ -1680,14 +1799,11 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
         bc[b] = ci;
     }
     const std::vector<fl::ContigDev>& cdev = SC.cdev;
-    struct Seg { size_t off, bytes; };
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { Seg s{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return s; };
-    const Seg s_cdev = seg(sizeof(fl::ContigDev) * std::max(1u, n_contigs)), s_bc = seg(4ull * n_blocks + 4), s_bs = seg(4ull * n_blocks + 4),
-              s_be = seg(4ull * n_blocks + 4), s_p0 = seg(4ull * n_blocks + 4), s_sp = seg(4ull * n_blocks + 4), s_cnt = seg(4ull * n_blocks + 4),
-              s_bytes = seg(8ull * n_blocks + 8), s_roff = seg(8ull * (n_blocks + 1));
-    int rc = ctx->misc0.ensure(cursor + 256); if (rc) return rc;
-    char* M0 = ctx->misc0.as<char>();
+    Carve C0;
+    const Seg s_cdev = C0.seg(sizeof(fl::ContigDev) * std::max(1u, n_contigs)), s_bc = C0.seg(4ull * n_blocks + 4), s_bs = C0.seg(4ull * n_blocks + 4),
+              s_be = C0.seg(4ull * n_blocks + 4), s_p0 = C0.seg(4ull * n_blocks + 4), s_sp = C0.seg(4ull * n_blocks + 4), s_cnt = C0.seg(4ull * n_blocks + 4),
+              s_bytes = C0.seg(8ull * n_blocks + 8), s_roff = C0.seg(8ull * (n_blocks + 1));
+    int rc = C0.place(ctx->misc0); if (rc) return rc;
     EventTimer T(ctx->stream);
     // the call's small transfers go through the context's host mailbox (HostBox): up by a copy kernel on the main stream, down by the kernel's own stores
     static_assert(sizeof(fl::ContigDev) % 4 == 0, "box_copy_kernel moves 4-byte words");
@@ -1705,18 +1821,18 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
         return hipGetLastError();
     };
     int th = T.begin(K_H2D);
-    HIPCHK(box_up(M0 + s_cdev.off, cdev.data(), sizeof(fl::ContigDev) * n_contigs, bx_cdev));
+    HIPCHK(box_up(C0.at(s_cdev), cdev.data(), sizeof(fl::ContigDev) * n_contigs, bx_cdev));
     if (n_blocks) {
-        HIPCHK(box_up(M0 + s_bc.off, bc.data(), 4ull * n_blocks, bx_bc));
-        HIPCHK(box_up(M0 + s_bs.off, blk_start, 4ull * n_blocks, bx_bs));
-        HIPCHK(box_up(M0 + s_be.off, blk_end, 4ull * n_blocks, bx_be));
+        HIPCHK(box_up(C0.at(s_bc), bc.data(), 4ull * n_blocks, bx_bc));
+        HIPCHK(box_up(C0.at(s_bs), blk_start, 4ull * n_blocks, bx_bs));
+        HIPCHK(box_up(C0.at(s_be), blk_end, 4ull * n_blocks, bx_be));
     }
     T.end(th);
     fl::ScanArgs sa{};
-    sa.contigs = (const fl::ContigDev*)(M0 + s_cdev.off);
-    sa.blk_contig = (const uint32_t*)(M0 + s_bc.off); sa.blk_start = (const uint32_t*)(M0 + s_bs.off); sa.blk_end = (const uint32_t*)(M0 + s_be.off);
+    sa.contigs = C0.at<const fl::ContigDev>(s_cdev);
+    sa.blk_contig = C0.at<const uint32_t>(s_bc); sa.blk_start = C0.at<const uint32_t>(s_bs); sa.blk_end = C0.at<const uint32_t>(s_be);
     sa.n_blocks = n_blocks; sa.max_ploidy = P;
-    sa.cnt = (uint32_t*)(M0 + s_cnt.off); sa.pos0 = (uint32_t*)(M0 + s_p0.off); sa.span = (uint32_t*)(M0 + s_sp.off); sa.bytes = (uint64_t*)(M0 + s_bytes.off);
+    sa.cnt = C0.at<uint32_t>(s_cnt); sa.pos0 = C0.at<uint32_t>(s_p0); sa.span = C0.at<uint32_t>(s_sp); sa.bytes = C0.at<uint64_t>(s_bytes);
     sa.h_cnt = (uint32_t*)(ctx->box.d + bx_cnt); sa.h_span = (uint32_t*)(ctx->box.d + bx_span); sa.h_bytes = (uint64_t*)(ctx->box.d + bx_bytes);
     std::vector<uint32_t> cnt(n_blocks, 0), span(n_blocks, 0);
     std::vector<uint64_t> blk_bytes(n_blocks, 0), roff(n_blocks + 1, 0);
@@ -1743,77 +1859,10 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     for (uint32_t b = 0; b < n_blocks; ++b) if (cnt[b]) jobs.push_back(b);
     std::stable_sort(jobs.begin(), jobs.end(), [&](uint32_t a, uint32_t b2) { return cnt[a] > cnt[b2]; });
     TR.mark("jobs sorted");
-    // job groups (longest-first inside each group).  Resident inputs: dealt round-robin so every group sees the same size mix.
-    // Chunked inputs (cells still arriving): group g = the blocks of chunk g, whose stream waits for the chunk's event.
     const bool chunked = SC.chunk_ev != nullptr && SC.n_chunks > 1;
-    // (measured, config 4, resident: one group wins while a stage has less than three rounds of jobs — 750 / 1000 / 1500 contigs: 55 / 61.5 / 80.5 ms against
-    // 58.7 / 68 / 82 ms with two groups — two groups win from there: 2000 contigs 96.4 against 99.4 ms.  End of round 4 (profiles/r04_groups_ab.txt), ms per
-    // step with 1 / 2 / 3 / 4 groups: 7 249 blocks 51.6 / 55.2 / 51.4 / -, 10 875 blocks 67.8 / 66.7 / 65.3 / -, 14 503 blocks 81.6 / 78.8 / 75.9 or 79.3 / 78.4-79.1:
-    // three groups are 3.7 % faster in five runs of seven and level in the other two (the three chains interleave in one of two patterns); the pipelined call,
-    // which has its own three chunk groups, does not change.  Round 5 (profiles/r05_groups_ab.txt; box A, three interleaved runs): 2 groups 79.5 / 79.6 / 80.2,
-    // 3 groups 77.3 / 76.1 / 77.2, 4 groups with half-size grids 78.9 / 79.3 / 79.2, an equal share of the wave slots per group (3 x 1 366) 81.8-82.2; box B, in the
-    // default bench flow and resident-only: 2 groups 79.9-80.3 (six runs), 3 groups 80.3 / 80.7 / 79.8 / 79.8 / 77.5 / 78.3; 1500 contigs 64.5 against 67.8 (2) and
-    // 68.6 (1).  Three groups land on the level of two or 3 % below it, never above by more than the noise -> three from 40 x CUs blocks on (round 4 kept two for
-    // the per-launch roofline fraction, which is not what a step costs).  Unequal groups (dealing weights 10:8:6 .. 14:8:2) do not pin the good pattern (78.4-80.9).
-    uint32_t G = ctx->knobs.groups ? ctx->knobs.groups : (jobs.size() >= (size_t)ctx->n_cu * 40 ? 3 : 1);
-    G = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(G, floria_hip_ctx::MAX_GROUPS), (uint32_t)(jobs.size() / 1024)));
-    if (ctx->hw_queues < 5 && !ctx->knobs.groups) G = std::min<uint32_t>(G, 2);
-    // chunked: consecutive chunks may share a job group (SC.chunk_groups), which then starts when its LAST chunk has landed
-    std::vector<uint32_t> chunk_group;
     hipEvent_t group_ev[floria_hip_ctx::MAX_GROUPS] = {};
-    if (chunked) {
-        const uint32_t nc = std::min<uint32_t>(SC.n_chunks, floria_hip_ctx::MAX_GROUPS);
-        G = SC.chunk_groups ? std::min<uint32_t>(SC.chunk_groups, nc) : nc;
-        if (ctx->hw_queues < 5) G = std::min<uint32_t>(G, 2);          // (groups on shared hardware queues serialise: two at most)
-        chunk_group.resize(SC.n_chunks);
-        for (uint32_t c = 0; c < SC.n_chunks; ++c) {
-            const uint32_t cc = std::min(c, nc - 1);
-            // ends_apart: the first chunk is a group of its own (it starts while the rest is still arriving and is too small to own every wave slot), so is the last
-            chunk_group[c] = SC.ends_apart && G == 3 && nc >= 3 ? (cc == 0 ? 0u : cc == nc - 1 ? 2u : 1u) : std::min<uint32_t>((uint32_t)((uint64_t)cc * G / nc), G - 1);
-            group_ev[chunk_group[c]] = SC.chunk_ev[cc];
-        }
-    }
-    std::vector<uint32_t> group_off(G + 1, 0);
-    if (chunked) {
-        std::vector<uint32_t> dealt; dealt.reserve(jobs.size());
-        for (uint32_t g = 0; g < G; ++g) { for (uint32_t b : jobs) if (chunk_group[SC.contig_chunk[bc[b]]] == g) dealt.push_back(b); group_off[g + 1] = (uint32_t)dealt.size(); }
-        jobs.swap(dealt);
-    } else if (G > 1) {
-        std::vector<uint32_t> dealt; dealt.reserve(jobs.size());
-        for (uint32_t g = 0; g < G; ++g) { for (size_t j = g; j < jobs.size(); j += G) dealt.push_back(jobs[j]); group_off[g + 1] = (uint32_t)dealt.size(); }
-        jobs.swap(dealt);
-    } else group_off[1] = (uint32_t)jobs.size();
-    // ploidy stages (run_phase): one ploidy per stage unless the batch is too small to fill the chip with (block, ploidy) jobs
-    std::vector<std::vector<uint32_t>> stages;
-    {
-        int spec = ctx->knobs.speculate;
-        const bool slab_path = P * prm->beam <= 63 && !ctx->knobs.beam_path;          // the wide-beam kernels own whole CUs: nothing to gain there
-        // (measured on config-4 shards, resident, with the gated high ploidies and the early stop-rule flags of run_phase; ms for speculate = 0 / 1 / 2:
-        //   915 blocks 37.6 / 21.3 / 24.3   1822: 40.4 / 24.8 / 27.1   2724: 44.1 / 32.2 / 32.7   3636: 48.0 / 46.5 / 36.8   4543: 50.9 / 57.7 / 44.9
-        //   5455: 55.5 / 69.1 / 50.9   6348: 58.7 / 80.8 / 56.9   7249: 61.6 / - / 62.5   14503: 98.6 / 141-155 / 115.5)
-        // round 4, faster beam steps (scripts/shard_sweep.py, profiles/r04_shard_sweep.txt; ms for speculate = 0 / 1 / 2):
-        //   915: 32.7 / 19.8 / 26.6   1822: 36.1 / 23.0 / 29.5   2724: 40.6 / 31.3 / 34.9   3636: 43.2 / 36.1 / 39.5   4543: 46.6 / 42.2 / 44.2
-        //   5455: 50.4 / 50.3 / 48.9   6348: 52.7 / 56.0 / 53.3   7249: 56.8 / 63.7 / 58.1
-        // -> every ploidy at once up to 18 x CUs blocks, {1,2,3} then {4..P} up to 23 x CUs, one ploidy per stage above
-        if (spec < 0) spec = !(slab_path && P >= 3) ? 0 : jobs.size() <= (size_t)ctx->n_cu * 18 ? 1 : (jobs.size() <= (size_t)ctx->n_cu * 23 && P >= 4) ? 2 : 0;
-        if (P * G > floria_hip_ctx::MAX_LANES || P < 3) spec = 0;
-        // a speculative stage's lanes wait on each other's events: with more lanes than hardware queues (GPU_MAX_HW_QUEUES, 12 in our hosts, minus the main,
-        // copy and flatten streams) they share queues and the gates serialise the stage (measured: 250 contigs in 3 / 4 / 5 chunk groups 94 / 141 / 187 ms against 32)
-        // (floria_hip_create measured how many streams really run side by side: hw_queues; main, copy and flatten streams take up to three of them)
-        // With GPU_MAX_HW_QUEUES=12 the probe sees 6 spinning kernels side by side on an MI355X, and stages of up to 10 lanes measured fine (round 2: 250
-        // contigs 24-26 ms against 38 without); with the runtime's default of 4 queues it sees 4 or fewer, and there the gated lanes serialise (3-8x).
-        const uint32_t lanes_ok = ctx->hw_queues >= 5 ? 10u : (ctx->hw_queues > 1 ? ctx->hw_queues - 1 : 1u);
-        if (ctx->knobs.speculate < 0 && spec) { const uint32_t w = spec == 1 ? P : std::max<uint32_t>(std::min(3u, P), P > 3 ? P - 3 : 0); if (w * G > lanes_ok) spec = 0; }
-        if (spec == 3 && P >= 5) {          // {1}{2}{3}{4..P}: only the ploidies few blocks reach run side by side
-            for (uint32_t p = 1; p <= 3; ++p) stages.push_back({p});
-            stages.emplace_back(); for (uint32_t p = 4; p <= P; ++p) stages.back().push_back(p);
-        }
-        else if (spec == 1) { stages.emplace_back(); for (uint32_t p = 1; p <= P; ++p) stages.back().push_back(p); }
-        else if (spec == 2) { stages.emplace_back(); for (uint32_t p = 1; p <= std::min(3u, P); ++p) stages.back().push_back(p);
-                              if (P > 3) { stages.emplace_back(); for (uint32_t p = 4; p <= P; ++p) stages.back().push_back(p); } }
-        else for (uint32_t p = 1; p <= P; ++p) stages.push_back({p});
-        if (spec == 3 && P < 5) { stages.clear(); for (uint32_t p = 1; p <= P; ++p) stages.push_back({p}); }
-    }
+    const std::vector<uint32_t> group_off = job_groups(ctx, SC, chunked, bc, jobs, group_ev);
+    const std::vector<std::vector<uint32_t>> stages = ploidy_stages(ctx, prm, jobs.size(), (uint32_t)group_off.size() - 1);
     uint32_t stage_w = 1;
     for (auto& st : stages) stage_w = std::max<uint32_t>(stage_w, (uint32_t)st.size());
 
@@ -1822,26 +1871,25 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     rc = ensure_hash(ctx, span_max * nall); if (rc) return rc;
 
     // ---- device staging of the per-call arrays ----------------------------------------------------------------------
-    cursor = 0;
-    const Seg s_rids = seg(4ull * tot + 4), s_jobs = seg(4ull * jobs.size() + 4), s_planes = seg((uint64_t)P * tot + 16), s_bpart = seg((uint64_t)(stage_w + 1) * (tot + 16)),        // (+1: the plane of a last-stage beam launch that runs beside the optimise launch below it)
-              s_margin = seg(8ull * n_blocks * P + 16),
+    Carve C;
+    const Seg s_rids = C.seg(4ull * tot + 4), s_jobs = C.seg(4ull * jobs.size() + 4), s_planes = C.seg((uint64_t)P * tot + 16), s_bpart = C.seg((uint64_t)(stage_w + 1) * (tot + 16)),        // (+1: the plane of a last-stage beam launch that runs beside the optimise launch below it)
+              s_margin = C.seg(8ull * n_blocks * P + 16),
               // zero-initialised, contiguous (ONE memset): partition output, mec / num_alleles / iters, stop-rule state, queue counters, diagnostics
-              s_out = seg(tot + 16), s_mec = seg(8ull * n_blocks * P + 8), s_na = seg(8ull * n_blocks * P + 8), s_it = seg(4ull * n_blocks * P + 4),
-              s_done = seg(n_blocks + 4), s_best = seg(4ull * n_blocks + 4), s_tried = seg(4ull * n_blocks + 4), s_ready = seg(4ull * n_blocks + 4),
-              s_q = seg(8ull * floria_hip_ctx::MAX_LANES * FLORIA_MAX_PLOIDY + 16), s_diag = seg(16 + 8 * 64), s_steps = seg(16);
-    const size_t zero_bytes = cursor - s_out.off;
-    const Seg s_stop = seg(4ull * n_blocks + 4);             // speculative stages: smallest ploidy at which the stop rule is known to break, 0xffffffff = unknown
-    rc = ctx->misc.ensure(cursor + 256); if (rc) return rc;
-    char* M = ctx->misc.as<char>();
+              s_out = C.seg(tot + 16), s_mec = C.seg(8ull * n_blocks * P + 8), s_na = C.seg(8ull * n_blocks * P + 8), s_it = C.seg(4ull * n_blocks * P + 4),
+              s_done = C.seg(n_blocks + 4), s_best = C.seg(4ull * n_blocks + 4), s_tried = C.seg(4ull * n_blocks + 4), s_ready = C.seg(4ull * n_blocks + 4),
+              s_q = C.seg(8ull * floria_hip_ctx::MAX_LANES * FLORIA_MAX_PLOIDY + 16), s_diag = C.seg(16 + 8 * 64), s_steps = C.seg(16);
+    const size_t zero_bytes = C.cursor - s_out.off;
+    const Seg s_stop = C.seg(4ull * n_blocks + 4);             // speculative stages: smallest ploidy at which the stop rule is known to break, 0xffffffff = unknown
+    rc = C.place(ctx->misc); if (rc) return rc;
     th = T.begin(K_H2D);
-    HIPCHK(box_up(M0 + s_roff.off, roff.data(), 8ull * (n_blocks + 1), bx_roff));
-    if (!jobs.empty()) HIPCHK(box_up(M + s_jobs.off, jobs.data(), 4ull * jobs.size(), bx_jobs));
-    HIPCHK(hipMemsetAsync(M + s_out.off, 0, zero_bytes, ctx->stream));
-    if (stage_w > 1) HIPCHK(hipMemsetAsync(M + s_stop.off, 0xff, s_stop.bytes, ctx->stream));
+    HIPCHK(box_up(C0.at(s_roff), roff.data(), 8ull * (n_blocks + 1), bx_roff));
+    if (!jobs.empty()) HIPCHK(box_up(C.at(s_jobs), jobs.data(), 4ull * jobs.size(), bx_jobs));
+    HIPCHK(hipMemsetAsync(C.at(s_out), 0, zero_bytes, ctx->stream));
+    if (stage_w > 1) HIPCHK(hipMemsetAsync(C.at(s_stop), 0xff, s_stop.bytes, ctx->stream));
     const double inf = std::numeric_limits<double>::infinity();
     T.end(th);
     if (n_blocks) {
-        sa.roff = (const uint64_t*)(M0 + s_roff.off); sa.rids = (uint32_t*)(M + s_rids.off);
+        sa.roff = C0.at<const uint64_t>(s_roff); sa.rids = C.at<uint32_t>(s_rids);
         int tk = T.begin(K_SEL);
         hipLaunchKernelGGL(fl::block_reads_kernel<true>, dim3(n_blocks), dim3(64), 0, ctx->stream, sa);
         T.end(tk);
@@ -1852,10 +1900,10 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     }
 
     fl::BlockSet bs{};
-    bs.contigs = (const fl::ContigDev*)(M0 + s_cdev.off);
-    bs.blk_contig = (const uint32_t*)(M0 + s_bc.off); bs.blk_start = (const uint32_t*)(M0 + s_bs.off); bs.blk_end = (const uint32_t*)(M0 + s_be.off);
-    bs.blk_pos0 = (const uint32_t*)(M0 + s_p0.off); bs.blk_span = (const uint32_t*)(M0 + s_sp.off);
-    bs.blk_read_off = (const uint64_t*)(M0 + s_roff.off); bs.blk_read = (const uint32_t*)(M + s_rids.off); bs.n_blocks = n_blocks;
+    bs.contigs = C0.at<const fl::ContigDev>(s_cdev);
+    bs.blk_contig = C0.at<const uint32_t>(s_bc); bs.blk_start = C0.at<const uint32_t>(s_bs); bs.blk_end = C0.at<const uint32_t>(s_be);
+    bs.blk_pos0 = C0.at<const uint32_t>(s_p0); bs.blk_span = C0.at<const uint32_t>(s_sp);
+    bs.blk_read_off = C0.at<const uint64_t>(s_roff); bs.blk_read = C.at<const uint32_t>(s_rids); bs.n_blocks = n_blocks;
 
     // ---- reference-arithmetic mode: the iteration order of every read's position set (arith_kernel.h) --------------------------------
     ctx->cur_ord = nullptr; ctx->cur_ord_off = nullptr; ctx->cur_len_max = len_max;
@@ -1882,26 +1930,26 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     struct ResultGuard { floria_hip_ctx* c; floria_block_result* r; ~ResultGuard() { if (r) { sync_all(c); floria_hip_block_result_free(r); } } } guard{ctx, R};   // every early return below
     if (!R->best_ploidy || !R->ploidies_tried || !R->read_off || !R->read_id || !R->part || !R->mec) { return fail(FLORIA_E_NOMEM, "malloc"); }
     bool p1_shortcut = false;
+    const PhaseShape shape{bs, any_q0, (uint32_t)jobs.size(), tot, n_max, span_max};
+    const PhaseBufs bufs{C.at<const uint32_t>(s_jobs), C.at<uint8_t>(s_planes), C.at<uint8_t>(s_bpart), C.at<double>(s_mec), C.at<double>(s_na), C.at<uint32_t>(s_it),
+                         C.at<uint8_t>(s_done), C.at<uint32_t>(s_best), C.at<uint32_t>(s_tried), C.at<uint32_t>(s_stop), C.at<uint32_t>(s_ready), C.at<uint32_t>(s_q),
+                         C.at<double>(s_margin), C.at<uint32_t>(s_diag), C.at<unsigned long long>(s_steps)};
     auto run = nall == 2 ? run_phase<2> : run_phase<4>;
-    rc = run(ctx, any_q0, bs, jobs, group_off, (const uint32_t*)(M + s_jobs.off), tot, n_max, span_max, prm, (uint8_t*)(M + s_planes.off),
-             (uint8_t*)(M + s_bpart.off), stages, chunked ? group_ev : nullptr, (double*)(M + s_mec.off), (double*)(M + s_na.off), (uint32_t*)(M + s_it.off),
-             (uint8_t*)(M + s_done.off), (uint32_t*)(M + s_best.off), (uint32_t*)(M + s_tried.off), (uint32_t*)(M + s_q.off),
-             (double*)(M + s_margin.off), (uint32_t*)(M + s_diag.off), (unsigned long long*)(M + s_steps.off), T, p1_shortcut,
-             (uint32_t*)(M + s_stop.off), (uint32_t*)(M + s_ready.off));
+    rc = run(ctx, prm, shape, group_off, stages, chunked ? group_ev : nullptr, bufs, T, p1_shortcut);
     if (rc) { sync_all(ctx); return rc; }
     TR.mark("every launch queued");
     int t_rids = -1;
     if (n_blocks && tot) {              // everything is queued: the copy (pageable destination, the host may block here) overlaps the kernels
         HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_rids, 0));
         t_rids = T.begin(K_D2H, ctx->copy_stream);
-        hipError_t ce = hipMemcpyAsync(R->read_id, M + s_rids.off, 4ull * tot, hipMemcpyDeviceToHost, ctx->copy_stream);
+        hipError_t ce = hipMemcpyAsync(R->read_id, C.at(s_rids), 4ull * tot, hipMemcpyDeviceToHost, ctx->copy_stream);
         T.end(t_rids);
         if (ce != hipSuccess) { sync_all(ctx); return fail(FLORIA_E_DEVICE, hipGetErrorString(ce)); }
     }
     {
         int t = T.begin(K_SEL);
         if (n_blocks) hipLaunchKernelGGL(fl::gather_kernel, dim3(n_blocks), dim3(64), 0, ctx->stream, n_blocks, bs.blk_read_off,
-                                         (const uint32_t*)(M + s_best.off), (const uint8_t*)(M + s_planes.off), tot, (uint8_t*)(M + s_out.off));
+                                         C.at<const uint32_t>(s_best), C.at<const uint8_t>(s_planes), tot, C.at<uint8_t>(s_out));
         T.end(t);
         HIPCHK(hipGetLastError());
     }
@@ -1912,15 +1960,15 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     unsigned long long steps = 0;
     double margin = inf;
     if (n_blocks) {
-        e = hipMemcpyAsync(R->best_ploidy, M + s_best.off, 4ull * n_blocks, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(R->ploidies_tried, M + s_tried.off, 4ull * n_blocks, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(R->mec, M + s_mec.off, 8ull * n_blocks * P, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && tot) e = hipMemcpyAsync(R->part, M + s_out.off, tot, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(R->best_ploidy, C.at(s_best), 4ull * n_blocks, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(R->ploidies_tried, C.at(s_tried), 4ull * n_blocks, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(R->mec, C.at(s_mec), 8ull * n_blocks * P, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && tot) e = hipMemcpyAsync(R->part, C.at(s_out), tot, hipMemcpyDeviceToHost, ctx->stream);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(diag, M + s_diag.off, 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&steps, M + s_steps.off, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(diag, C.at(s_diag), 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&steps, C.at(s_steps), 8, hipMemcpyDeviceToHost, ctx->stream);
     std::vector<double> job_margin((size_t)n_blocks * P + 1, inf);
-    if (e == hipSuccess && n_blocks) e = hipMemcpyAsync(job_margin.data(), M + s_margin.off, 8ull * n_blocks * P, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && n_blocks) e = hipMemcpyAsync(job_margin.data(), C.at(s_margin), 8ull * n_blocks * P, hipMemcpyDeviceToHost, ctx->stream);
     T.end(td);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess && ctx->copy_stream) e = hipStreamSynchronize(ctx->copy_stream);
@@ -1928,7 +1976,7 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     TR.mark("results on the host");
     if (diag[1]) { return fail(FLORIA_E_DEVICE, "internal: beam slab free-list underflow"); }
 #ifdef FLORIA_PROF
-    { unsigned long long prof[64]; (void)hipMemcpy(prof, M + s_diag.off + 16, sizeof(prof), hipMemcpyDeviceToHost); fprintf(stderr, "[prof]"); for (int i = 0; i < 64; ++i) fprintf(stderr, " %d:%.1fM", i, prof[i] / 1e6); fprintf(stderr, "\n"); }
+    { unsigned long long prof[64]; (void)hipMemcpy(prof, C.at<char>(s_diag) + 16, sizeof(prof), hipMemcpyDeviceToHost); fprintf(stderr, "[prof]"); for (int i = 0; i < 64; ++i) fprintf(stderr, " %d:%.1fM", i, prof[i] / 1e6); fprintf(stderr, "\n"); }
 #endif
     memcpy(R->read_off, roff.data(), 8ull * (n_blocks + 1));
     // the pruning decisions of the (block, ploidy) jobs the reference runs, i.e. ploidy <= ploidies_tried (a speculative stage may have run more)
@@ -1949,7 +1997,7 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
         ctx->timing.beam_launch_bytes += blk_bytes[b] * launches_b; ctx->timing.jobs += tb;
     }
     ctx->batch_token = R->batch_token = ++ctx->token_counter;
-    ctx->last_bs = bs; ctx->last_part = (const uint8_t*)(M + s_out.off); ctx->last_best = (const uint32_t*)(M + s_best.off); ctx->last_nall = nall;
+    ctx->last_bs = bs; ctx->last_part = C.at<const uint8_t>(s_out); ctx->last_best = C.at<const uint32_t>(s_best); ctx->last_nall = nall;
     ctx->last_bc = bc; ctx->last_start.assign(blk_start, blk_start + n_blocks); ctx->last_end.assign(blk_end, blk_end + n_blocks);
     guard.r = nullptr;
     *out = R;
@@ -2196,11 +2244,9 @@ int floria_hip_hap_graph(floria_hip_ctx* ctx, const floria_block_result* res, fl
     if (!G->node_off || !G->edge_off || !G->pred || !G->node_cov || !G->edge_w) { floria_hip_hap_graph_free(G); return fail(FLORIA_E_NOMEM, "calloc"); }
     if (nb == 0) { *out = G; return 0; }
     const uint32_t A = ctx->last_nall;
-    struct Seg { size_t off, bytes; };
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { Seg sg{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return sg; };
-    const Seg s_pred = seg(4ull * nb), s_noff = seg(8ull * (nb + 1)), s_eoff = seg(8ull * (nb + 1)), s_cov = seg(8ull * n_nodes + 8), s_ew = seg(4ull * n_edges + 4);
-    int rc = ctx->graph_buf.ensure(cursor + 256);
+    Carve C;
+    const Seg s_pred = C.seg(4ull * nb), s_noff = C.seg(8ull * (nb + 1)), s_eoff = C.seg(8ull * (nb + 1)), s_cov = C.seg(8ull * n_nodes + 8), s_ew = C.seg(4ull * n_edges + 4);
+    int rc = C.place(ctx->graph_buf);
     const size_t hist_bytes = (size_t)range_max * pmax * A * 8;
     const bool in_lds = hist_bytes <= 40 * 1024;
     uint64_t sort_cap = 1;
@@ -2208,14 +2254,13 @@ int floria_hip_hap_graph(floria_hip_ctx* ctx, const floria_block_result* res, fl
     if (!rc && !in_lds) rc = ctx->graph_hist.ensure((uint64_t)nb * hist_bytes);
     if (!rc && (uint64_t)range_max * A > (uint64_t)fl::GRAPH_SORT_CAP) rc = ctx->graph_sort.ensure((uint64_t)nb * sort_cap * 8);
     if (rc) { floria_hip_hap_graph_free(G); return rc; }
-    char* B = ctx->graph_buf.as<char>();
-    hipError_t e = hipMemcpyAsync(B + s_pred.off, G->pred, 4ull * nb, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(B + s_noff.off, G->node_off, 8ull * (nb + 1), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(B + s_eoff.off, G->edge_off, 8ull * (nb + 1), hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = C.up(s_pred, G->pred, 4ull * nb, ctx->stream);
+    if (e == hipSuccess) e = C.up(s_noff, G->node_off, 8ull * (nb + 1), ctx->stream);
+    if (e == hipSuccess) e = C.up(s_eoff, G->edge_off, 8ull * (nb + 1), ctx->stream);
     fl::GraphArgs a{};
     a.bs = ctx->last_bs; a.best_ploidy = ctx->last_best; a.part = ctx->last_part;
-    a.pred = (const int32_t*)(B + s_pred.off); a.node_off = (const uint64_t*)(B + s_noff.off); a.edge_off = (const uint64_t*)(B + s_eoff.off);
-    a.node_cov = (double*)(B + s_cov.off); a.edge_w = (uint32_t*)(B + s_ew.off);
+    a.pred = C.at<const int32_t>(s_pred); a.node_off = C.at<const uint64_t>(s_noff); a.edge_off = C.at<const uint64_t>(s_eoff);
+    a.node_cov = C.at<double>(s_cov); a.edge_w = C.at<uint32_t>(s_ew);
     a.hist_pool = ctx->graph_hist.as<uint64_t>(); a.sort_pool = ctx->graph_sort.as<uint64_t>(); a.sort_cap = sort_cap;
     a.range_max = range_max; a.hist_in_lds = in_lds ? 1 : 0; a.hist_stride = hist_bytes / 8;
     EventTimer T(ctx->stream);
@@ -2226,8 +2271,8 @@ int floria_hip_hap_graph(floria_hip_ctx* ctx, const floria_block_result* res, fl
         e = hipGetLastError();
     }
     T.end(tk);
-    if (e == hipSuccess && n_nodes) e = hipMemcpyAsync(G->node_cov, B + s_cov.off, 8ull * n_nodes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && n_edges) e = hipMemcpyAsync(G->edge_w, B + s_ew.off, 4ull * n_edges, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && n_nodes) e = hipMemcpyAsync(G->node_cov, C.at(s_cov), 8ull * n_nodes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && n_edges) e = hipMemcpyAsync(G->edge_w, C.at(s_ew), 4ull * n_edges, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { floria_hip_hap_graph_free(G); return fail(FLORIA_E_DEVICE, std::string("hap_graph: ") + hipGetErrorString(e)); }
     ctx->timing.select_ms = T.sum(K_SEL);
@@ -2263,26 +2308,22 @@ int floria_hip_haploset_stats(floria_hip_ctx* ctx, const floria_hip_contig* cons
         hoff[g + 1] = hoff[g] + (hi >= lo ? (uint64_t)(hi - lo + 1) * A : 0);
     }
     const uint64_t n_reads_tot = grp_off[n_groups];
-    struct Seg { size_t off, bytes; };
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { Seg sg{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return sg; };
-    const Seg s_cd = seg(sizeof(fl::ContigDev) * n_contigs), s_gc = seg(4ull * n_groups), s_go = seg(8ull * (n_groups + 1)), s_gr = seg(4ull * n_reads_tot + 4),
-              s_rg = seg(8ull * n_groups), s_ho = seg(8ull * (n_groups + 1)), s_h = seg(4ull * hoff[n_groups] + 4), s_out = seg(32ull * n_groups);
-    int rc = ctx->misc.ensure(cursor + 256); if (rc) return rc;
-    char* M = ctx->misc.as<char>();
-    auto h2d = [&](Seg sg, const void* src, size_t bytes) -> hipError_t { return bytes ? hipMemcpyAsync(M + sg.off, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
-    HIPCHK(h2d(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs)); HIPCHK(h2d(s_gc, gc.data(), 4ull * n_groups));
-    HIPCHK(h2d(s_go, grp_off, 8ull * (n_groups + 1))); HIPCHK(h2d(s_gr, grp_read, 4ull * n_reads_tot));
-    HIPCHK(h2d(s_rg, grp_range, 8ull * n_groups)); HIPCHK(h2d(s_ho, hoff.data(), 8ull * (n_groups + 1)));
-    HIPCHK(hipMemsetAsync(M + s_h.off, 0, s_h.bytes, ctx->stream));
+    Carve C;
+    const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4ull * n_reads_tot + 4),
+              s_rg = C.seg(8ull * n_groups), s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * hoff[n_groups] + 4), s_out = C.seg(32ull * n_groups);
+    int rc = C.place(ctx->misc); if (rc) return rc;
+    HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, gc.data(), 4ull * n_groups, ctx->stream));
+    HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4ull * n_reads_tot, ctx->stream));
+    HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, ctx->stream)); HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
+    HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
     fl::StatsArgs a{};
-    a.contigs = (const fl::ContigDev*)(M + s_cd.off); a.grp_contig = (const uint32_t*)(M + s_gc.off); a.grp_off = (const uint64_t*)(M + s_go.off);
-    a.grp_read = (const uint32_t*)(M + s_gr.off); a.grp_range = (const uint32_t*)(M + s_rg.off); a.hist_off = (const uint64_t*)(M + s_ho.off);
-    a.hist = (uint32_t*)(M + s_h.off); a.out = (double*)(M + s_out.off); a.n_groups = n_groups;
+    a.contigs = C.at<const fl::ContigDev>(s_cd); a.grp_contig = C.at<const uint32_t>(s_gc); a.grp_off = C.at<const uint64_t>(s_go);
+    a.grp_read = C.at<const uint32_t>(s_gr); a.grp_range = C.at<const uint32_t>(s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
+    a.hist = C.at<uint32_t>(s_h); a.out = C.at<double>(s_out); a.n_groups = n_groups;
     if (A == 2) hipLaunchKernelGGL(fl::stats_kernel<2>, dim3(n_groups), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(fl::stats_kernel<4>, dim3(n_groups), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out4, M + s_out.off, 32ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out4, C.at(s_out), 32ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -2313,24 +2354,21 @@ int floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const u
     for (uint64_t i = 0; i < n; ++i) if (n_alleles[i] == 0 || n_alleles[i] > FLORIA_MAX_ALLELES) return fail(FLORIA_E_INVALID, "n_alleles must be 1..FLORIA_MAX_ALLELES");
     HIPCHK(hipSetDevice(ctx->device));
     ctx->batch_token = 0;
-    struct Seg { size_t off, bytes; };
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { Seg sg{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return sg; };
-    const Seg s_q = seg(32 * n), s_r = seg(32 * n), s_a = seg((size_t)FLORIA_MAX_ALLELES * n), s_n = seg(n), s_b = seg(n), s_s = seg(4 * n);
-    int rc = ctx->misc.ensure(cursor + 256); if (rc) return rc;
-    char* M = ctx->misc.as<char>();
-    HIPCHK(hipMemcpyAsync(M + s_q.off, read_windows, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(M + s_r.off, ref_windows, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(M + s_a.off, alleles, (size_t)FLORIA_MAX_ALLELES * n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(M + s_n.off, n_alleles, n, hipMemcpyHostToDevice, ctx->stream));
+    Carve C;
+    const Seg s_q = C.seg(32 * n), s_r = C.seg(32 * n), s_a = C.seg((size_t)FLORIA_MAX_ALLELES * n), s_n = C.seg(n), s_b = C.seg(n), s_s = C.seg(4 * n);
+    int rc = C.place(ctx->misc); if (rc) return rc;
+    HIPCHK(C.up(s_q, read_windows, 32 * n, ctx->stream));
+    HIPCHK(C.up(s_r, ref_windows, 32 * n, ctx->stream));
+    HIPCHK(C.up(s_a, alleles, (size_t)FLORIA_MAX_ALLELES * n, ctx->stream));
+    HIPCHK(C.up(s_n, n_alleles, n, ctx->stream));
     fl::RealignArgs a{};
-    a.q = (const uint8_t*)(M + s_q.off); a.r = (const uint8_t*)(M + s_r.off); a.alleles = (const uint8_t*)(M + s_a.off); a.n_alleles = (const uint8_t*)(M + s_n.off);
-    a.best = (uint8_t*)(M + s_b.off); a.score = score ? (int32_t*)(M + s_s.off) : nullptr; a.n = n;
+    a.q = C.at<const uint8_t>(s_q); a.r = C.at<const uint8_t>(s_r); a.alleles = C.at<const uint8_t>(s_a); a.n_alleles = C.at<const uint8_t>(s_n);
+    a.best = C.at<uint8_t>(s_b); a.score = score ? C.at<int32_t>(s_s) : nullptr; a.n = n;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 3) / 4, (uint64_t)ctx->n_cu * 32);      // 4 windows per workgroup, grid-stride beyond 8 workgroups per CU
     hipLaunchKernelGGL(fl::realign_kernel, dim3(grid), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(best, M + s_b.off, n, hipMemcpyDeviceToHost, ctx->stream));
-    if (score) HIPCHK(hipMemcpyAsync(score, M + s_s.off, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(best, C.at(s_b), n, hipMemcpyDeviceToHost, ctx->stream));
+    if (score) HIPCHK(hipMemcpyAsync(score, C.at(s_s), 4 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -2417,34 +2455,30 @@ int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* c
         std::vector<fl::ContigDev> cdev(n_contigs);
         for (uint32_t c = 0; c < n_contigs; ++c) cdev[c] = contigs[c]->dev;
         const uint64_t n_reads_tot = grp_off[n_groups];
-        struct Seg { size_t off, bytes; };
-        size_t cursor = 0;
-        auto seg = [&](size_t bytes) { Seg sg{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return sg; };
-        const Seg s_cd = seg(sizeof(fl::ContigDev) * n_contigs), s_gc = seg(4ull * n_groups), s_go = seg(8ull * (n_groups + 1)), s_gr = seg(4ull * n_reads_tot + 4),
-                  s_lo = seg(4ull * n_groups), s_len = seg(4ull * n_groups), s_co = seg(8ull * (n_groups + 1)), s_h = seg(8ull * coff[n_groups] * A + 8),
-                  s_c = seg(coff[n_groups] + 8), s_pi = seg(4ull * n_pairs), s_pj = seg(4ull * n_pairs), s_sd = seg(8ull * n_pairs);
-        rc = ctx->misc.ensure(cursor + 256); if (rc) return rc;
-        char* M = ctx->misc.as<char>();
-        auto h2d = [&](Seg sg, const void* src, size_t bytes) -> hipError_t { return bytes ? hipMemcpyAsync(M + sg.off, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
-        HIPCHK(h2d(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs)); HIPCHK(h2d(s_gc, gc.data(), 4ull * n_groups));
-        HIPCHK(h2d(s_go, grp_off, 8ull * (n_groups + 1))); HIPCHK(h2d(s_gr, grp_read, 4ull * n_reads_tot));
-        HIPCHK(h2d(s_lo, lo.data(), 4ull * n_groups)); HIPCHK(h2d(s_len, len.data(), 4ull * n_groups)); HIPCHK(h2d(s_co, coff.data(), 8ull * (n_groups + 1)));
-        HIPCHK(h2d(s_pi, pi.data(), 4ull * n_pairs)); HIPCHK(h2d(s_pj, pj.data(), 4ull * n_pairs));
-        HIPCHK(hipMemsetAsync(M + s_h.off, 0, s_h.bytes, ctx->stream));
+        Carve C;
+        const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4ull * n_reads_tot + 4),
+                  s_lo = C.seg(4ull * n_groups), s_len = C.seg(4ull * n_groups), s_co = C.seg(8ull * (n_groups + 1)), s_h = C.seg(8ull * coff[n_groups] * A + 8),
+                  s_c = C.seg(coff[n_groups] + 8), s_pi = C.seg(4ull * n_pairs), s_pj = C.seg(4ull * n_pairs), s_sd = C.seg(8ull * n_pairs);
+        rc = C.place(ctx->misc); if (rc) return rc;
+        HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, gc.data(), 4ull * n_groups, ctx->stream));
+        HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4ull * n_reads_tot, ctx->stream));
+        HIPCHK(C.up(s_lo, lo.data(), 4ull * n_groups, ctx->stream)); HIPCHK(C.up(s_len, len.data(), 4ull * n_groups, ctx->stream)); HIPCHK(C.up(s_co, coff.data(), 8ull * (n_groups + 1), ctx->stream));
+        HIPCHK(C.up(s_pi, pi.data(), 4ull * n_pairs, ctx->stream)); HIPCHK(C.up(s_pj, pj.data(), 4ull * n_pairs, ctx->stream));
+        HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
         fl::ConsensusArgs ca{};
-        ca.contigs = (const fl::ContigDev*)(M + s_cd.off); ca.grp_contig = (const uint32_t*)(M + s_gc.off);
-        ca.grp_off = (const uint64_t*)(M + s_go.off); ca.grp_read = (const uint32_t*)(M + s_gr.off);
-        ca.span_lo = (const uint32_t*)(M + s_lo.off); ca.span_len = (const uint32_t*)(M + s_len.off); ca.cons_off = (const uint64_t*)(M + s_co.off);
-        ca.hist = (unsigned long long*)(M + s_h.off); ca.cons = (uint8_t*)(M + s_c.off); ca.n_groups = n_groups;
+        ca.contigs = C.at<const fl::ContigDev>(s_cd); ca.grp_contig = C.at<const uint32_t>(s_gc);
+        ca.grp_off = C.at<const uint64_t>(s_go); ca.grp_read = C.at<const uint32_t>(s_gr);
+        ca.span_lo = C.at<const uint32_t>(s_lo); ca.span_len = C.at<const uint32_t>(s_len); ca.cons_off = C.at<const uint64_t>(s_co);
+        ca.hist = C.at<unsigned long long>(s_h); ca.cons = C.at<uint8_t>(s_c); ca.n_groups = n_groups;
         if (A == 2) hipLaunchKernelGGL(fl::consensus_kernel<2>, dim3(n_groups), dim3(256), 0, ctx->stream, ca);
         else hipLaunchKernelGGL(fl::consensus_kernel<4>, dim3(n_groups), dim3(256), 0, ctx->stream, ca);
         HIPCHK(hipGetLastError());
         fl::PairArgs pa{};
-        pa.pair_i = (const uint32_t*)(M + s_pi.off); pa.pair_j = (const uint32_t*)(M + s_pj.off); pa.span_lo = ca.span_lo; pa.span_len = ca.span_len;
-        pa.cons_off = ca.cons_off; pa.cons = ca.cons; pa.same_diff = (uint32_t*)(M + s_sd.off); pa.n_pairs = n_pairs;
+        pa.pair_i = C.at<const uint32_t>(s_pi); pa.pair_j = C.at<const uint32_t>(s_pj); pa.span_lo = ca.span_lo; pa.span_len = ca.span_len;
+        pa.cons_off = ca.cons_off; pa.cons = ca.cons; pa.same_diff = C.at<uint32_t>(s_sd); pa.n_pairs = n_pairs;
         hipLaunchKernelGGL(fl::pair_kernel, dim3(n_pairs), dim3(64), 0, ctx->stream, pa);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sd.data(), M + s_sd.off, 8ull * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(sd.data(), C.at(s_sd), 8ull * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     // (3) the scalar tail (:543-615), same operation order as the reference
@@ -2571,40 +2605,36 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
     }
     std::vector<int32_t> assign(n_assign, -1);
     if (n_assign && n_groups) {
-        struct Seg { size_t off, bytes; };
-        size_t cursor = 0;
-        auto seg = [&](size_t bytes) { Seg s{cursor, bytes}; cursor += (bytes + 255) & ~(size_t)255; return s; };
-        const Seg s_cd = seg(sizeof(fl::ContigDev) * n_contigs), s_rob = seg(8ull * n_contigs), s_rb = seg(8ull * n_contigs), s_gb = seg(8ull * n_contigs),
-                  s_ab = seg(8ull * n_contigs), s_ro = seg(8ull * r2g_off_all.size() + 8), s_r2g = seg(4ull * r2g_all.size() + 4),
-                  s_ho = seg(8ull * hist_off_all.size() + 8), s_p0 = seg(4ull * gpos0_all.size() + 4), s_hist = seg(8ull * hist_cells + 8),
-                  s_as = seg(4ull * n_assign + 4), s_q = seg(16), s_ord = seg(read_order ? 4ull * order_off[n_contigs] + 4 : 4),
-                  s_oo = seg(8ull * (n_contigs + 1)), s_mu = seg(4ull * multi_all.size() + 4), s_mo = seg(8ull * (n_contigs + 1)), s_ls = seg(4ull * n_contigs + 4);
+        Carve C;
+        const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_rob = C.seg(8ull * n_contigs), s_rb = C.seg(8ull * n_contigs), s_gb = C.seg(8ull * n_contigs),
+                  s_ab = C.seg(8ull * n_contigs), s_ro = C.seg(8ull * r2g_off_all.size() + 8), s_r2g = C.seg(4ull * r2g_all.size() + 4),
+                  s_ho = C.seg(8ull * hist_off_all.size() + 8), s_p0 = C.seg(4ull * gpos0_all.size() + 4), s_hist = C.seg(8ull * hist_cells + 8),
+                  s_as = C.seg(4ull * n_assign + 4), s_q = C.seg(16), s_ord = C.seg(read_order ? 4ull * order_off[n_contigs] + 4 : 4),
+                  s_oo = C.seg(8ull * (n_contigs + 1)), s_mu = C.seg(4ull * multi_all.size() + 4), s_mo = C.seg(8ull * (n_contigs + 1)), s_ls = C.seg(4ull * n_contigs + 4);
         multi_off_all.push_back(multi_all.size());
-        int rc = ctx->misc.ensure(cursor + 256); if (rc) return rc;
-        char* M = ctx->misc.as<char>();
+        int rc = C.place(ctx->misc); if (rc) return rc;
         EventTimer T(ctx->stream);
         int th = T.begin(K_H2D);
-        auto h2d = [&](Seg sg, const void* src, size_t bytes) -> hipError_t { return bytes ? hipMemcpyAsync(M + sg.off, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess; };
-        HIPCHK(h2d(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs));
-        HIPCHK(h2d(s_rob, r2g_off_base.data(), 8ull * n_contigs)); HIPCHK(h2d(s_rb, r2g_base.data(), 8ull * n_contigs));
-        HIPCHK(h2d(s_gb, grp_base.data(), 8ull * n_contigs)); HIPCHK(h2d(s_ab, assign_base.data(), 8ull * n_contigs));
-        HIPCHK(h2d(s_ro, r2g_off_all.data(), 8ull * r2g_off_all.size())); HIPCHK(h2d(s_r2g, r2g_all.data(), 4ull * r2g_all.size()));
-        HIPCHK(h2d(s_ho, hist_off_all.data(), 8ull * hist_off_all.size())); HIPCHK(h2d(s_p0, gpos0_all.data(), 4ull * gpos0_all.size()));
-        HIPCHK(hipMemsetAsync(M + s_hist.off, 0, s_hist.bytes, ctx->stream));
-        HIPCHK(hipMemsetAsync(M + s_q.off, 0, 16, ctx->stream));
-        HIPCHK(hipMemsetAsync(M + s_as.off, 0xff, s_as.bytes, ctx->stream));            // -1 = not assigned
-        if (read_order) { HIPCHK(h2d(s_ord, read_order, 4ull * order_off[n_contigs])); HIPCHK(h2d(s_oo, order_off, 8ull * (n_contigs + 1))); }
-        HIPCHK(h2d(s_mu, multi_all.data(), 4ull * multi_all.size())); HIPCHK(h2d(s_mo, multi_off_all.data(), 8ull * (n_contigs + 1)));
+        HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream));
+        HIPCHK(C.up(s_rob, r2g_off_base.data(), 8ull * n_contigs, ctx->stream)); HIPCHK(C.up(s_rb, r2g_base.data(), 8ull * n_contigs, ctx->stream));
+        HIPCHK(C.up(s_gb, grp_base.data(), 8ull * n_contigs, ctx->stream)); HIPCHK(C.up(s_ab, assign_base.data(), 8ull * n_contigs, ctx->stream));
+        HIPCHK(C.up(s_ro, r2g_off_all.data(), 8ull * r2g_off_all.size(), ctx->stream)); HIPCHK(C.up(s_r2g, r2g_all.data(), 4ull * r2g_all.size(), ctx->stream));
+        HIPCHK(C.up(s_ho, hist_off_all.data(), 8ull * hist_off_all.size(), ctx->stream)); HIPCHK(C.up(s_p0, gpos0_all.data(), 4ull * gpos0_all.size(), ctx->stream));
+        HIPCHK(hipMemsetAsync(C.at(s_hist), 0, s_hist.bytes, ctx->stream));
+        HIPCHK(hipMemsetAsync(C.at(s_q), 0, 16, ctx->stream));
+        HIPCHK(hipMemsetAsync(C.at(s_as), 0xff, s_as.bytes, ctx->stream));            // -1 = not assigned
+        if (read_order) { HIPCHK(C.up(s_ord, read_order, 4ull * order_off[n_contigs], ctx->stream)); HIPCHK(C.up(s_oo, order_off, 8ull * (n_contigs + 1), ctx->stream)); }
+        HIPCHK(C.up(s_mu, multi_all.data(), 4ull * multi_all.size(), ctx->stream)); HIPCHK(C.up(s_mo, multi_off_all.data(), 8ull * (n_contigs + 1), ctx->stream));
         T.end(th);
         fl::ReassignArgs a{};
-        a.contigs = (const fl::ContigDev*)(M + s_cd.off); a.n_contigs = n_contigs;
-        a.r2g_off_base = (const uint64_t*)(M + s_rob.off); a.r2g_off = (const uint64_t*)(M + s_ro.off);
-        a.r2g_base = (const uint64_t*)(M + s_rb.off); a.r2g = (const uint32_t*)(M + s_r2g.off);
-        a.grp_base = (const uint64_t*)(M + s_gb.off); a.grp_hist_off = (const uint64_t*)(M + s_ho.off); a.grp_pos0 = (const uint32_t*)(M + s_p0.off);
-        a.hist = (uint64_t*)(M + s_hist.off); a.assign = (int32_t*)(M + s_as.off); a.assign_base = (const uint64_t*)(M + s_ab.off);
-        a.eps = epsilon; a.queue_head = (uint32_t*)(M + s_q.off);
-        a.order = read_order ? (const uint32_t*)(M + s_ord.off) : nullptr; a.order_off = (const uint64_t*)(M + s_oo.off);
-        a.multi = (const uint32_t*)(M + s_mu.off); a.multi_off = (const uint64_t*)(M + s_mo.off);
+        a.contigs = C.at<const fl::ContigDev>(s_cd); a.n_contigs = n_contigs;
+        a.r2g_off_base = C.at<const uint64_t>(s_rob); a.r2g_off = C.at<const uint64_t>(s_ro);
+        a.r2g_base = C.at<const uint64_t>(s_rb); a.r2g = C.at<const uint32_t>(s_r2g);
+        a.grp_base = C.at<const uint64_t>(s_gb); a.grp_hist_off = C.at<const uint64_t>(s_ho); a.grp_pos0 = C.at<const uint32_t>(s_p0);
+        a.hist = C.at<uint64_t>(s_hist); a.assign = C.at<int32_t>(s_as); a.assign_base = C.at<const uint64_t>(s_ab);
+        a.eps = epsilon; a.queue_head = C.at<uint32_t>(s_q);
+        a.order = read_order ? C.at<const uint32_t>(s_ord) : nullptr; a.order_off = C.at<const uint64_t>(s_oo);
+        a.multi = C.at<const uint32_t>(s_mu); a.multi_off = C.at<const uint64_t>(s_mo);
         const bool arith = ctx->knobs.arith != 0;
         if (arith) {                                // the reference's running sums: every read's cells in the order of its position set
             std::vector<uint64_t> ncells(n_contigs); uint32_t len_max = 1;
@@ -2622,10 +2652,10 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
         }
         std::vector<uint32_t> lists(list_par);
         lists.insert(lists.end(), list_chain.begin(), list_chain.end());
-        HIPCHK(hipMemcpyAsync(M + s_ls.off, lists.data(), 4ull * lists.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(C.up(s_ls, lists.data(), 4ull * lists.size(), ctx->stream));
         int tk = T.begin(K_REASSIGN);
         if (!list_par.empty()) {
-            a.list = (const uint32_t*)(M + s_ls.off); a.n_list = (uint32_t)list_par.size(); a.queue_head = (uint32_t*)(M + s_q.off);
+            a.list = C.at<const uint32_t>(s_ls); a.n_list = (uint32_t)list_par.size(); a.queue_head = C.at<uint32_t>(s_q);
             const uint32_t grid = std::min<uint32_t>(a.n_list, (uint32_t)ctx->n_cu * 8);
             if (arith) { if (A == 2) hipLaunchKernelGGL((fl::reassign_kernel<2, true>), dim3(grid), dim3(fl::REASSIGN_THREADS), 0, ctx->stream, a);
                          else hipLaunchKernelGGL((fl::reassign_kernel<4, true>), dim3(grid), dim3(fl::REASSIGN_THREADS), 0, ctx->stream, a); }
@@ -2633,7 +2663,7 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
             else hipLaunchKernelGGL(fl::reassign_kernel<4>, dim3(grid), dim3(fl::REASSIGN_THREADS), 0, ctx->stream, a);
         }
         if (!list_chain.empty()) {
-            a.list = (const uint32_t*)(M + s_ls.off) + list_par.size(); a.n_list = (uint32_t)list_chain.size(); a.queue_head = (uint32_t*)(M + s_q.off) + 1;
+            a.list = C.at<const uint32_t>(s_ls) + list_par.size(); a.n_list = (uint32_t)list_chain.size(); a.queue_head = C.at<uint32_t>(s_q) + 1;
             const uint32_t grid = std::min<uint32_t>(a.n_list, (uint32_t)ctx->n_cu * 16);
             if (A == 2) hipLaunchKernelGGL(fl::reassign_chain_kernel<2>, dim3(grid), dim3(64), 0, ctx->stream, a);
             else hipLaunchKernelGGL(fl::reassign_chain_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
@@ -2642,7 +2672,7 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
         T.end(tk);
         HIPCHK(hipGetLastError());
         int td = T.begin(K_D2H);
-        HIPCHK(hipMemcpyAsync(assign.data(), M + s_as.off, 4ull * n_assign, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(assign.data(), C.at(s_as), 4ull * n_assign, hipMemcpyDeviceToHost, ctx->stream));
         T.end(td);
         HIPCHK(hipStreamSynchronize(ctx->stream));
         ctx->timing.reassign_ms = T.sum(K_REASSIGN); ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.total_ms = T.span();

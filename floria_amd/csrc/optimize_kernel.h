@@ -149,10 +149,8 @@ __device__ inline void bitonic_sort(G gain, K key, uint32_t n, int tid, int nthr
 // of its position set (utils_frags.rs:33-72), a partition's `errors` the running sum over its positions in the bucket order of its position
 // map (local_clustering.rs:226-256), which is emulated per partition (arith_kernel.h).
 // (the ploidy 1-3 instances of 512 threads are held to the 80 VGPRs that let three workgroups share a CU: six waves per SIMD)
-#ifndef FLORIA_ARITH_OPT_WAVES
-#define FLORIA_ARITH_OPT_WAVES 6
-#endif
-constexpr int opt_min_waves(int tp, int threads, bool arith, int ow = 0) { return arith ? (threads == 512 ? (ow ? ow : FLORIA_ARITH_OPT_WAVES) : 1) : ((threads == 512 && tp >= 1 && tp <= 3) ? 6 : 1); }      // (ARITH, 512 threads: 80 VGPRs = three workgroups per CU; the 149 hipcc takes when left alone leave one.  Measured on config 4, arith = 1: 4 / 5 / 6 waves 177 / 175 / 171 ms)
+constexpr int OPT_WAVES_ARITH = 6;
+constexpr int opt_min_waves(int tp, int threads, bool arith, int ow = 0) { return arith ? (threads == 512 ? (ow ? ow : OPT_WAVES_ARITH) : 1) : ((threads == 512 && tp >= 1 && tp <= 3) ? 6 : 1); }      // (ARITH, 512 threads: 80 VGPRs = three workgroups per CU; the 149 hipcc takes when left alone leave one.  Measured on config 4, arith = 1: 4 / 5 / 6 waves 177 / 175 / 171 ms)
 // OW (ARITH): waves per SIMD to compile for, 0 = the default above (where LDS allows two workgroups per CU anyway — ploidy >= 3 on config 4 — four waves' worth of registers)
 template <int A, bool HL, int OPT_THREADS, int TP = 0, bool ARITH = false, int OW = 0>
 __global__ __launch_bounds__(OPT_THREADS) __attribute__((amdgpu_waves_per_eu(opt_min_waves(TP, OPT_THREADS, ARITH, OW))))
@@ -730,11 +728,7 @@ void optimize_kernel(OptArgs g) {
                 // ---- opt_iterate (:292-358): distance of every read to every partition ------------------------
                 // 16 lanes per read: every lane classifies its cells against all p partitions (p x 16 B of one histogram row),
                 // packed partial (diff Q24 << 16 | #eps) per partition, DPP row all-reduce, lane k of the row stores
-#ifdef FLORIA_OPT_FULL_DIST
-                const bool incremental = false;
-#else
                 const bool incremental = HL && meta && it > 0 && span <= 65535u;
-#endif
                 const uint32_t chg_lo = incremental ? s_chg_lo : 0u, chg_hi = incremental ? s_chg_hi : 0xffffffffu;
                 if constexpr (ARITH) { /* the distances of this round were computed beside the last statistics call (dist_arith) */                } else
                 for (uint32_t iv = grp; iv < n16; iv += OPT_THREADS / 16) {
