@@ -65,6 +65,10 @@ class CTiming(C.Structure):
                 ("beam_union_ms", C.c_double), ("optimize_union_ms", C.c_double)]
 
 
+class CRealignWalk(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("step", C.c_uint32), ("rule", C.c_uint32), ("tie", C.c_uint32)]
+
+
 def ptr(a, ctype):
     """Pointer to a C-contiguous numpy array (the array must outlive the call)."""
     return a.ctypes.data_as(C.POINTER(ctype))

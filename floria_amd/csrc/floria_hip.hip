@@ -40,6 +40,7 @@
 #include "graph_kernel.h"
 #include "stats_kernel.h"
 #include "realign_kernel.h"
+#include "realign_walk_kernel.h"
 #include "upload_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
@@ -2347,8 +2348,26 @@ int floria_hip_selftest(floria_hip_ctx* ctx, double epsilon, uint32_t n_max, dou
 }
 
 // ---- alignment::realign (alignment.rs:7-64) for the windows the host could not decide --------------------------------------------------------
-int floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles, const uint8_t* n_alleles,
-                       uint64_t n, uint8_t* best, int32_t* score) {
+namespace {
+// the exact affine-gap DP: one wavefront per window
+hipError_t launch_realign(const floria_hip_ctx* ctx, const fl::RealignArgs& a) {
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((a.n + 3) / 4, (uint64_t)ctx->n_cu * 32);      // 4 windows per workgroup, grid-stride beyond 8 workgroups per CU
+    hipLaunchKernelGGL(fl::realign_kernel, dim3(grid), dim3(256), 0, ctx->stream, a);
+    return hipGetLastError();
+}
+// The one place where a member of the fixed-block walk family becomes a kernel instance: realign_walk_kernel<step = 1 | 2 | 4 | 8, rule = max | sum, tie = right | down>
+// (compile-time members: the strip loop of a shift unrolls to step + 8 steps, the rule's reduction and the tie are folded; 59-78 VGPRs, 6-8 waves per SIMD, no scratch in any of the 16).
+hipError_t launch_realign_walk(const floria_hip_ctx* ctx, const floria_realign_walk& walk, const fl::RealignArgs& a) {
+    const uint32_t per = fl::walk::GROUPS;                                                              // a 16-lane group per window
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((a.n + per - 1) / per, (uint64_t)ctx->n_cu * 32);
+    return pick<1, 2, 4, 8>(walk.step, [&](auto ST) { return with_bool(walk.rule != 0, [&](auto RU) { return with_bool(walk.tie != 0, [&](auto TI) {
+        hipLaunchKernelGGL((fl::realign_walk_kernel<ST, RU ? 1 : 0, TI ? 1 : 0>), dim3(grid), dim3(256), 0, ctx->stream, a);
+        return hipGetLastError();
+    }); }); });
+}
+// upload the windows, score them (walk == null: the exact DP), fetch the calls
+int realign_windows(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles, const uint8_t* n_alleles,
+                    uint64_t n, const floria_realign_walk* walk, uint8_t* best, int32_t* score) {
     if (!ctx || (n && (!read_windows || !ref_windows || !alleles || !n_alleles || !best))) return fail(FLORIA_E_INVALID, "null argument");
     if (n == 0) return 0;
     for (uint64_t i = 0; i < n; ++i) if (n_alleles[i] == 0 || n_alleles[i] > FLORIA_MAX_ALLELES) return fail(FLORIA_E_INVALID, "n_alleles must be 1..FLORIA_MAX_ALLELES");
@@ -2364,13 +2383,25 @@ int floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const u
     fl::RealignArgs a{};
     a.q = C.at<const uint8_t>(s_q); a.r = C.at<const uint8_t>(s_r); a.alleles = C.at<const uint8_t>(s_a); a.n_alleles = C.at<const uint8_t>(s_n);
     a.best = C.at<uint8_t>(s_b); a.score = score ? C.at<int32_t>(s_s) : nullptr; a.n = n;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 3) / 4, (uint64_t)ctx->n_cu * 32);      // 4 windows per workgroup, grid-stride beyond 8 workgroups per CU
-    hipLaunchKernelGGL(fl::realign_kernel, dim3(grid), dim3(256), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
+    HIPCHK(walk ? launch_realign_walk(ctx, *walk, a) : launch_realign(ctx, a));
     HIPCHK(hipMemcpyAsync(best, C.at(s_b), n, hipMemcpyDeviceToHost, ctx->stream));
     if (score) HIPCHK(hipMemcpyAsync(score, C.at(s_s), 4 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
+}
+}  // namespace
+
+int floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles, const uint8_t* n_alleles,
+                       uint64_t n, uint8_t* best, int32_t* score) {
+    return realign_windows(ctx, read_windows, ref_windows, alleles, n_alleles, n, nullptr, best, score);
+}
+
+int floria_hip_realign_walk(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles, const uint8_t* n_alleles,
+                            uint64_t n, const floria_realign_walk* walk, uint8_t* best, int32_t* score) {
+    if (!walk) return fail(FLORIA_E_INVALID, "null argument");
+    if (walk->block != 8 || (walk->step != 1 && walk->step != 2 && walk->step != 4 && walk->step != 8) || walk->rule > 1 || walk->tie > 1)
+        return fail(FLORIA_E_INVALID, "floria_realign_walk: block must be 8, step 1, 2, 4 or 8, rule 0 (max) or 1 (sum), tie 0 (right) or 1 (down)");
+    return realign_windows(ctx, read_windows, ref_windows, alleles, n_alleles, n, walk, best, score);
 }
 
 // ---- get_hapq (part_block_manip.rs:517-616) for the haplosets of many contigs (the reference calls it once per contig) ----------

@@ -243,11 +243,12 @@ std::vector<Frag> remove_monomorphic_allele(std::vector<Frag> frags, double erro
     return out;
 }
 
-void realign_queue_on_device(Session& s, RealignQueue& q) {
+void realign_queue_on_device(Session& s, RealignQueue& q, const floria_realign_walk* walk) {
     const size_t n = q.size();
     if (!n) return;
     std::vector<uint8_t> best(n);
-    check(floria_hip_realign(s.ctx(), q.read_windows.data(), q.ref_windows.data(), q.alleles.data(), q.n_alleles.data(), (uint64_t)n, best.data(), nullptr));
+    if (walk) check(floria_hip_realign_walk(s.ctx(), q.read_windows.data(), q.ref_windows.data(), q.alleles.data(), q.n_alleles.data(), (uint64_t)n, walk, best.data(), nullptr));
+    else check(floria_hip_realign(s.ctx(), q.read_windows.data(), q.ref_windows.data(), q.alleles.data(), q.n_alleles.data(), (uint64_t)n, best.data(), nullptr));
     for (size_t i = 0; i < n; ++i) *q.dst[i] = (Genotype)best[i];
     q = RealignQueue();
 }

@@ -63,7 +63,16 @@ struct Options {
     bool trim_reads = false;            // --extra-trimming
     bool ignore_monomorphic = false;    // --ignore-monomorphic (utils_frags.rs:713-772)
     int device = 0;
+    // --realign exact | block:STEP,RULE,TIE: how alignment::realign scores a window.  false: the exact affine-gap DP (default); true: the member `walk` of the
+    // fixed-block walk family (floria_hip_realign_walk on the device, walk_affine_score on the host)
+    bool realign_walk = false;
+    floria_realign_walk walk = {8, 8, 0, 0};
 };
+// "exact" | "block:STEP,RULE,TIE" (STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down) -> options.realign_walk / options.walk; anything else throws with the grammar
+void parse_realign_spec(const std::string& spec, Options& options);
+std::string realign_spec(const Options& options);                                     // the spelling parse_realign_spec accepts
+// score of one member of the fixed-block walk family (block 8; scripts/probes/block_walk.c: walk_score), the host twin of floria_hip_realign_walk
+int walk_affine_score(const unsigned char* q, int nq, const unsigned char* r, int nr, const floria_realign_walk& walk);
 
 // The per-read maps of the reference's Frag (FxHashMap<SnpPosition, _>, types_structs.rs:72-84) as a sorted vector with std::map's
 // interface: a read has ~100 entries, inserted in ascending order by the CIGAR walk — one allocation instead of one tree node per entry
@@ -279,7 +288,7 @@ std::vector<std::string> get_contigs_to_phase(const BamFile& bam);              
 VcfProfile get_vcf_profile(const std::string& vcf_file, const std::vector<std::string>& ref_chroms);       // :239-314 (+ :113-175); text VCF, optionally gzipped
 std::map<std::string, std::string> get_fasta_seqs(const std::string& fasta_file);      // :462-489 (whole sequences)
 // :343-460 + combine_frags :491-659 + frag_from_record :661-736; with `ref_seq` (the contig's reference sequence) every call is
-// realigned (alignment.rs:7-64, exact affine-gap DP in place of block-aligner)
+// realigned (alignment.rs:7-64, exact affine-gap DP in place of block-aligner; options.realign_walk: a selected fixed-block walk)
 std::pair<std::vector<Frag>, std::vector<Frag>> get_frags_from_bamvcf_rewrite(const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string& contig,
                                                                                const std::string* ref_seq = nullptr);
 // The same in two halves with the realignment's DP on the device between them.  alignment::realign decides most calls from the mismatch
@@ -368,8 +377,8 @@ std::vector<Frag> remove_monomorphic_allele(std::vector<Frag> frags, double erro
 void write_reads(const std::vector<std::vector<const Frag*>>& part, const std::vector<std::pair<SnpPosition, SnpPosition>>& snp_range_parts_vec, const std::string& out_bam_part_dir,
                  bool extend_read_clipping, const std::vector<uint8_t>& hapqs, bool gzip);
 void write_nosnp_reads(const std::string& out_bam_part_dir, const std::vector<const Frag*>& snpless_frags, bool gzip);
-// scores the queued realignment windows on the device (floria_hip_realign) and stores the winning alleles where they belong
-void realign_queue_on_device(Session& s, RealignQueue& queue);
+// scores the queued realignment windows on the device (floria_hip_realign; with a walk floria_hip_realign_walk) and stores the winning alleles where they belong
+void realign_queue_on_device(Session& s, RealignQueue& queue, const floria_realign_walk* walk = nullptr);
 // write_outputs for a contig whose statistics were computed by Batch::stats_and_hapq
 void write_outputs(const ContigWork& w, const Options& options);
 // the same in two halves, for hosts that write the contigs of a batch from several threads: the files of the contig (returns its

@@ -275,11 +275,78 @@ int nw_affine_score(const unsigned char* q, int nq, const unsigned char* r, int 
     return std::max(Mv[nr], std::max(Iv[nr], Dv[nr]));
 }
 
+}  // namespace
+
+// One member of the fixed-block walk family, as scripts/probes/block_walk.c defines it (walk_score): the same cells as nw_affine_score (D best, C gap in the
+// column, H gap in the row), but only those a block of B x B cells (plus its border row / column) visits on its way from the top-left corner to cell (nq, nr),
+// shifted right or down by `step` cells at a time; a cell whose neighbour was never computed sees -infinity from it.  Never above the exact score.
+int walk_affine_score(const unsigned char* q, int nq, const unsigned char* r, int nr, const floria_realign_walk& walk) {
+    constexpr int MATCH = 1, MISMATCH = -1, OPEN = -2, EXTEND = -1, NEG = -1000000;
+    const int B = (int)walk.block, step = (int)walk.step, W = nr + 1;
+    static thread_local std::vector<int> D, C, H;
+    static thread_local std::vector<unsigned char> done;
+    const size_t cells = (size_t)(nq + 1) * W;
+    D.assign(cells, NEG); C.assign(cells, NEG); H.assign(cells, NEG); done.assign(cells, 0);
+    const auto up = [](unsigned char c) { return (unsigned char)(c >= 'a' && c <= 'z' ? c - 32 : c); };
+    const auto cell = [&](int i, int j) {
+        const size_t x = (size_t)i * W + j;
+        if (done[x]) return;
+        int d = NEG, c = NEG, h = NEG;
+        if (i == 0 && j == 0) d = 0;
+        else {
+            if (i > 0 && done[x - W]) c = std::max(D[x - W] + OPEN, C[x - W] + EXTEND);
+            if (j > 0 && done[x - 1]) h = std::max(D[x - 1] + OPEN, H[x - 1] + EXTEND);
+            if (i > 0 && j > 0 && done[x - W - 1]) d = D[x - W - 1] + (up(q[i - 1]) == up(r[j - 1]) ? MATCH : MISMATCH);
+            d = std::max(d, std::max(c, h));
+        }
+        D[x] = d < NEG / 2 ? NEG : d; C[x] = c < NEG / 2 ? NEG : c; H[x] = h < NEG / 2 ? NEG : h; done[x] = 1;
+    };
+    const auto block = [&](int i0, int j0) { for (int i = i0; i <= std::min(i0 + B, nq); ++i) for (int j = j0; j <= std::min(j0 + B, nr); ++j) cell(i, j); };
+    int i0 = 0, j0 = 0;
+    block(0, 0);
+    for (;;) {
+        const int ie = std::min(i0 + B, nq), je = std::min(j0 + B, nr);
+        if (ie == nq && je == nr) break;
+        bool down;
+        if (je == nr) down = true;
+        else if (ie == nq) down = false;
+        else {
+            long a = walk.rule ? 0 : NEG, b = a;                      // right border column, bottom border row
+            for (int i = i0; i <= ie; ++i) { const size_t x = (size_t)i * W + je; const int v = done[x] ? D[x] : NEG; a = walk.rule ? a + v : std::max<long>(a, v); }
+            for (int j = j0; j <= je; ++j) { const size_t x = (size_t)ie * W + j; const int v = done[x] ? D[x] : NEG; b = walk.rule ? b + v : std::max<long>(b, v); }
+            down = b > a ? true : (a > b ? false : walk.tie != 0);
+        }
+        if (down) { i0 += step; if (i0 + B > nq) i0 = std::max(nq - B, 0); }
+        else      { j0 += step; if (j0 + B > nr) j0 = std::max(nr - B, 0); }
+        block(i0, j0);
+    }
+    return D[(size_t)nq * W + nr];
+}
+
+void parse_realign_spec(const std::string& spec, Options& o) {
+    const std::string grammar = "--realign takes exact | block:STEP,RULE,TIE with STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down (e.g. block:8,max,right), not '" + spec + "'";
+    if (spec == "exact") { o.realign_walk = false; return; }
+    if (spec.compare(0, 6, "block:") != 0) throw Error(FLORIA_E_INVALID, grammar);
+    std::vector<std::string> f(1);
+    for (size_t i = 6; i < spec.size(); ++i) { if (spec[i] == ',') f.emplace_back(); else f.back().push_back(spec[i]); }
+    if (f.size() != 3 || (f[0] != "1" && f[0] != "2" && f[0] != "4" && f[0] != "8") || (f[1] != "max" && f[1] != "sum") || (f[2] != "right" && f[2] != "down"))
+        throw Error(FLORIA_E_INVALID, grammar);
+    o.realign_walk = true;
+    o.walk = {8, (uint32_t)(f[0][0] - '0'), f[1] == "sum" ? 1u : 0u, f[2] == "down" ? 1u : 0u};
+}
+
+std::string realign_spec(const Options& o) {
+    if (!o.realign_walk) return "exact";
+    return "block:" + std::to_string(o.walk.step) + (o.walk.rule ? ",sum" : ",max") + (o.walk.tie ? ",down" : ",right");
+}
+
+namespace {
 // alignment::realign (alignment.rs:7-64)
+// `walk`: score with that member of the fixed-block walk family instead of the exact DP (null: exact)
 // `queue`: calls the exact shortcut cannot decide are not scored here but appended to the queue (windows + where the result goes) for
 // floria_hip_realign, the same DP on the device; null = score them on the host (--ingest-only, tests)
 void realign(const std::string& ref_gn, Frag& frag, const BamSeqView& read_seq, const std::map<SnpPosition, GnPosition>& var_to_gn_pos,
-             const std::map<GnPosition, std::vector<Genotype>>& gn_pos_to_allele, RealignQueue* queue) {
+             const std::map<GnPosition, std::vector<Genotype>>& gn_pos_to_allele, RealignQueue* queue, const floria_realign_walk* walk) {
     constexpr size_t flank = 16;
     for (auto& kv : frag.seq_dict) {
         const size_t snp_gn_pos = var_to_gn_pos.at(kv.first);
@@ -297,6 +364,9 @@ void realign(const std::string& ref_gn, Frag& frag, const BamSeqView& read_seq, 
         // ungapped alignment scores 32 - 2h for an allele equal to the read's base and 30 - 2h for any other.  So for h <= 2 the
         // first allele equal to the read's base wins strictly (28 > 27); with no such allele and h <= 1 every allele scores
         // 30 - 2h >= 28 and the first one is kept (`score > best_score`).  Everything else takes the DP.
+        // Under a fixed-block walk the shortcut stays: a walk's score is never above the exact one (it maximises over fewer paths), and on a window with
+        // h <= 2 every member's block keeps the main diagonal, so the ungapped alignment's score is found
+        // (tests/test_realign_walk_cpu.py::test_shortcut_is_exact_under_every_walk: all 16 members, both sides of the bound).
         {
             const auto up = [](unsigned char c) { return (unsigned char)(c >= 'a' && c <= 'z' ? c - 32 : c); };
             int h = 0;
@@ -322,7 +392,7 @@ void realign(const std::string& ref_gn, Frag& frag, const BamSeqView& read_seq, 
         Genotype best_geno = 0;
         for (size_t a = 0; a < alleles.size(); ++a) {
             r[flank] = alleles[a];
-            const int score = nw_affine_score(q, 2 * flank, r, 2 * flank);
+            const int score = walk ? walk_affine_score(q, 2 * flank, r, 2 * flank, *walk) : nw_affine_score(q, 2 * flank, r, 2 * flank);
             if (score > best_score) { best_score = score; best_geno = (Genotype)a; }
         }
         kv.second = best_geno;
@@ -825,7 +895,7 @@ ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Optio
         auto ins = name_ix.emplace(std::string(rec.qname), names.size());
         if (ins.second) { names.emplace_back(rec.qname); buckets.emplace_back(); }
         Frag fr = frag_from_record(rec, snp_positions, pos_allele_map, this_count, o.output_reads);
-        if (ref_seq) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue);             // :416-423
+        if (ref_seq) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue, o.realign_walk ? &o.walk : nullptr);             // :416-423
         buckets[ins.first->second].push_back({rec.flags, std::move(fr)});
     }
 }

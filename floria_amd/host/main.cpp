@@ -15,6 +15,9 @@
 // --batch-contigs N / --batch-cells N (size of a device batch), --debug (debug_graph.txt per contig), --lp-tie first|last (which optimal vertex of the
 // stitching LP is used where the optimum is not unique; the run reports how many contigs that concerns), and for tests --dump-frags FILE,
 // --ingest-only, --no-realign, --stitch-graph FILE.
+// --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
+// RULE max | sum, TIE right | down): one member of the family of fixed-block walks (block 8) that scripts/probes/block_walk.c defines.  The reference's block-aligner is
+// some heuristic of this kind; which member, if any, is not known, so there is no bare `block`.  The run's log and cmd.log name the scoring used.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -58,8 +61,12 @@ void usage() {
           "  --epsilon-round   round an ESTIMATED -e to a multiple of 2^-10 (there both arithmetics are the same function)\n"
           "  --lp-tie first|last, --lp-report   which optimal vertex of the stitching LP is used where the optimum is not unique, and how often that is\n"
           "  --no-realign      skip the re-alignment of the reads' bases around SNPs\n"
+          "  --realign exact | block:STEP,RULE,TIE   how that re-alignment scores a window: exact [default] = the exact affine-gap alignment; block:... = a walk of a fixed\n"
+          "                 8 x 8 block over the alignment matrix, shifted by STEP = 1 | 2 | 4 | 8 cells towards the larger border by RULE = max | sum, ties going\n"
+          "                 TIE = right | down (e.g. block:8,max,right).  floria's block-aligner is a heuristic of this kind; which member is unknown, so one must be named\n"
           "where this build is not floria (DESIGN.md sections 6 and 7):\n"
-          "  * re-alignment around SNPs is the EXACT affine-gap alignment of the 32-base windows; floria's block-aligner is a banded heuristic of it (calls can differ)\n"
+          "  * re-alignment around SNPs is the EXACT affine-gap alignment of the 32-base windows; floria's block-aligner is a banded heuristic of it (calls can differ;\n"
+          "    --realign block:... selects one of 16 fixed-block walks instead, none of which is known to be block-aligner's)\n"
           "  * the stitching LP is solved exactly as a min-cost flow: the same optimal value as floria's simplex, possibly another optimal vertex (short reads: haplosets can differ)\n"
           "  * hash-set iteration orders decide ties in floria (visiting order of the final reassignment, the read dropped at a haplogroup split): here ascending read order\n"
           "  * not supported: -H / --hybrid, --reassign-short, --bin-by-cov (hidden or beta in floria)\n", stderr);
@@ -116,7 +123,7 @@ int main(int argc, char** argv) {
     std::string dump_frags;
     size_t batch_contigs = 4096;         // --batch-contigs
     uint64_t batch_cells = 256ull << 20; // --batch-cells (1.5 GB of pinned staging)
-    bool ingest_only = false, no_realign = false;
+    bool ingest_only = false, no_realign = false, have_realign = false;
     std::string stitch_graph;
     LpTie lp_tie = LpTie::First;         // --lp-tie first|last: which optimal vertex of the stitching LP is used where the optimum is not unique (stitch.cpp)
     std::atomic<size_t> lp_contigs{0}, lp_not_unique{0}, lp_edges{0}, lp_movable{0};
@@ -200,6 +207,7 @@ int main(int argc, char** argv) {
             else if (a == "--batch-cells") batch_cells = std::max<uint64_t>(1, std::stoull(val()));        // SNP calls per device batch
             else if (a == "--dump-frags") dump_frags = val();
             else if (a == "--no-realign") no_realign = true;                   // (tests) keep the alleles as called
+            else if (a == "--realign") { parse_realign_spec(val(), o); have_realign = true; }
             else if (a == "--ingest-only") ingest_only = true;          // (tests) stop after ingest: needs no GPU
             else if (a == "--stitch-graph") stitch_graph = val();       // (tests) N / E lines of a hap graph -> F / P lines on stdout: needs no GPU
             else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -253,6 +261,7 @@ int main(int argc, char** argv) {
             }
             return 0;
         }
+        if (no_realign && have_realign && o.realign_walk) throw Error(FLORIA_E_INVALID, "--no-realign and --realign " + realign_spec(o) + " exclude each other");
         if (o.bam_file.empty()) throw Error(FLORIA_E_INVALID, "Must input a BAM file.");
         if (o.vcf_file.empty() || o.reference_fasta.empty()) throw Error(FLORIA_E_INVALID, "-v and -r are required");
         if (!(o.ploidy_sensitivity >= 1 && o.ploidy_sensitivity <= 3)) throw Error(FLORIA_E_INVALID, "Ploidy sensitivty option must be between 1 and 3");
@@ -301,6 +310,10 @@ int main(int argc, char** argv) {
             else
                 fprintf(stderr, "floria-hip: warning: -e %.17g is not a multiple of 2^-10; with --arith canonical sums of epsilon terms are rounded once here and term by term (in hash-map order) in floria, "
                                 "so haplosets can differ from floria's in exact ties (-e %.10g, or --epsilon-round for an estimated one, avoids that)\n", o.epsilon, near);
+        }
+        if (o.realign_walk) {
+            if (!run_note.empty()) run_note += "\n";
+            run_note += "# floria-hip: realignment scored by the fixed-block walk " + realign_spec(o) + " (block 8; default: the exact affine-gap DP)";
         }
         if (!ingest_only) write_run_files(o, argc, argv, run_note);
         const std::vector<std::string> contigs = stream.target_names();                 // get_contigs_to_phase (file_reader.rs:738-746)
@@ -382,7 +395,7 @@ int main(int argc, char** argv) {
                     RealignQueue all;
                     for (RealignQueue& q : queues) all.append(std::move(q));
                     n_realign_device += all.size();
-                    realign_queue_on_device(*session_holder, all);
+                    realign_queue_on_device(*session_holder, all, o.realign_walk ? &o.walk : nullptr);
                     t_realign += now_s() - tr;
                 }
                 parallel_for(take, n_threads, [&](size_t i) {
@@ -496,7 +509,8 @@ int main(int argc, char** argv) {
         }
         }       // (next segment of the BAM)
         fprintf(stderr, "BAM: %zu records in %zu segments, %.3fs of inflate + decode, largest inflated buffer %zu MiB\n", n_records, n_segments, t_stream, stream.peak_buffer_bytes() >> 20);
-        fprintf(stderr, "Realignment: %zu calls scored on the device in %.3fs (inside the ingest time)\n", n_realign_device, t_realign);
+        fprintf(stderr, "Realignment: %zu calls scored on the device in %.3fs (inside the ingest time), scoring %s\n", n_realign_device, t_realign,
+                o.realign_walk ? ("fixed-block walk " + realign_spec(o)).c_str() : "exact affine-gap DP");
         fprintf(stderr, "Batches %zu; ingest %.3fs, phasing (upload + S1 + graph) %.3fs, LP + paths %.3fs, S2 %.3fs, COV/ERR/HAPQ %.3fs, writers %.3fs\n", n_batches, t_ingest, t_s1,
                 t_stitch, t_s2, t_stats, t_write);
         if (reference_arith && n_batches_orders)

@@ -19,7 +19,7 @@ _LIB = None
 
 # every symbol include/floria_hip.h declares
 SYMBOLS = [
-    "floria_hip_create", "floria_hip_destroy", "floria_hip_last_error", "floria_hip_version", "floria_hip_init_env", "floria_hip_realign", "floria_hip_selftest",
+    "floria_hip_create", "floria_hip_destroy", "floria_hip_last_error", "floria_hip_version", "floria_hip_init_env", "floria_hip_realign", "floria_hip_realign_walk", "floria_hip_selftest",
     "floria_hip_block_ranges", "floria_hip_ranges_free", "floria_hip_contig_upload", "floria_hip_contig_free",
     "floria_hip_phase_blocks_resident", "floria_hip_phase_blocks", "floria_hip_block_result_free",
     "floria_hip_phase_blocks_batch", "floria_hip_reassign", "floria_hip_groups_free", "floria_hip_last_timing",
@@ -422,6 +422,20 @@ class FloriaHip:
         score = np.zeros(n, np.int32) if want_scores else None
         _check(load().floria_hip_realign(self._h, capi.ptr(q, C.c_uint8), capi.ptr(r, C.c_uint8), capi.ptr(al, C.c_uint8), capi.ptr(na, C.c_uint8), C.c_uint64(n),
                                          capi.ptr(best, C.c_uint8), capi.ptr(score, C.c_int32) if want_scores else None))
+        return (best, score) if want_scores else best
+
+    def realign_walk(self, read_windows, ref_windows, alleles, n_alleles, step, rule, tie, want_scores=False, block=8):
+        """realign() scored by one member of the fixed-block walk family instead of the exact DP (floria_hip_realign_walk): block 8, step 1 | 2 | 4 | 8,
+        rule 0 / "max" | 1 / "sum", tie 0 / "right" | 1 / "down"; any other member raises FloriaHipError (FLORIA_E_INVALID)."""
+        q = np.ascontiguousarray(read_windows, np.uint8); r = np.ascontiguousarray(ref_windows, np.uint8)
+        al = np.ascontiguousarray(alleles, np.uint8); na = np.ascontiguousarray(n_alleles, np.uint8)
+        n = len(na)
+        assert q.shape == (n, 32) and r.shape == (n, 32) and al.shape == (n, 4)
+        walk = capi.CRealignWalk(int(block), int(step), {"max": 0, "sum": 1}.get(rule, rule), {"right": 0, "down": 1}.get(tie, tie))
+        best = np.zeros(n, np.uint8)
+        score = np.zeros(n, np.int32) if want_scores else None
+        _check(load().floria_hip_realign_walk(self._h, capi.ptr(q, C.c_uint8), capi.ptr(r, C.c_uint8), capi.ptr(al, C.c_uint8), capi.ptr(na, C.c_uint8), C.c_uint64(n),
+                                              C.byref(walk), capi.ptr(best, C.c_uint8), capi.ptr(score, C.c_int32) if want_scores else None))
         return (best, score) if want_scores else best
 
     def hapq_batch(self, contigs, grp_contig, groups, ranges, snp_positions, block_length):

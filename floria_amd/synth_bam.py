@@ -176,6 +176,89 @@ def nw_affine_batch(Q, R, match=1, mismatch=-1, gap_open=-2, gap_extend=-1, band
     return np.maximum(np.maximum(M[:, m], X[:, m]), Y[:, m])
 
 
+def walk_affine_batch(Q, R, step, rule, tie, block=8, gap_open=-2, gap_extend=-1, want_cells=False):
+    """Scores of N sequence pairs under one member of the FIXED-BLOCK WALK family (scripts/probes/block_walk.c: walk_score, restated for N windows at
+    once): NW1, a gap of length k costs open + (k - 1) * extend, three states per cell (D best, C gap in the column, H gap in the row); a block of
+    `block` x `block` cells plus its border row / column starts at the top-left corner and is shifted right or down by `step` cells, clamped to
+    the matrix, until it holds the last cell; away from the edges the direction compares the block's right border column with its bottom border row
+    (`rule` 0: maxima, 1: sums; `tie` 0: right, 1: down); a cell whose neighbour was never computed sees -infinity from it.  What floria-hip
+    --realign block:STEP,RULE,TIE and floria_hip_realign_walk compute.  want_cells: also the number of cells each walk computed (cells_out)."""
+    N, n = Q.shape
+    m = R.shape[1]
+    B, NEG = int(block), -10 ** 6
+    ar = np.arange(N)
+    D = np.full((N, n + 1, m + 1), NEG, np.int32); Cc = D.copy(); H = D.copy()
+    done = np.zeros((N, n + 1, m + 1), bool)
+
+    def cell(I, J, act):
+        """cell() of the definition for window x at (I[x], J[x]) where act[x] (and the cell has not been computed yet)"""
+        Ic, Jc = np.clip(I, 0, n), np.clip(J, 0, m)
+        act = act & (I <= n) & (J <= m) & ~done[ar, Ic, Jc]
+        if not act.any():
+            return
+        Iu, Jl = np.maximum(Ic - 1, 0), np.maximum(Jc - 1, 0)
+        up = (Ic > 0) & done[ar, Iu, Jc]; left = (Jc > 0) & done[ar, Ic, Jl]; dg = (Ic > 0) & (Jc > 0) & done[ar, Iu, Jl]
+        c = np.where(up, np.maximum(D[ar, Iu, Jc] + gap_open, Cc[ar, Iu, Jc] + gap_extend), NEG)
+        h = np.where(left, np.maximum(D[ar, Ic, Jl] + gap_open, H[ar, Ic, Jl] + gap_extend), NEG)
+        sub = np.where(Q[ar, Iu] == R[ar, Jl], 1, -1)
+        d = np.where(dg, D[ar, Iu, Jl] + sub, NEG)
+        d = np.maximum(d, np.maximum(c, h))
+        origin = (Ic == 0) & (Jc == 0)
+        d = np.where(origin, 0, d); c = np.where(origin, NEG, c); h = np.where(origin, NEG, h)
+        d = np.where(d < NEG // 2, NEG, d); c = np.where(c < NEG // 2, NEG, c); h = np.where(h < NEG // 2, NEG, h)
+        w = np.nonzero(act)[0]
+        D[w, Ic[w], Jc[w]] = d[w]; Cc[w, Ic[w], Jc[w]] = c[w]; H[w, Ic[w], Jc[w]] = h[w]; done[w, Ic[w], Jc[w]] = True
+
+    everyone = np.ones(N, bool)
+    zero = np.zeros(N, np.int64)
+    for i in range(min(B, n) + 1):
+        for j in range(min(B, m) + 1):
+            cell(zero + i, zero + j, everyone)
+    i0 = np.zeros(N, np.int64); j0 = np.zeros(N, np.int64)
+    gi, gj = np.meshgrid(np.arange(B + 1), np.arange(B + 1), indexing="ij")
+    while True:
+        ie, je = np.minimum(i0 + B, n), np.minimum(j0 + B, m)
+        go = ~((ie == n) & (je == m))
+        if not go.any():
+            break
+        a = np.full(N, 0 if rule else NEG, np.int64); b = a.copy()
+        for t in range(B + 1):
+            i = np.minimum(i0 + t, ie); ok = i0 + t <= ie
+            v = np.where(done[ar, i, je], D[ar, i, je], NEG).astype(np.int64)
+            a = np.where(ok, a + v if rule else np.maximum(a, v), a)
+            j = np.minimum(j0 + t, je); ok = j0 + t <= je
+            v = np.where(done[ar, ie, j], D[ar, ie, j], NEG).astype(np.int64)
+            b = np.where(ok, b + v if rule else np.maximum(b, v), b)
+        down = np.where(je == m, True, np.where(ie == n, False, np.where(b > a, True, np.where(a > b, False, bool(tie)))))
+        right = go & ~down; down = go & down
+        j0 = np.where(right, np.where(j0 + step + B > m, max(m - B, 0), j0 + step), j0)
+        i0 = np.where(down, np.where(i0 + step + B > n, max(n - B, 0), i0 + step), i0)
+        # the cells of the new block that the old one did not hold: `step` columns right of je / rows below ie (the rest returns at once in the definition)
+        for s in range(B + 1):
+            for k in range(1, step + 1):
+                I, J = np.where(down, ie + k, i0 + s), np.where(down, j0 + s, je + k)
+                cell(I, J, go & (I <= i0 + B) & (J <= j0 + B))                      # (a clamped shift is shorter than `step`)
+        blk_i = np.minimum(i0[:, None, None] + gi, n); blk_j = np.minimum(j0[:, None, None] + gj, m)
+        assert done[ar[:, None, None], blk_i, blk_j].all(), "a cell of the shifted block was left uncomputed"
+    if want_cells:
+        return D[:, n, m].copy(), done.reshape(N, -1).sum(axis=1)
+    return D[:, n, m].copy()
+
+
+WALK_RULES = {"max": 0, "sum": 1}
+WALK_TIES = {"right": 0, "down": 1}
+
+
+def parse_walk(walk):
+    """(step, rule, tie) with rule / tie as names or numbers -> (step, 0 | 1, 0 | 1), the members floria-hip --realign block:STEP,RULE,TIE accepts"""
+    step, rule, tie = walk
+    rule = WALK_RULES[rule] if isinstance(rule, str) else int(rule)
+    tie = WALK_TIES[tie] if isinstance(tie, str) else int(tie)
+    if int(step) not in (1, 2, 4, 8) or rule not in (0, 1) or tie not in (0, 1):
+        raise ValueError(f"walk {walk!r}: step 1 | 2 | 4 | 8, rule max | sum, tie right | down")
+    return int(step), rule, tie
+
+
 def realign_windows(d, flank=16):
     """The (read window, REF window, ALT window) triples alignment::realign (alignment.rs:21-37) scores for contig_dataset `d`, as uint8 arrays
     [N, 2 * flank], and for each the (read index, cell index) it decides."""
@@ -208,13 +291,17 @@ def realign_windows(d, flank=16):
     return np.array(wq, np.uint8).reshape(-1, 2 * flank), np.array(wr0, np.uint8).reshape(-1, 2 * flank), np.array(wr1, np.uint8).reshape(-1, 2 * flank), where
 
 
-def realign_dataset(d, flank=16):
+def realign_dataset(d, flank=16, walk=None):
     """What alignment::realign (alignment.rs:7-64) makes of the calls of contig_dataset `d`: every call whose 2 x 16-base windows fit is
-    replaced by the allele whose reference window aligns best to the read's window (first best).  Updates d["reads"][...] cells in place."""
+    replaced by the allele whose reference window aligns best to the read's window (first best).  Updates d["reads"][...] cells in place.
+    walk = (step, rule, tie): scored by that member of the fixed-block walk family (walk_affine_batch) instead of the exact DP."""
     Q, R0, R1, where = realign_windows(d, flank)
     if not len(where):
         return 0
-    s0 = nw_affine_batch(Q, R0); s1 = nw_affine_batch(Q, R1)
+    if walk is None:
+        s0 = nw_affine_batch(Q, R0); s1 = nw_affine_batch(Q, R1)
+    else:
+        s0 = walk_affine_batch(Q, R0, *parse_walk(walk)); s1 = walk_affine_batch(Q, R1, *parse_walk(walk))
     changed = 0
     for (ri, k), a0, a1 in zip(where, s0, s1):
         new = 0 if a0 >= a1 else 1
@@ -225,9 +312,9 @@ def realign_dataset(d, flank=16):
     return changed
 
 
-def write_dataset(prefix, contigs, seed=0, extra_vcf_lines=True, edit_frac=0.1, realign=True, sub_rate=0.0):
+def write_dataset(prefix, contigs, seed=0, extra_vcf_lines=True, edit_frac=0.1, realign=True, sub_rate=0.0, walk=None):
     """Write {prefix}.bam / .vcf / .fa for a list of synth Contigs (keep_layout=True).  With realign=False the returned pileups hold the
-    calls as sequenced (floria-hip --no-realign).  Returns, per contig name,
+    calls as sequenced (floria-hip --no-realign), with walk = (step, rule, tie) the calls as floria-hip --realign block:STEP,RULE,TIE makes them.  Returns, per contig name,
     dict(pileup=Pileup in the order a correct ingest produces, names=[read name], spans=[(first_pos_base, last_pos_base)], segments=[[SNPs of alignment k]],
          snp_pos0=[0-based genome position of every SNP], contig_len, seq_len=[bases of every read])."""
     rng = np.random.default_rng(seed)
@@ -239,7 +326,7 @@ def write_dataset(prefix, contigs, seed=0, extra_vcf_lines=True, edit_frac=0.1, 
     for tid, c in enumerate(contigs):
         d = contig_dataset(c, rng, edit_frac=edit_frac, sub_rate=sub_rate)
         if realign:                # the pileup floria makes of these files when a reference FASTA is given (it always is): calls realigned
-            d["realigned_calls"] = realign_dataset(d)
+            d["realigned_calls"] = realign_dataset(d, walk=walk)
         datasets.append(d)
         targets.append((c.name, d["contig_len"]))
         vcf.write(f"##contig=<ID={c.name},length={d['contig_len']}>\n")

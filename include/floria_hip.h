@@ -331,6 +331,17 @@ int  floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* 
 int  floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles,
                         const uint8_t* n_alleles, uint64_t n, uint8_t* best, int32_t* score);
 
+/* The same calls scored by a FIXED-BLOCK WALK instead of the exact DP: a block of `block` x `block` cells starts at the top-left corner of the
+ * alignment matrix and is shifted right or down by `step` cells until it holds the last cell; the direction compares the block's right border
+ * column with its bottom border row (`rule` 0: their maxima, 1: their sums), ties go right (`tie` 0) or down (1); a cell whose neighbour was never
+ * computed sees -infinity from it.  The definition is walk_score() of scripts/probes/block_walk.c; the result is bit-equal to it and never above
+ * the exact score.  Supported members: block 8, step 1 | 2 | 4 | 8, rule 0 | 1, tie 0 | 1; anything else is FLORIA_E_INVALID.  The reference's
+ * block-aligner (block size 8, alignment.rs:14) is SOME fixed-block heuristic; which member it is, if any, is unknown without the crate: the family
+ * is selectable, nothing is pinned, and floria_hip_realign (the exact DP) stays the default everywhere. */
+typedef struct floria_realign_walk { uint32_t block, step, rule, tie; } floria_realign_walk;
+int  floria_hip_realign_walk(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles,
+                             const uint8_t* n_alleles, uint64_t n, const floria_realign_walk* walk, uint8_t* best, int32_t* score);
+
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
 /* Self-test of a hardware assumption: the beam kernel screens the pruning test (global_clustering.rs:98) with an f32 evaluation of stable_binom_cdf_p_rev

@@ -1,6 +1,9 @@
 """floria-hip on a metagenome-shaped synthetic data set: stage times of the batched flow against one contig per device batch.
 
-    python scripts/cli_timing.py [--contigs 60] [--scale 0.5] [--threads 16]
+    python scripts/cli_timing.py [--contigs 60] [--scale 0.5] [--threads 16] [--sub-rate 0.12] [--realign exact|block:STEP,RULE,TIE ...] [--exe PATH] [--only batched]
+
+--realign (repeatable, needs --only or takes the batched run): the batched run once per scoring, in the order given, e.g. --realign exact --realign block:8,max,right
+--realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
 
 Writes BAM / VCF / FASTA under $TMPDIR, runs the driver twice and prints its stage-time lines (stderr of floria-hip)."""
 import argparse
@@ -22,10 +25,14 @@ def main():
     ap.add_argument("--scale", type=float, default=0.5)
     ap.add_argument("--threads", type=int, default=min(32, os.cpu_count() or 1))
     ap.add_argument("--sub-rate", type=float, default=0.0, help="substitution errors in the reads (what realign has to absorb)")
+    ap.add_argument("--realign", action="append", default=[], help="run the batched flow once per given scoring (exact | block:STEP,RULE,TIE), in this order")
+    ap.add_argument("--exe", default=None, help="floria-hip binary to time (default: this tree's, built first)")
+    ap.add_argument("--only", default=None, help="only the runs whose label contains this text")
     ap.add_argument("--arith-compare", action="store_true", help="only: the batched flow at -e 0.04 with --arith canonical against --arith reference (the default there)")
     a = ap.parse_args()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "floria_amd", "host"), "floria-hip"], stdout=subprocess.DEVNULL)
-    exe = os.path.join(ROOT, "floria_amd", "host", "floria-hip")
+    if a.exe is None:
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "floria_amd", "host"), "floria-hip"], stdout=subprocess.DEVNULL)
+    exe = a.exe or os.path.join(ROOT, "floria_amd", "host", "floria-hip")
     tmp = tempfile.mkdtemp(prefix="floria_cli_")
     prefix = os.path.join(tmp, "d")
     t = time.time()
@@ -40,6 +47,10 @@ def main():
         base[base.index("-e") + 1] = "0.04"
         runs = (("e 0.04, canonical arithmetic", ["-t", str(a.threads), "--arith", "canonical"]), ("e 0.04, reference arithmetic", ["-t", str(a.threads), "--arith", "reference"]),
                 ("e 0.04, canonical arithmetic (again)", ["-t", str(a.threads), "--arith", "canonical"]), ("e 0.04, reference arithmetic (again)", ["-t", str(a.threads), "--arith", "reference"]))
+    if a.realign:
+        runs = tuple((f"batched, --realign {spec}" + (" (again)" if spec in a.realign[:k] else ""), ["-t", str(a.threads), "--realign", spec]) for k, spec in enumerate(a.realign))
+    if a.only:
+        runs = tuple(r for r in runs if a.only in r[0])
     for label, extra in runs:
         out = os.path.join(tmp, "o_" + label.replace(" ", "_").replace(",", ""))
         t = time.time()
