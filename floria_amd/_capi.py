@@ -62,11 +62,28 @@ class CTiming(C.Structure):
                 ("streams", C.c_uint32), ("stage_width", C.c_uint32), ("phase_ms", C.c_double),
                 ("upload_pinned_bytes", C.c_uint64), ("upload_staged_bytes", C.c_uint64),
                 ("upload_chunks", C.c_uint32), ("reserved", C.c_uint32),
-                ("beam_union_ms", C.c_double), ("optimize_union_ms", C.c_double)]
+                ("beam_union_ms", C.c_double), ("optimize_union_ms", C.c_double), ("pileup_ms", C.c_double)]
 
 
 class CRealignWalk(C.Structure):
     _fields_ = [("block", C.c_uint32), ("step", C.c_uint32), ("rule", C.c_uint32), ("tie", C.c_uint32)]
+
+
+i64p = C.POINTER(C.c_int64)
+u16p = C.POINTER(C.c_uint16)
+
+
+class CAlignments(C.Structure):
+    _fields_ = [("blob", u8p), ("blob_bytes", C.c_uint64), ("n_records", C.c_uint32), ("pos", i32p), ("flags", u16p), ("contig", u32p),
+                ("cigar_off", u64p), ("n_cigar", u32p), ("seq_off", u64p), ("l_seq", u32p), ("qual_off", u64p)]
+
+
+class CSnpTable(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint32), ("snp_off", u64p), ("snp_pos", i64p), ("alleles", u8p), ("n_alleles", u8p)]
+
+
+class CRecordCells(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("cell_off", u64p), ("snp", u32p), ("allele", u8p), ("qual", u8p), ("seq_pos", u32p), ("ref_end", i64p)]
 
 
 def ptr(a, ctype):

@@ -41,6 +41,7 @@
 #include "stats_kernel.h"
 #include "realign_kernel.h"
 #include "realign_walk_kernel.h"
+#include "pileup_kernel.h"
 #include "upload_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
@@ -244,6 +245,7 @@ struct floria_hip_ctx {
     DevBuf up_tmp;                            // raw allele / qual bytes + the flatten kernel's tables (transient per upload)
     std::vector<Arena*> arena_cache;          // released batch arenas, reused by the next upload
     StagePool stage;                          // pinned staging ring for pageable sources
+    DevBuf pile_in, pile_out;                 // floria_hip_pileup_records: blob + record arrays + SNP table + offsets, and the cell arrays
     uint32_t stage_threads = 8;
 };
 
@@ -366,7 +368,7 @@ struct EventTimer {
         return ms;
     }
 };
-enum { K_BEAM = 0, K_OPT = 1, K_SEL = 2, K_H2D = 3, K_D2H = 4, K_REASSIGN = 5, K_PHASE = 6 };
+enum { K_BEAM = 0, K_OPT = 1, K_SEL = 2, K_H2D = 3, K_D2H = 4, K_REASSIGN = 5, K_PHASE = 6, K_PILEUP = 7 };
 
 void sync_all(floria_hip_ctx* ctx) {
     for (uint32_t g = 0; g < floria_hip_ctx::MAX_LANES; ++g) if (ctx->gstream[g]) (void)hipStreamSynchronize(ctx->gstream[g]);
@@ -969,7 +971,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -2402,6 +2404,134 @@ int floria_hip_realign_walk(floria_hip_ctx* ctx, const uint8_t* read_windows, co
     if (walk->block != 8 || (walk->step != 1 && walk->step != 2 && walk->step != 4 && walk->step != 8) || walk->rule > 1 || walk->tie > 1)
         return fail(FLORIA_E_INVALID, "floria_realign_walk: block must be 8, step 1, 2, 4 or 8, rule 0 (max) or 1 (sum), tie 0 (right) or 1 (down)");
     return realign_windows(ctx, read_windows, ref_windows, alleles, n_alleles, n, walk, best, score);
+}
+
+// ---- frag_from_record (file_reader.rs:661-736) for a batch of alignment records (pileup_kernel.h) -------------------------------------------------
+namespace {
+// every length the kernels rely on, checked on the host before anything is uploaded or launched
+int pileup_validate(const floria_alignments* A, const floria_snp_table* S) {
+    const uint32_t n = A->n_records, nc = S->n_contigs;
+    if (n && (!A->pos || !A->flags || !A->contig || !A->cigar_off || !A->n_cigar || !A->seq_off || !A->l_seq || !A->qual_off)) return fail(FLORIA_E_INVALID, "floria_alignments: null array");
+    if (A->blob_bytes && !A->blob) return fail(FLORIA_E_INVALID, "floria_alignments: null blob");
+    if (!S->snp_off) return fail(FLORIA_E_INVALID, "floria_snp_table: null snp_off");
+    for (uint32_t c = 0; c < nc; ++c)
+        if (S->snp_off[c] > S->snp_off[c + 1]) return fail(FLORIA_E_INVALID, "floria_snp_table: snp_off decreases at contig " + std::to_string(c));
+    const uint64_t b = S->snp_off[0], e = S->snp_off[nc];
+    if (e > b && (!S->snp_pos || !S->alleles || !S->n_alleles)) return fail(FLORIA_E_INVALID, "floria_snp_table: null array");
+    for (uint32_t c = 0; c < nc; ++c)
+        for (uint64_t i = S->snp_off[c] + 1; i < S->snp_off[c + 1]; ++i)
+            if (S->snp_pos[i] <= S->snp_pos[i - 1])
+                return fail(FLORIA_E_INVALID, "floria_snp_table: snp_pos is not strictly ascending at SNP " + std::to_string(i - S->snp_off[c] + 1) + " of contig " + std::to_string(c));
+    for (uint64_t i = b; i < e; ++i) {
+        if (S->n_alleles[i] == 0) return fail(FLORIA_E_INVALID, "floria_snp_table: n_alleles is 0 at SNP " + std::to_string(i) + " (1.." + std::to_string(FLORIA_MAX_ALLELES) + ")");
+        if (S->n_alleles[i] > FLORIA_MAX_ALLELES)
+            return fail(FLORIA_E_UNSUPPORTED, "floria_snp_table: " + std::to_string((unsigned)S->n_alleles[i]) + " alleles at SNP " + std::to_string(i) + " (at most " + std::to_string(FLORIA_MAX_ALLELES) + " are supported)");
+    }
+    const uint64_t B = A->blob_bytes;
+    const auto inside = [B](uint64_t off, uint64_t bytes) { return off <= B && bytes <= B - off; };
+    for (uint32_t i = 0; i < n; ++i) {
+        if (A->contig[i] >= nc) return fail(FLORIA_E_INVALID, "floria_alignments: record " + std::to_string(i) + " names contig " + std::to_string(A->contig[i]) + " of " + std::to_string(nc));
+        const uint64_t l = A->l_seq[i];
+        const char* what = !inside(A->cigar_off[i], 4ull * A->n_cigar[i]) ? "CIGAR" : !inside(A->seq_off[i], (l + 1) / 2) ? "sequence" : !inside(A->qual_off[i], l) ? "quality" : nullptr;
+        if (what) return fail(FLORIA_E_INVALID, std::string("floria_alignments: the ") + what + " bytes of record " + std::to_string(i) + " reach past blob_bytes (" + std::to_string(B) + ")");
+    }
+    return 0;
+}
+void* cells_bytes(uint64_t bytes) { return g_big.get((size_t)std::max<uint64_t>(1, bytes)); }      // (library-owned result arrays: floria_hip_record_cells_free)
+}  // namespace
+
+void floria_hip_record_cells_free(floria_record_cells* r) {
+    if (!r) return;
+    g_big.put(r->cell_off); g_big.put(r->snp); g_big.put(r->allele); g_big.put(r->qual); g_big.put(r->seq_pos); g_big.put(r->ref_end); free(r);
+}
+
+int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, floria_record_cells** out) {
+    if (!ctx || !A || !S || !out) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = pileup_validate(A, S)) return rc;
+    const uint32_t n = A->n_records, nc = S->n_contigs;
+    floria_record_cells* R = (floria_record_cells*)calloc(1, sizeof(floria_record_cells));
+    if (!R) return fail(FLORIA_E_NOMEM, "calloc");
+    // (an error return: nothing may still be copying into the arrays when they are released)
+    struct Guard { floria_record_cells* r; hipStream_t st; ~Guard() { if (r) { (void)hipStreamSynchronize(st); floria_hip_record_cells_free(r); } } } guard{R, ctx->stream};
+    R->n_records = n;
+    R->cell_off = (uint64_t*)cells_bytes(8ull * ((uint64_t)n + 1)); R->ref_end = (int64_t*)cells_bytes(8ull * n);
+    if (!R->cell_off || !R->ref_end) return fail(FLORIA_E_NOMEM, "malloc");
+    R->cell_off[0] = 0;
+    uint64_t total = 0;
+    const auto alloc_cells = [R](uint64_t t) {
+        R->snp = (uint32_t*)cells_bytes(4 * t); R->allele = (uint8_t*)cells_bytes(t); R->qual = (uint8_t*)cells_bytes(t); R->seq_pos = (uint32_t*)cells_bytes(4 * t);
+        return R->snp && R->allele && R->qual && R->seq_pos ? 0 : fail(FLORIA_E_NOMEM, "malloc");
+    };
+    ctx->timing = floria_timing{};
+    if (n == 0) { if (int rc = alloc_cells(0)) return rc; }
+    else {
+        HIPCHK(hipSetDevice(ctx->device));
+        const uint64_t snp_b = S->snp_off[0], n_snps = S->snp_off[nc] - snp_b;
+        const uint32_t n_tiles = (n + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+        Carve C;
+        const Seg s_blob = C.seg(A->blob_bytes), s_pos = C.seg(4ull * n), s_flag = C.seg(2ull * n), s_ctg = C.seg(4ull * n), s_co = C.seg(8ull * n), s_nc = C.seg(4ull * n),
+                  s_so = C.seg(8ull * n), s_ls = C.seg(4ull * n), s_qo = C.seg(8ull * n), s_soff = C.seg(8ull * (nc + 1)), s_sp = C.seg(8 * n_snps), s_al = C.seg(4 * n_snps),
+                  s_na = C.seg(n_snps), s_off = C.seg(8ull * ((uint64_t)n + 1)), s_tile = C.seg(8ull * n_tiles), s_re = C.seg(8ull * n);
+        if (int rc = C.place(ctx->pile_in)) return rc;
+        EventTimer T(ctx->stream);
+        uint64_t pinned_b = 0, staged_b = 0;
+        {
+            std::vector<CopyRun> runs;
+            const auto up = [&](Seg s, const void* src) { if (s.bytes) runs.push_back({(const char*)src, C.at<char>(s), s.bytes}); };
+            up(s_blob, A->blob); up(s_pos, A->pos); up(s_flag, A->flags); up(s_ctg, A->contig); up(s_co, A->cigar_off); up(s_nc, A->n_cigar); up(s_so, A->seq_off);
+            up(s_ls, A->l_seq); up(s_qo, A->qual_off); up(s_soff, S->snp_off);
+            if (n_snps) { up(s_sp, S->snp_pos + snp_b); up(s_al, S->alleles + 4 * snp_b); up(s_na, S->n_alleles + snp_b); }
+            const int t = T.begin(K_H2D);
+            if (int rc = issue_copies(ctx, runs, &pinned_b, &staged_b)) return rc;
+            T.end(t);
+        }
+        fl::PileupArgs a{};
+        a.blob = C.at<const uint8_t>(s_blob); a.pos = C.at<const int32_t>(s_pos); a.flags = C.at<const uint16_t>(s_flag); a.contig = C.at<const uint32_t>(s_ctg);
+        a.cigar_off = C.at<const uint64_t>(s_co); a.n_cigar = C.at<const uint32_t>(s_nc); a.seq_off = C.at<const uint64_t>(s_so); a.l_seq = C.at<const uint32_t>(s_ls);
+        a.qual_off = C.at<const uint64_t>(s_qo); a.snp_off = C.at<const uint64_t>(s_soff);
+        // (the table travels from its first used entry: the kernels index it with the caller's offsets)
+        a.snp_pos = C.at<const int64_t>(s_sp) - snp_b; a.alleles = C.at<const uint8_t>(s_al) - 4 * snp_b; a.n_alleles = C.at<const uint8_t>(s_na) - snp_b;
+        a.cell_off = C.at<uint64_t>(s_off); a.ref_end = C.at<int64_t>(s_re); a.n_records = n;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, (uint64_t)ctx->n_cu * 8);      // one wavefront per record, grid-stride beyond 8 workgroups per CU
+        int t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::pileup_walk_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(fl::pileup_scan_tiles_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, a.cell_off, C.at<uint64_t>(s_tile), n);
+        hipLaunchKernelGGL(fl::pileup_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, C.at<uint64_t>(s_tile), n_tiles, a.cell_off + n);
+        hipLaunchKernelGGL(fl::pileup_scan_add_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a.cell_off, C.at<const uint64_t>(s_tile), n);
+        HIPCHK(hipGetLastError());
+        T.end(t);
+        t = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(R->cell_off, a.cell_off, 8ull * ((uint64_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        total = R->cell_off[n];
+        if (int rc = alloc_cells(total)) return rc;
+        Carve O;
+        const Seg o_snp = O.seg(4 * total), o_al = O.seg(total), o_q = O.seg(total), o_sp = O.seg(4 * total);
+        if (int rc = O.place(ctx->pile_out)) return rc;
+        a.snp = O.at<uint32_t>(o_snp); a.allele = O.at<uint8_t>(o_al); a.qual = O.at<uint8_t>(o_q); a.seq_pos = O.at<uint32_t>(o_sp);
+        t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::pileup_walk_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        T.end(t);
+        t = T.begin(K_D2H);
+        if (total) {
+            HIPCHK(hipMemcpyAsync(R->snp, a.snp, 4 * total, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(R->allele, a.allele, total, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(R->qual, a.qual, total, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(R->seq_pos, a.seq_pos, 4 * total, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIPCHK(hipMemcpyAsync(R->ref_end, a.ref_end, 8ull * n, hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.total_ms = T.span();
+        ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
+    }
+    guard.r = nullptr;
+    *out = R;
+    return 0;
 }
 
 // ---- get_hapq (part_block_manip.rs:517-616) for the haplosets of many contigs (the reference calls it once per contig) ----------

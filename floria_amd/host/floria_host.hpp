@@ -67,6 +67,7 @@ struct Options {
     // fixed-block walk family (floria_hip_realign_walk on the device, walk_affine_score on the host)
     bool realign_walk = false;
     floria_realign_walk walk = {8, 8, 0, 0};
+    bool pileup_device = false;         // --pileup host | device: frag_from_record's CIGAR walk on the host (default) or by floria_hip_pileup_records, one call per ingest round
 };
 // "exact" | "block:STEP,RULE,TIE" (STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down) -> options.realign_walk / options.walk; anything else throws with the grammar
 void parse_realign_spec(const std::string& spec, Options& options);
@@ -301,10 +302,31 @@ struct RealignQueue {
     size_t size() const { return dst.size(); }
     void append(RealignQueue&& other);
 };
+// --pileup device: the CIGAR walks of one ingest round in ONE floria_hip_pileup_records call.  Every record of the given contigs that passes alignment_passed_check is
+// sent as offsets into the segment's inflated buffer (the stretch of bam.raw that holds those records travels as it is); a ContigIngest given the result fills its Frags
+// from the records' cells instead of walking their CIGARs.  A contig whose SNP counters are not rank + 1 in position order (a VCF that repeats a position) or that has a
+// site with more than FLORIA_MAX_ALLELES alleles is not sent: its records keep the host walk (host_contigs names them).
+class RecordPileup {
+public:
+    RecordPileup(Session& s, const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string* contigs, size_t n_contigs);
+    ~RecordPileup();
+    RecordPileup(const RecordPileup&) = delete;
+    RecordPileup& operator=(const RecordPileup&) = delete;
+    struct Cells { const uint32_t* snp; const uint8_t* allele; const uint8_t* qual; const uint32_t* seq_pos; size_t n; int64_t ref_end; };
+    bool cells(uint32_t record_index, Cells& out) const;     // false: the record was not sent
+    size_t records_sent = 0, blob_bytes = 0;
+    double kernel_ms = 0., h2d_ms = 0., d2h_ms = 0.;         // floria_hip_last_timing of the call
+    std::vector<std::string> host_contigs;
+private:
+    floria_record_cells* cells_ = nullptr;
+    std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
+};
 class ContigIngest {
 public:
-    // records of `contig` -> one Frag per passing alignment (file_reader.rs:343-430); with a queue the undecided realignments are deferred
-    ContigIngest(const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string& contig, const std::string* ref_seq, RealignQueue* queue);
+    // records of `contig` -> one Frag per passing alignment (file_reader.rs:343-430); with a queue the undecided realignments are deferred; with a RecordPileup the
+    // records it holds are not walked
+    ContigIngest(const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string& contig, const std::string* ref_seq, RealignQueue* queue,
+                 const RecordPileup* device_cells = nullptr);
     ~ContigIngest();
     ContigIngest(ContigIngest&&) noexcept;
     ContigIngest& operator=(ContigIngest&&) noexcept;

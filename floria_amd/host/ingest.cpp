@@ -191,16 +191,38 @@ int64_t reference_end(const BamRecord& r) {                 // bam_endpos
     return (int64_t)r.pos + (len ? len : 1);
 }
 
-// frag_from_record (file_reader.rs:661-736)
-Frag frag_from_record(const BamRecord& rec, const std::map<GnPosition, SnpPosition>& snp_positions, const std::map<GnPosition, std::vector<Genotype>>& pos_allele_map, size_t counter_id,
-                      bool keep_sequences) {
+// the parts of frag_from_record that do not depend on the SNPs: identity and start before the calls, the read's own bases behind them (:728-734)
+Frag frag_without_calls(const BamRecord& rec, size_t counter_id) {
     Frag frag;
     frag.id = std::string(rec.qname); frag.counter_id = counter_id;
     frag.is_paired = (rec.flags & F_PAIRED1) || (rec.flags & F_PAIRED2);
     frag.first_position = UINT32_MAX; frag.last_position = 0;
+    frag.first_pos_base = (GnPosition)rec.pos;
+    return frag;
+}
+void frag_sequences(Frag& frag, const BamRecord& rec, bool keep_sequences);
+
+// --pileup device: the Frag of a record from the cells floria_hip_pileup_records walked for it (no CIGAR walk, no lookup in the SNP maps)
+Frag frag_from_cells(const BamRecord& rec, const RecordPileup::Cells& cells, size_t counter_id, bool keep_sequences) {
+    Frag frag = frag_without_calls(rec, counter_id);
+    frag.last_pos_base = (GnPosition)cells.ref_end;
+    for (size_t k = 0; k < cells.n; ++k) {                                         // (ascending SNPs: every insert appends)
+        const SnpPosition snp_pos = cells.snp[k];
+        frag.seq_dict[snp_pos] = (Genotype)cells.allele[k];
+        frag.qual_dict[snp_pos] = cells.qual[k];
+        frag.snp_pos_to_seq_pos[snp_pos] = {0, (GnPosition)cells.seq_pos[k]};
+    }
+    if (cells.n) { frag.first_position = cells.snp[0]; frag.last_position = cells.snp[cells.n - 1]; }
+    frag_sequences(frag, rec, keep_sequences);
+    return frag;
+}
+
+// frag_from_record (file_reader.rs:661-736)
+Frag frag_from_record(const BamRecord& rec, const std::map<GnPosition, SnpPosition>& snp_positions, const std::map<GnPosition, std::vector<Genotype>>& pos_allele_map, size_t counter_id,
+                      bool keep_sequences) {
+    Frag frag = frag_without_calls(rec, counter_id);
     size_t leading_hardclips = 0;
     if ((rec.flags & F_SUPP) && !rec.cigar.empty() && cig_op(rec.cigar[0]) == 5) leading_hardclips = cig_len(rec.cigar[0]);
-    frag.first_pos_base = (GnPosition)rec.pos;
     frag.last_pos_base = (GnPosition)reference_end(rec);
     size_t q = 0;
     int64_t r = rec.pos;
@@ -235,6 +257,11 @@ Frag frag_from_record(const BamRecord& rec, const std::map<GnPosition, SnpPositi
         if (consumes_q(op)) q += len;
         if (consumes_r(op)) r += len;                                          // D / N over a SNP: pair[0] is None -> no call
     }
+    frag_sequences(frag, rec, keep_sequences);
+    return frag;
+}
+
+void frag_sequences(Frag& frag, const BamRecord& rec, bool keep_sequences) {
     frag.seq_len[0] = rec.seq.size();
     if (keep_sequences) {                                                      // :728-734
         frag.seq_string[0].resize(rec.seq.size());
@@ -245,7 +272,6 @@ Frag frag_from_record(const BamRecord& rec, const std::map<GnPosition, SnpPositi
         frag.qual_string[0].resize(rec.qual.size());
         for (size_t i = 0; i < rec.qual.size(); ++i) frag.qual_string[0][i] = rec.qual[i] > 222 ? 255 : (uint8_t)(rec.qual[i] + 33);     // checked_add(33).unwrap_or(255)
     }
-    return frag;
 }
 
 struct Tagged { uint16_t flags; Frag frag; };
@@ -873,7 +899,8 @@ ContigIngest::~ContigIngest() = default;
 ContigIngest::ContigIngest(ContigIngest&&) noexcept = default;
 ContigIngest& ContigIngest::operator=(ContigIngest&&) noexcept = default;
 
-ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string& contig, const std::string* ref_seq, RealignQueue* queue)
+ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string& contig, const std::string* ref_seq, RealignQueue* queue,
+                           const RecordPileup* device_cells)
     : p_(new Impl) {
     const bool filter_supplementary = true, use_supplementary = !o.dont_use_supp_aln;
     const auto tid_it = std::find(bam.target_names.begin(), bam.target_names.end(), contig);
@@ -894,10 +921,81 @@ ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Optio
         if (!alignment_passed_check(rec.flags, rec.mapq, use_supplementary, filter_supplementary, o.mapq_cutoff).first) continue;
         auto ins = name_ix.emplace(std::string(rec.qname), names.size());
         if (ins.second) { names.emplace_back(rec.qname); buckets.emplace_back(); }
-        Frag fr = frag_from_record(rec, snp_positions, pos_allele_map, this_count, o.output_reads);
+        RecordPileup::Cells dc;
+        const bool on_device = device_cells && device_cells->cells(rec_ix, dc);
+        Frag fr = on_device ? frag_from_cells(rec, dc, this_count, o.output_reads) : frag_from_record(rec, snp_positions, pos_allele_map, this_count, o.output_reads);
         if (ref_seq) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue, o.realign_walk ? &o.walk : nullptr);             // :416-423
         buckets[ins.first->second].push_back({rec.flags, std::move(fr)});
     }
+}
+
+// ---- --pileup device ------------------------------------------------------------------------------------------------------------------------
+RecordPileup::~RecordPileup() { floria_hip_record_cells_free(cells_); }
+bool RecordPileup::cells(uint32_t rec_ix, Cells& out) const {
+    const uint32_t s = rec_ix < slot_.size() ? slot_[rec_ix] : 0;
+    if (!s) return false;
+    const uint64_t b = cells_->cell_off[s - 1], e = cells_->cell_off[s];
+    out = {cells_->snp + b, cells_->allele + b, cells_->qual + b, cells_->seq_pos + b, (size_t)(e - b), cells_->ref_end[s - 1]};
+    return true;
+}
+RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs) {
+    const bool filter_supplementary = true, use_supplementary = !o.dont_use_supp_aln;
+    // the SNP table of the round's contigs: positions in order, REF + ALT bytes; a contig the device's numbering (rank + 1) would not match stays on the host
+    std::vector<uint64_t> snp_off{0};
+    std::vector<int64_t> snp_pos;
+    std::vector<uint8_t> alleles, n_alleles;
+    std::vector<int32_t> pos;
+    std::vector<uint16_t> flags;
+    std::vector<uint32_t> contig, n_cigar, l_seq, rec_of;
+    std::vector<const unsigned char*> cig_p, seq_p, qual_p;
+    for (size_t ci = 0; ci < n_contigs; ++ci) {
+        const auto tid_it = std::find(bam.target_names.begin(), bam.target_names.end(), contigs[ci]);
+        const auto counters = vp.vcf_pos_to_snp_counter_map.find(contigs[ci]);
+        const auto pam = vp.vcf_pos_allele_map.find(contigs[ci]);
+        if (tid_it == bam.target_names.end() || counters == vp.vcf_pos_to_snp_counter_map.end() || pam == vp.vcf_pos_allele_map.end()) continue;
+        // both maps in lockstep: the same positions, the counters 1, 2, .. in position order, 1 to FLORIA_MAX_ALLELES alleles at every site
+        bool ok = counters->second.size() == pam->second.size();
+        SnpPosition rank = 0;
+        auto al = pam->second.begin();
+        for (auto ct = counters->second.begin(); ok && ct != counters->second.end(); ++ct, ++al)
+            ok = ct->first == al->first && ct->second == ++rank && !al->second.empty() && al->second.size() <= FLORIA_MAX_ALLELES;
+        if (!ok) { host_contigs.push_back(contigs[ci]); continue; }
+        const uint32_t table_ix = (uint32_t)snp_off.size() - 1;
+        for (const auto& kv : pam->second) {
+            snp_pos.push_back((int64_t)kv.first);
+            for (size_t a = 0; a < FLORIA_MAX_ALLELES; ++a) alleles.push_back(a < kv.second.size() ? kv.second[a] : 0);
+            n_alleles.push_back((uint8_t)kv.second.size());
+        }
+        snp_off.push_back(snp_pos.size());
+        for (const uint32_t rec_ix : bam.by_tid[(size_t)(tid_it - bam.target_names.begin())]) {
+            const BamRecord& rec = bam.records[rec_ix];
+            if (!alignment_passed_check(rec.flags, rec.mapq, use_supplementary, filter_supplementary, o.mapq_cutoff).first) continue;
+            pos.push_back(rec.pos); flags.push_back(rec.flags); contig.push_back(table_ix); n_cigar.push_back((uint32_t)rec.cigar.n); l_seq.push_back((uint32_t)rec.seq.n);
+            cig_p.push_back(rec.cigar.p); seq_p.push_back(rec.seq.packed); qual_p.push_back(rec.qual.p); rec_of.push_back(rec_ix);
+        }
+    }
+    const size_t n = pos.size();
+    records_sent = n;
+    if (n == 0) return;
+    // the stretch of the inflated buffer that holds these records' CIGARs, bases and qualities (a round's contigs are neighbours in a sorted BAM)
+    const unsigned char *lo = cig_p[0], *hi = cig_p[0];
+    for (size_t i = 0; i < n; ++i) {
+        lo = std::min({lo, cig_p[i], seq_p[i], qual_p[i]});
+        hi = std::max({hi, cig_p[i] + 4 * (size_t)n_cigar[i], seq_p[i] + ((size_t)l_seq[i] + 1) / 2, qual_p[i] + l_seq[i]});
+    }
+    std::vector<uint64_t> cigar_off(n), seq_off(n), qual_off(n);
+    for (size_t i = 0; i < n; ++i) { cigar_off[i] = (uint64_t)(cig_p[i] - lo); seq_off[i] = (uint64_t)(seq_p[i] - lo); qual_off[i] = (uint64_t)(qual_p[i] - lo); }
+    blob_bytes = (size_t)(hi - lo);
+    floria_alignments A{};
+    A.blob = lo; A.blob_bytes = blob_bytes; A.n_records = (uint32_t)n; A.pos = pos.data(); A.flags = flags.data(); A.contig = contig.data();
+    A.cigar_off = cigar_off.data(); A.n_cigar = n_cigar.data(); A.seq_off = seq_off.data(); A.l_seq = l_seq.data(); A.qual_off = qual_off.data();
+    floria_snp_table S{};
+    S.n_contigs = (uint32_t)snp_off.size() - 1; S.snp_off = snp_off.data(); S.snp_pos = snp_pos.data(); S.alleles = alleles.data(); S.n_alleles = n_alleles.data();
+    if (const int rc = floria_hip_pileup_records(session.ctx(), &A, &S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
+    floria_timing tm;
+    if (floria_hip_last_timing(session.ctx(), &tm) == 0) { kernel_ms = tm.pileup_ms; h2d_ms = tm.h2d_ms; d2h_ms = tm.d2h_ms; }
+    slot_.assign(bam.records.size(), 0);
+    for (size_t i = 0; i < n; ++i) slot_[rec_of[i]] = (uint32_t)i + 1;
 }
 
 std::pair<std::vector<Frag>, std::vector<Frag>> ContigIngest::finish() {

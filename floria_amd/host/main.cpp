@@ -15,6 +15,8 @@
 // --batch-contigs N / --batch-cells N (size of a device batch), --debug (debug_graph.txt per contig), --lp-tie first|last (which optimal vertex of the
 // stitching LP is used where the optimum is not unique; the run reports how many contigs that concerns), and for tests --dump-frags FILE,
 // --ingest-only, --no-realign, --stitch-graph FILE.
+// --pileup host | device: where the CIGAR walk that turns alignment records into SNP calls runs.  host [default]: frag_from_record on -t threads, one contig per task;
+// device: one floria_hip_pileup_records call per ingest round for every record that passes the alignment filter, the Frags filled from its cells (same files).
 // --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
 // RULE max | sum, TIE right | down): one member of the family of fixed-block walks (block 8) that scripts/probes/block_walk.c defines.  The reference's block-aligner is
 // some heuristic of this kind; which member, if any, is not known, so there is no bare `block`.  The run's log and cmd.log name the scoring used.
@@ -61,6 +63,7 @@ void usage() {
           "  --epsilon-round   round an ESTIMATED -e to a multiple of 2^-10 (there both arithmetics are the same function)\n"
           "  --lp-tie first|last, --lp-report   which optimal vertex of the stitching LP is used where the optimum is not unique, and how often that is\n"
           "  --no-realign      skip the re-alignment of the reads' bases around SNPs\n"
+          "  --pileup host|device   where alignment records become SNP calls (the CIGAR walk): on the host threads [default] or in one device call per ingest round; same files\n"
           "  --realign exact | block:STEP,RULE,TIE   how that re-alignment scores a window: exact [default] = the exact affine-gap alignment; block:... = a walk of a fixed\n"
           "                 8 x 8 block over the alignment matrix, shifted by STEP = 1 | 2 | 4 | 8 cells towards the larger border by RULE = max | sum, ties going\n"
           "                 TIE = right | down (e.g. block:8,max,right).  floria's block-aligner is a heuristic of this kind; which member is unknown, so one must be named\n"
@@ -208,6 +211,11 @@ int main(int argc, char** argv) {
             else if (a == "--dump-frags") dump_frags = val();
             else if (a == "--no-realign") no_realign = true;                   // (tests) keep the alleles as called
             else if (a == "--realign") { parse_realign_spec(val(), o); have_realign = true; }
+            else if (a == "--pileup") {
+                const std::string v = val();
+                if (v != "host" && v != "device") throw Error(FLORIA_E_INVALID, "--pileup takes host or device, not '" + v + "'");
+                o.pileup_device = v == "device";
+            }
             else if (a == "--ingest-only") ingest_only = true;          // (tests) stop after ingest: needs no GPU
             else if (a == "--stitch-graph") stitch_graph = val();       // (tests) N / E lines of a hap graph -> F / P lines on stdout: needs no GPU
             else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -325,7 +333,7 @@ int main(int argc, char** argv) {
         // one context per device of --devices (default: the one --device); every one throws without a usable MI355X: no CPU fallback
         if (devices.empty()) devices.push_back(o.device);
         std::vector<std::unique_ptr<Session>> sessions;
-        if (!ingest_only) for (int d : devices) sessions.emplace_back(new Session(d));
+        if (!ingest_only || o.pileup_device) for (int d : devices) sessions.emplace_back(new Session(d));     // (--ingest-only --pileup device needs a device for the walk)
         for (auto& s : sessions) if (floria_hip_set_option(s->ctx(), "arith", reference_arith ? 1 : 0) != 0) throw Error(FLORIA_E_INVALID, floria_hip_last_error());
         // The reference-arithmetic mode adds a read's terms in the iteration order of its position set.  For a fragment built from ONE alignment the library emulates that
         // set on the device (arith_kernel.h); fragments whose set was EXTENDED by a mate or a supplementary piece (file_reader.rs:541, 639) or cut down by
@@ -342,6 +350,9 @@ int main(int argc, char** argv) {
         const size_t n_threads = std::max<size_t>(1, o.num_threads);
         double t_ingest = 0., t_s1 = 0., t_stitch = 0., t_s2 = 0., t_stats = 0., t_write = 0., t_realign = 0., t_stream = 0.;
         size_t n_realign_device = 0, n_batches = 0, n_records = 0, n_segments = 0;
+        size_t n_pileup_records = 0, n_pileup_bytes = 0, n_pileup_calls = 0;      // --pileup device
+        double t_pileup = 0., t_pileup_kernels = 0., t_pileup_h2d = 0., t_pileup_d2h = 0.;
+        bool said_host_walk = false;
         // every contig that will be phased must be in the reference FASTA: said before anything is written, not when its batch comes up
         if (!ingest_only)
             for (const std::string& contig : contigs) {
@@ -385,11 +396,25 @@ int main(int argc, char** argv) {
                 std::vector<std::unique_ptr<ContigIngest>> ing(take);
                 std::vector<RealignQueue> queues(take);
                 const bool on_device = !ingest_only && !no_realign;
+                std::unique_ptr<RecordPileup> device_cells;                    // --pileup device: the round's CIGAR walks in one device call
+                if (o.pileup_device) {
+                    const double tw = now_s();
+                    device_cells.reset(new RecordPileup(*session_holder, bam, vp, o, &todo[done], take));
+                    t_pileup += now_s() - tw;
+                    ++n_pileup_calls; n_pileup_records += device_cells->records_sent; n_pileup_bytes += device_cells->blob_bytes;
+                    t_pileup_kernels += device_cells->kernel_ms * 1e-3; t_pileup_h2d += device_cells->h2d_ms * 1e-3; t_pileup_d2h += device_cells->d2h_ms * 1e-3;
+                    if (!device_cells->host_contigs.empty() && !said_host_walk) {
+                        said_host_walk = true;
+                        fprintf(stderr, "floria-hip: --pileup device: contig %s keeps the host walk (its SNP numbers are not their rank in position order, or a site has more than %d alleles); "
+                                        "this is said once\n", device_cells->host_contigs[0].c_str(), FLORIA_MAX_ALLELES);
+                    }
+                }
                 parallel_for(take, n_threads, [&](size_t i) {
                     const std::string& contig = todo[done + i];
                     const auto fa = fasta.find(contig);
-                    ing[i].reset(new ContigIngest(bam, vp, o, contig, (fa != fasta.end() && !no_realign) ? &fa->second : nullptr, on_device ? &queues[i] : nullptr));
+                    ing[i].reset(new ContigIngest(bam, vp, o, contig, (fa != fasta.end() && !no_realign) ? &fa->second : nullptr, on_device ? &queues[i] : nullptr, device_cells.get()));
                 });
+                device_cells.reset();
                 if (on_device) {
                     const double tr = now_s();
                     RealignQueue all;
@@ -511,6 +536,9 @@ int main(int argc, char** argv) {
         fprintf(stderr, "BAM: %zu records in %zu segments, %.3fs of inflate + decode, largest inflated buffer %zu MiB\n", n_records, n_segments, t_stream, stream.peak_buffer_bytes() >> 20);
         fprintf(stderr, "Realignment: %zu calls scored on the device in %.3fs (inside the ingest time), scoring %s\n", n_realign_device, t_realign,
                 o.realign_walk ? ("fixed-block walk " + realign_spec(o)).c_str() : "exact affine-gap DP");
+        if (o.pileup_device)
+            fprintf(stderr, "Pileup on the device: %zu records, %zu blob bytes in %zu calls, %.3fs (inside the ingest time; device events: upload %.3fs, kernels %.3fs, download %.3fs)\n",
+                    n_pileup_records, n_pileup_bytes, n_pileup_calls, t_pileup, t_pileup_h2d, t_pileup_kernels, t_pileup_d2h);
         fprintf(stderr, "Batches %zu; ingest %.3fs, phasing (upload + S1 + graph) %.3fs, LP + paths %.3fs, S2 %.3fs, COV/ERR/HAPQ %.3fs, writers %.3fs\n", n_batches, t_ingest, t_s1,
                 t_stitch, t_s2, t_stats, t_write);
         if (reference_arith && n_batches_orders)

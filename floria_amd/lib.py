@@ -28,6 +28,7 @@ SYMBOLS = [
     "floria_hip_hapq", "floria_hip_hapq_batch",
     "floria_hip_contig_upload_batch", "floria_hip_host_alloc", "floria_hip_host_free", "floria_hip_set_option",
     "floria_hip_contig_download", "floria_hip_phase_pileups_batch",
+    "floria_hip_pileup_records", "floria_hip_record_cells_free",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -60,7 +61,7 @@ def load():
         L.floria_hip_last_error.restype = C.c_char_p
         L.floria_hip_version.restype = C.c_char_p
         for s in ("floria_hip_destroy", "floria_hip_ranges_free", "floria_hip_contig_free", "floria_hip_block_result_free", "floria_hip_groups_free",
-                  "floria_hip_groups_array_free", "floria_hip_hap_graph_free"):
+                  "floria_hip_groups_array_free", "floria_hip_hap_graph_free", "floria_hip_record_cells_free"):
             getattr(L, s).restype = None
         L.floria_hip_destroy.argtypes = [C.c_void_p]
         L.floria_hip_contig_free.argtypes = [C.c_void_p]
@@ -75,6 +76,8 @@ def load():
         L.floria_hip_pack_bytes_batch.argtypes = [C.c_void_p, C.c_uint32]
         L.floria_hip_pack_pileups_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
         L.floria_hip_pack_pileup.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.floria_hip_pileup_records.argtypes = [C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(C.POINTER(capi.CRecordCells))]
+        L.floria_hip_record_cells_free.argtypes = [C.POINTER(capi.CRecordCells)]
         _LIB = L
     return _LIB
 
@@ -437,6 +440,36 @@ class FloriaHip:
         _check(load().floria_hip_realign_walk(self._h, capi.ptr(q, C.c_uint8), capi.ptr(r, C.c_uint8), capi.ptr(al, C.c_uint8), capi.ptr(na, C.c_uint8), C.c_uint64(n),
                                               C.byref(walk), capi.ptr(best, C.c_uint8), capi.ptr(score, C.c_int32) if want_scores else None))
         return (best, score) if want_scores else best
+
+    def pileup_records(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles):
+        """floria_hip_pileup_records: frag_from_record (file_reader.rs:661-736) for n alignment records given as offsets into one byte `blob`
+        (pos int32 [n], flags uint16 [n], contig uint32 [n], cigar_off / seq_off / qual_off uint64 [n], n_cigar / l_seq uint32 [n]) against a SNP table
+        (snp_off uint64 [n_contigs + 1], snp_pos int64, alleles uint8 [n_snps, 4], n_alleles uint8) -> numpy arrays
+        (cell_off uint64 [n + 1], snp uint32, allele uint8, qual uint8, seq_pos uint32, ref_end int64 [n]).  Arrays that live in a PinnedArena go up by DMA."""
+        def arr(a, dt):
+            return a if isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous else np.ascontiguousarray(a, dt)
+        keep = [arr(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8), arr(pos, np.int32), arr(flags, np.uint16),
+                arr(contig, np.uint32), arr(cigar_off, np.uint64), arr(n_cigar, np.uint32), arr(seq_off, np.uint64), arr(l_seq, np.uint32), arr(qual_off, np.uint64),
+                arr(snp_off, np.uint64), arr(snp_pos, np.int64), arr(alleles, np.uint8), arr(n_alleles, np.uint8)]      # every input buffer stays alive until the call returns
+        b, po, fl, ct, co, ncg, so, ls, qo, soff, sp, al, na = keep
+        n = len(po)
+        if not all(len(x) == n for x in (fl, ct, co, ncg, so, ls, qo)):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "pileup_records: the record arrays differ in length")
+        if len(soff) < 1 or not (len(sp) == len(na) and al.size == 4 * len(sp)) or (len(soff) and int(soff[-1]) > len(sp)):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "pileup_records: snp_off needs n_contigs + 1 entries, the last at most the number of SNPs; alleles is [n_snps, 4]")
+        A = capi.CAlignments(capi.ptr(b, C.c_uint8), b.size, n, capi.ptr(po, C.c_int32), capi.ptr(fl, C.c_uint16), capi.ptr(ct, C.c_uint32), capi.ptr(co, C.c_uint64),
+                             capi.ptr(ncg, C.c_uint32), capi.ptr(so, C.c_uint64), capi.ptr(ls, C.c_uint32), capi.ptr(qo, C.c_uint64))
+        S = capi.CSnpTable(len(soff) - 1, capi.ptr(soff, C.c_uint64), capi.ptr(sp, C.c_int64), capi.ptr(al, C.c_uint8), capi.ptr(na, C.c_uint8))
+        out = C.POINTER(capi.CRecordCells)()
+        _check(load().floria_hip_pileup_records(self._h, C.byref(A), C.byref(S), C.byref(out)))
+        r = out.contents
+        cell_off = capi.np_from(r.cell_off, n + 1, np.uint64)
+        t = int(cell_off[n])
+        res = (cell_off, capi.np_from(r.snp, t, np.uint32), capi.np_from(r.allele, t, np.uint8), capi.np_from(r.qual, t, np.uint8),
+               capi.np_from(r.seq_pos, t, np.uint32), capi.np_from(r.ref_end, n, np.int64))
+        load().floria_hip_record_cells_free(out)
+        del keep
+        return res
 
     def hapq_batch(self, contigs, grp_contig, groups, ranges, snp_positions, block_length):
         """get_hapq for the haplosets of many contigs in one call -> (hapq uint8 [n], rel_err float64 [n], avg_err float64 [n_contigs])."""

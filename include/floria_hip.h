@@ -170,6 +170,8 @@ typedef struct {
     uint32_t reserved;
     double   beam_union_ms;    /* wall time with at least one beam-search launch in flight (<= phase_ms; beam_ms, a sum over overlapping launches, can exceed it) */
     double   optimize_union_ms;/* ... with at least one optimise launch in flight */
+    double   pileup_ms;        /* floria_hip_pileup_records: sum over the call's launches (count pass, offset scan, fill pass).  Appended with that entry point:
+                                * floria_hip_last_timing writes the whole struct, so callers built against the shorter layout must be rebuilt */
 } floria_timing;
 
 typedef struct floria_hip_ctx floria_hip_ctx;
@@ -341,6 +343,51 @@ int  floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const 
 typedef struct floria_realign_walk { uint32_t block, step, rule, tie; } floria_realign_walk;
 int  floria_hip_realign_walk(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles,
                              const uint8_t* n_alleles, uint64_t n, const floria_realign_walk* walk, uint8_t* best, int32_t* score);
+
+/* ---- frag_from_record (file_reader.rs:661-736) on the device: alignment records -> SNP calls ------------------------------------------------------
+ * Alignment records as offsets into one byte blob. The blob may be an uncompressed BAM alignment section as it is
+ * (offsets point into the records), or arrays the host packed itself. Nothing is assumed about alignment. */
+typedef struct {
+    const uint8_t*  blob;  uint64_t blob_bytes;
+    uint32_t        n_records;
+    const int32_t*  pos;        /* [n] 0-based leftmost reference position (BAM `pos`)                        */
+    const uint16_t* flags;      /* [n] BAM FLAG; only 0x800 is read (leading hard clip of a supplementary)    */
+    const uint32_t* contig;     /* [n] index into the SNP table                                               */
+    const uint64_t* cigar_off;  /* [n] byte offset of n_cigar[i] little-endian u32 ops (len << 4 | op)        */
+    const uint32_t* n_cigar;    /* [n]                                                                        */
+    const uint64_t* seq_off;    /* [n] byte offset of (l_seq[i]+1)/2 bytes, two bases per byte, high nibble first (BAM) */
+    const uint32_t* l_seq;      /* [n]                                                                        */
+    const uint64_t* qual_off;   /* [n] byte offset of l_seq[i] quality bytes                                  */
+} floria_alignments;
+
+typedef struct {
+    uint32_t        n_contigs;
+    const uint64_t* snp_off;    /* [n_contigs+1]                                                              */
+    const int64_t*  snp_pos;    /* 0-based genome positions, strictly ascending inside a contig; the SNP's    */
+                                /* 1-based index (SnpPosition) is its rank in the contig + 1                  */
+    const uint8_t*  alleles;    /* [4 * n_snps] the record's REF then ALT bases, as bytes                     */
+    const uint8_t*  n_alleles;  /* [n_snps] 1..4                                                              */
+} floria_snp_table;
+
+typedef struct {               /* library-owned; record i owns cells [cell_off[i], cell_off[i+1]), ascending snp */
+    uint32_t  n_records;
+    uint64_t* cell_off;  uint32_t* snp;  uint8_t* allele;  uint8_t* qual;  uint32_t* seq_pos;
+    int64_t*  ref_end;         /* [n] bam_endpos: pos + reference bases consumed (1 if none)                  */
+} floria_record_cells;
+
+/* One record's walk: a query cursor q = 0 and a reference cursor r = pos go through the CIGAR; for an M, = or X run [r, r + len) every SNP of the record's
+ * contig with r <= snp_pos < r + len is visited: seq_pos = q + (snp_pos - r); if seq_pos < l_seq the base there is decoded with "=ACMGRSVTWYHKDBN", and if it
+ * equals alleles[k] (as a byte) for some k < n_alleles, ONE cell is emitted for the first such k: snp = the SNP's rank in its contig + 1, allele = k, qual = the
+ * quality byte at seq_pos, seq_pos = seq_pos plus the length of a leading H operation when flag 0x800 is set (modulo 2^32).  D and N advance r only (a SNP under
+ * them yields nothing), I and S advance q only, H and P neither.  SNP indices are the table's own (snp_pos, alleles, n_alleles are indexed from 0, contig c
+ * owning [snp_off[c], snp_off[c+1])).
+ * The host part validates every input before anything is launched: every offset range against blob_bytes, contig < n_contigs, non-decreasing snp_off, strictly
+ * ascending snp_pos inside a contig, n_alleles >= 1 (FLORIA_E_INVALID each) and n_alleles <= 4 (FLORIA_E_UNSUPPORTED, as elsewhere); the kernels
+ * (csrc/pileup_kernel.h) bound every access by those lengths.  The blob and the arrays go up by DMA where they lie in floria_hip_host_alloc memory and through the
+ * library's pinned staging ring otherwise; every result array comes back in one transfer.  floria_hip_last_timing then reports h2d_ms, d2h_ms, pileup_ms,
+ * total_ms and upload_pinned_bytes / upload_staged_bytes of the call. */
+int  floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* alignments, const floria_snp_table* snps, floria_record_cells** out);
+void floria_hip_record_cells_free(floria_record_cells* cells);
 
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
