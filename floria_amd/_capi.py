@@ -86,6 +86,14 @@ class CRecordCells(C.Structure):
     _fields_ = [("n_records", C.c_uint32), ("cell_off", u64p), ("snp", u32p), ("allele", u8p), ("qual", u8p), ("seq_pos", u32p), ("ref_end", i64p)]
 
 
+class CRefSeqs(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint32), ("seq_off", u64p), ("seq", u8p)]
+
+
+class CRealignCounts(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("in_bounds", C.c_uint64), ("shortcut", C.c_uint64), ("scored", C.c_uint64), ("changed", C.c_uint64)]
+
+
 def ptr(a, ctype):
     """Pointer to a C-contiguous numpy array (the array must outlive the call)."""
     return a.ctypes.data_as(C.POINTER(ctype))

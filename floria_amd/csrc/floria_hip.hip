@@ -42,6 +42,7 @@
 #include "realign_kernel.h"
 #include "realign_walk_kernel.h"
 #include "pileup_kernel.h"
+#include "realign_gather_kernel.h"
 #include "upload_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
@@ -2367,6 +2368,12 @@ hipError_t launch_realign_walk(const floria_hip_ctx* ctx, const floria_realign_w
         return hipGetLastError();
     }); }); });
 }
+// the members realign_walk_kernel<..> is instantiated for
+int walk_member_validate(const floria_realign_walk* walk) {
+    if (walk->block != 8 || (walk->step != 1 && walk->step != 2 && walk->step != 4 && walk->step != 8) || walk->rule > 1 || walk->tie > 1)
+        return fail(FLORIA_E_INVALID, "floria_realign_walk: block must be 8, step 1, 2, 4 or 8, rule 0 (max) or 1 (sum), tie 0 (right) or 1 (down)");
+    return 0;
+}
 // upload the windows, score them (walk == null: the exact DP), fetch the calls
 int realign_windows(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles, const uint8_t* n_alleles,
                     uint64_t n, const floria_realign_walk* walk, uint8_t* best, int32_t* score) {
@@ -2401,8 +2408,7 @@ int floria_hip_realign(floria_hip_ctx* ctx, const uint8_t* read_windows, const u
 int floria_hip_realign_walk(floria_hip_ctx* ctx, const uint8_t* read_windows, const uint8_t* ref_windows, const uint8_t* alleles, const uint8_t* n_alleles,
                             uint64_t n, const floria_realign_walk* walk, uint8_t* best, int32_t* score) {
     if (!walk) return fail(FLORIA_E_INVALID, "null argument");
-    if (walk->block != 8 || (walk->step != 1 && walk->step != 2 && walk->step != 4 && walk->step != 8) || walk->rule > 1 || walk->tie > 1)
-        return fail(FLORIA_E_INVALID, "floria_realign_walk: block must be 8, step 1, 2, 4 or 8, rule 0 (max) or 1 (sum), tie 0 (right) or 1 (down)");
+    if (int rc = walk_member_validate(walk)) return rc;
     return realign_windows(ctx, read_windows, ref_windows, alleles, n_alleles, n, walk, best, score);
 }
 
@@ -2437,6 +2443,16 @@ int pileup_validate(const floria_alignments* A, const floria_snp_table* S) {
     }
     return 0;
 }
+// the reference sequences of floria_hip_pileup_records_realign: one (possibly empty) sequence per contig of the SNP table
+int refs_validate(const floria_ref_seqs* F, const floria_snp_table* S) {
+    if (F->n_contigs != S->n_contigs)
+        return fail(FLORIA_E_INVALID, "floria_ref_seqs: " + std::to_string(F->n_contigs) + " contigs, the SNP table has " + std::to_string(S->n_contigs));
+    if (!F->seq_off) return fail(FLORIA_E_INVALID, "floria_ref_seqs: null seq_off");
+    for (uint32_t c = 0; c < F->n_contigs; ++c)
+        if (F->seq_off[c] > F->seq_off[c + 1]) return fail(FLORIA_E_INVALID, "floria_ref_seqs: seq_off decreases at contig " + std::to_string(c));
+    if (F->seq_off[F->n_contigs] > F->seq_off[0] && !F->seq) return fail(FLORIA_E_INVALID, "floria_ref_seqs: null seq");
+    return 0;
+}
 void* cells_bytes(uint64_t bytes) { return g_big.get((size_t)std::max<uint64_t>(1, bytes)); }      // (library-owned result arrays: floria_hip_record_cells_free)
 }  // namespace
 
@@ -2445,13 +2461,22 @@ void floria_hip_record_cells_free(floria_record_cells* r) {
     g_big.put(r->cell_off); g_big.put(r->snp); g_big.put(r->allele); g_big.put(r->qual); g_big.put(r->seq_pos); g_big.put(r->ref_end); free(r);
 }
 
-int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, floria_record_cells** out) {
+namespace {
+// The body of floria_hip_pileup_records and floria_hip_pileup_records_realign: upload, COUNT, offset scan, FILL, download.  With reference sequences (F) the cells'
+// alleles are realigned on the device between FILL and the download (realign_gather_kernel.h): DECIDE, one read of its counters, then — when anything is left
+// undecided — FILL of the work list, the scoring kernel (walk == null: the exact DP) and the scatter.  Without F nothing of that is allocated, uploaded or launched.
+int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F, const floria_realign_walk* walk,
+                        floria_record_cells** out, floria_realign_counts* counts) {
     if (!ctx || !A || !S || !out) return fail(FLORIA_E_INVALID, "null argument");
     *out = nullptr;
+    if (counts) *counts = floria_realign_counts{};
     if (int rc = pileup_validate(A, S)) return rc;
+    if (F) { if (int rc = refs_validate(F, S)) return rc; }
+    if (walk) { if (int rc = walk_member_validate(walk)) return rc; }
     const uint32_t n = A->n_records, nc = S->n_contigs;
     floria_record_cells* R = (floria_record_cells*)calloc(1, sizeof(floria_record_cells));
     if (!R) return fail(FLORIA_E_NOMEM, "calloc");
+    uint64_t hc[fl::RG_N_COUNTS] = {};      // the realignment's counters come back here: declared before `guard`, which synchronises the stream on every early return, so no copy outlives it
     // (an error return: nothing may still be copying into the arrays when they are released)
     struct Guard { floria_record_cells* r; hipStream_t st; ~Guard() { if (r) { (void)hipStreamSynchronize(st); floria_hip_record_cells_free(r); } } } guard{R, ctx->stream};
     R->n_records = n;
@@ -2473,6 +2498,8 @@ int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, c
         const Seg s_blob = C.seg(A->blob_bytes), s_pos = C.seg(4ull * n), s_flag = C.seg(2ull * n), s_ctg = C.seg(4ull * n), s_co = C.seg(8ull * n), s_nc = C.seg(4ull * n),
                   s_so = C.seg(8ull * n), s_ls = C.seg(4ull * n), s_qo = C.seg(8ull * n), s_soff = C.seg(8ull * (nc + 1)), s_sp = C.seg(8 * n_snps), s_al = C.seg(4 * n_snps),
                   s_na = C.seg(n_snps), s_off = C.seg(8ull * ((uint64_t)n + 1)), s_tile = C.seg(8ull * n_tiles), s_re = C.seg(8ull * n);
+        const uint64_t ref_b = F ? F->seq_off[0] : 0, ref_bytes = F ? F->seq_off[nc] - ref_b : 0;
+        const Seg s_roff = C.seg(F ? 8ull * (nc + 1) : 0), s_ref = C.seg(ref_bytes), s_cnt = C.seg(F ? 8ull * fl::RG_N_COUNTS : 0);
         if (int rc = C.place(ctx->pile_in)) return rc;
         EventTimer T(ctx->stream);
         uint64_t pinned_b = 0, staged_b = 0;
@@ -2482,6 +2509,7 @@ int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, c
             up(s_blob, A->blob); up(s_pos, A->pos); up(s_flag, A->flags); up(s_ctg, A->contig); up(s_co, A->cigar_off); up(s_nc, A->n_cigar); up(s_so, A->seq_off);
             up(s_ls, A->l_seq); up(s_qo, A->qual_off); up(s_soff, S->snp_off);
             if (n_snps) { up(s_sp, S->snp_pos + snp_b); up(s_al, S->alleles + 4 * snp_b); up(s_na, S->n_alleles + snp_b); }
+            if (F) { up(s_roff, F->seq_off); if (ref_bytes) up(s_ref, F->seq + ref_b); }
             const int t = T.begin(K_H2D);
             if (int rc = issue_copies(ctx, runs, &pinned_b, &staged_b)) return rc;
             T.end(t);
@@ -2509,14 +2537,52 @@ int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, c
         total = R->cell_off[n];
         if (int rc = alloc_cells(total)) return rc;
         Carve O;
-        const Seg o_snp = O.seg(4 * total), o_al = O.seg(total), o_q = O.seg(total), o_sp = O.seg(4 * total);
+        const Seg o_snp = O.seg(4 * total), o_al = O.seg(total), o_q = O.seg(total), o_sp = O.seg(4 * total), o_und = O.seg(F ? total : 0);
         if (int rc = O.place(ctx->pile_out)) return rc;
         a.snp = O.at<uint32_t>(o_snp); a.allele = O.at<uint8_t>(o_al); a.qual = O.at<uint8_t>(o_q); a.seq_pos = O.at<uint32_t>(o_sp);
         t = T.begin(K_PILEUP);
         hipLaunchKernelGGL(fl::pileup_walk_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
         T.end(t);
+        if (F && total) {
+            fl::RealignGatherArgs r{};
+            r.blob = a.blob; r.contig = a.contig; r.seq_off = a.seq_off; r.l_seq = a.l_seq; r.cell_off = a.cell_off; r.snp_off = a.snp_off; r.snp_pos = a.snp_pos;
+            r.alleles = a.alleles; r.n_alleles = a.n_alleles; r.ref_off = C.at<const uint64_t>(s_roff); r.ref_seq = C.at<const uint8_t>(s_ref) - ref_b;
+            r.snp = a.snp; r.seq_pos = a.seq_pos; r.allele = a.allele; r.undecided = O.at<uint8_t>(o_und); r.counts = C.at<uint64_t>(s_cnt);
+            r.n_cells = total; r.n_records = n;
+            const uint32_t ggrid = (uint32_t)std::min<uint64_t>((total + 7) / 8, (uint64_t)ctx->n_cu * 8);      // 8 cells per workgroup and trip
+            t = T.begin(K_PILEUP);
+            HIPCHK(hipMemsetAsync(r.counts, 0, 8ull * fl::RG_N_COUNTS, ctx->stream));
+            hipLaunchKernelGGL(fl::realign_decide_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, r);
+            HIPCHK(hipGetLastError());
+            T.end(t);
+            t = T.begin(K_D2H);
+            HIPCHK(hipMemcpyAsync(hc, r.counts, sizeof hc, hipMemcpyDeviceToHost, ctx->stream));      // the work list is sized from the count, not from 69 B x cells
+            T.end(t);
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            const uint64_t n_work = hc[fl::RG_SCORED];
+            if (n_work > total) return fail(FLORIA_E_DEVICE, "realign: more undecided cells than cells");
+            if (n_work) {
+                Carve W;
+                const Seg w_q = W.seg(32 * n_work), w_r = W.seg(32 * n_work), w_a = W.seg((size_t)FLORIA_MAX_ALLELES * n_work), w_n = W.seg(n_work), w_b = W.seg(n_work),
+                          w_c = W.seg(8 * n_work);
+                ctx->batch_token = 0;                                   // misc is about to be overwritten: a resident S1 batch is gone (floria_hip_hap_graph checks the token)
+                if (int rc = W.place(ctx->misc)) return rc;
+                r.wq = W.at<uint8_t>(w_q); r.wr = W.at<uint8_t>(w_r); r.wal = W.at<uint8_t>(w_a); r.wna = W.at<uint8_t>(w_n); r.wcell = W.at<uint64_t>(w_c); r.cap = n_work;
+                fl::RealignArgs ra{};
+                ra.q = r.wq; ra.r = r.wr; ra.alleles = r.wal; ra.n_alleles = r.wna; ra.best = W.at<uint8_t>(w_b); ra.score = nullptr; ra.n = n_work;
+                t = T.begin(K_PILEUP);
+                hipLaunchKernelGGL(fl::realign_fill_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, r);
+                HIPCHK(hipGetLastError());
+                HIPCHK(walk ? launch_realign_walk(ctx, *walk, ra) : launch_realign(ctx, ra));
+                const uint32_t sgrid = (uint32_t)std::min<uint64_t>((n_work + 255) / 256, (uint64_t)ctx->n_cu * 8);
+                hipLaunchKernelGGL(fl::realign_scatter_kernel, dim3(sgrid), dim3(256), 0, ctx->stream, (const uint8_t*)ra.best, (const uint64_t*)r.wcell, n_work, r.allele, r.counts);
+                HIPCHK(hipGetLastError());
+                T.end(t);
+            }
+        }
         t = T.begin(K_D2H);
+        if (F && total && hc[fl::RG_SCORED]) HIPCHK(hipMemcpyAsync(hc, C.at<uint64_t>(s_cnt), sizeof hc, hipMemcpyDeviceToHost, ctx->stream));      // (the scatter's share of `changed`)
         if (total) {
             HIPCHK(hipMemcpyAsync(R->snp, a.snp, 4 * total, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(R->allele, a.allele, total, hipMemcpyDeviceToHost, ctx->stream));
@@ -2528,10 +2594,26 @@ int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, c
         HIPCHK(hipStreamSynchronize(ctx->stream));
         ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.total_ms = T.span();
         ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
+        if (F && total) {
+            if (hc[fl::RG_APPENDED] != hc[fl::RG_SCORED]) return fail(FLORIA_E_DEVICE, "realign: the work list holds another number of windows than were counted");
+            if (counts) { counts->in_bounds = hc[fl::RG_IN_BOUNDS]; counts->shortcut = hc[fl::RG_SHORTCUT]; counts->scored = hc[fl::RG_SCORED]; counts->changed = hc[fl::RG_CHANGED]; }
+        }
+        if (counts) counts->cells = total;
     }
     guard.r = nullptr;
     *out = R;
     return 0;
+}
+}  // namespace
+
+int floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, floria_record_cells** out) {
+    return pileup_records_impl(ctx, A, S, nullptr, nullptr, out, nullptr);
+}
+
+int floria_hip_pileup_records_realign(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F, const floria_realign_walk* walk,
+                                      floria_record_cells** out, floria_realign_counts* counts) {
+    if (!F) return fail(FLORIA_E_INVALID, "null argument");
+    return pileup_records_impl(ctx, A, S, F, walk, out, counts);
 }
 
 // ---- get_hapq (part_block_manip.rs:517-616) for the haplosets of many contigs (the reference calls it once per contig) ----------

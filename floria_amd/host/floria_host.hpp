@@ -68,6 +68,7 @@ struct Options {
     bool realign_walk = false;
     floria_realign_walk walk = {8, 8, 0, 0};
     bool pileup_device = false;         // --pileup host | device: frag_from_record's CIGAR walk on the host (default) or by floria_hip_pileup_records, one call per ingest round
+    bool pileup_fused = false;          // --pileup fused: pileup_device, and the calls are realigned by the same device call (floria_hip_pileup_records_realign) instead of by realign()
 };
 // "exact" | "block:STEP,RULE,TIE" (STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down) -> options.realign_walk / options.walk; anything else throws with the grammar
 void parse_realign_spec(const std::string& spec, Options& options);
@@ -308,7 +309,10 @@ struct RealignQueue {
 // site with more than FLORIA_MAX_ALLELES alleles is not sent: its records keep the host walk (host_contigs names them).
 class RecordPileup {
 public:
-    RecordPileup(Session& s, const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string* contigs, size_t n_contigs);
+    // ref_seqs (--pileup fused): the reference sequences by contig name; the call is then floria_hip_pileup_records_realign with options.realign_walk / walk, the cells come
+    // back realigned (a contig that is not in the map travels with an empty sequence: its cells stay as walked) and `realigned` tells ContigIngest to leave them alone
+    RecordPileup(Session& s, const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string* contigs, size_t n_contigs,
+                 const std::map<std::string, std::string>* ref_seqs = nullptr);
     ~RecordPileup();
     RecordPileup(const RecordPileup&) = delete;
     RecordPileup& operator=(const RecordPileup&) = delete;
@@ -317,6 +321,8 @@ public:
     size_t records_sent = 0, blob_bytes = 0;
     double kernel_ms = 0., h2d_ms = 0., d2h_ms = 0.;         // floria_hip_last_timing of the call
     std::vector<std::string> host_contigs;
+    bool realigned = false;
+    floria_realign_counts counts = {};                       // of the realigning call
 private:
     floria_record_cells* cells_ = nullptr;
     std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
@@ -324,7 +330,7 @@ private:
 class ContigIngest {
 public:
     // records of `contig` -> one Frag per passing alignment (file_reader.rs:343-430); with a queue the undecided realignments are deferred; with a RecordPileup the
-    // records it holds are not walked
+    // records it holds are not walked (and not realigned here when it holds realigned cells)
     ContigIngest(const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string& contig, const std::string* ref_seq, RealignQueue* queue,
                  const RecordPileup* device_cells = nullptr);
     ~ContigIngest();

@@ -924,7 +924,7 @@ ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Optio
         RecordPileup::Cells dc;
         const bool on_device = device_cells && device_cells->cells(rec_ix, dc);
         Frag fr = on_device ? frag_from_cells(rec, dc, this_count, o.output_reads) : frag_from_record(rec, snp_positions, pos_allele_map, this_count, o.output_reads);
-        if (ref_seq) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue, o.realign_walk ? &o.walk : nullptr);             // :416-423
+        if (ref_seq && !(on_device && device_cells->realigned)) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue, o.realign_walk ? &o.walk : nullptr);             // :416-423
         buckets[ins.first->second].push_back({rec.flags, std::move(fr)});
     }
 }
@@ -938,7 +938,8 @@ bool RecordPileup::cells(uint32_t rec_ix, Cells& out) const {
     out = {cells_->snp + b, cells_->allele + b, cells_->qual + b, cells_->seq_pos + b, (size_t)(e - b), cells_->ref_end[s - 1]};
     return true;
 }
-RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs) {
+RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
+                           const std::map<std::string, std::string>* ref_seqs) {
     const bool filter_supplementary = true, use_supplementary = !o.dont_use_supp_aln;
     // the SNP table of the round's contigs: positions in order, REF + ALT bytes; a contig the device's numbering (rank + 1) would not match stays on the host
     std::vector<uint64_t> snp_off{0};
@@ -948,6 +949,8 @@ RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfil
     std::vector<uint16_t> flags;
     std::vector<uint32_t> contig, n_cigar, l_seq, rec_of;
     std::vector<const unsigned char*> cig_p, seq_p, qual_p;
+    std::vector<uint64_t> ref_off{0};                                          // ref_seqs: the table's contigs' sequences back to back
+    std::vector<uint8_t> ref_bytes;
     for (size_t ci = 0; ci < n_contigs; ++ci) {
         const auto tid_it = std::find(bam.target_names.begin(), bam.target_names.end(), contigs[ci]);
         const auto counters = vp.vcf_pos_to_snp_counter_map.find(contigs[ci]);
@@ -967,6 +970,11 @@ RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfil
             n_alleles.push_back((uint8_t)kv.second.size());
         }
         snp_off.push_back(snp_pos.size());
+        if (ref_seqs) {
+            const auto fa = ref_seqs->find(contigs[ci]);
+            if (fa != ref_seqs->end()) ref_bytes.insert(ref_bytes.end(), fa->second.begin(), fa->second.end());
+            ref_off.push_back(ref_bytes.size());
+        }
         for (const uint32_t rec_ix : bam.by_tid[(size_t)(tid_it - bam.target_names.begin())]) {
             const BamRecord& rec = bam.records[rec_ix];
             if (!alignment_passed_check(rec.flags, rec.mapq, use_supplementary, filter_supplementary, o.mapq_cutoff).first) continue;
@@ -991,7 +999,13 @@ RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfil
     A.cigar_off = cigar_off.data(); A.n_cigar = n_cigar.data(); A.seq_off = seq_off.data(); A.l_seq = l_seq.data(); A.qual_off = qual_off.data();
     floria_snp_table S{};
     S.n_contigs = (uint32_t)snp_off.size() - 1; S.snp_off = snp_off.data(); S.snp_pos = snp_pos.data(); S.alleles = alleles.data(); S.n_alleles = n_alleles.data();
-    if (const int rc = floria_hip_pileup_records(session.ctx(), &A, &S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
+    if (ref_seqs) {
+        floria_ref_seqs F{};
+        F.n_contigs = S.n_contigs; F.seq_off = ref_off.data(); F.seq = ref_bytes.data();
+        if (const int rc = floria_hip_pileup_records_realign(session.ctx(), &A, &S, &F, o.realign_walk ? &o.walk : nullptr, &cells_, &counts))
+            throw Error(rc, std::string("floria_hip_pileup_records_realign: ") + floria_hip_last_error());
+        realigned = true;
+    } else if (const int rc = floria_hip_pileup_records(session.ctx(), &A, &S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
     floria_timing tm;
     if (floria_hip_last_timing(session.ctx(), &tm) == 0) { kernel_ms = tm.pileup_ms; h2d_ms = tm.h2d_ms; d2h_ms = tm.d2h_ms; }
     slot_.assign(bam.records.size(), 0);

@@ -17,6 +17,8 @@
 // --ingest-only, --no-realign, --stitch-graph FILE.
 // --pileup host | device: where the CIGAR walk that turns alignment records into SNP calls runs.  host [default]: frag_from_record on -t threads, one contig per task;
 // device: one floria_hip_pileup_records call per ingest round for every record that passes the alignment filter, the Frags filled from its cells (same files).
+// fused: device, with the realignment of the calls done by the same call (floria_hip_pileup_records_realign) before the cells come back; without realignment (--no-realign)
+// it is device.  Same files.
 // --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
 // RULE max | sum, TIE right | down): one member of the family of fixed-block walks (block 8) that scripts/probes/block_walk.c defines.  The reference's block-aligner is
 // some heuristic of this kind; which member, if any, is not known, so there is no bare `block`.  The run's log and cmd.log name the scoring used.
@@ -63,7 +65,8 @@ void usage() {
           "  --epsilon-round   round an ESTIMATED -e to a multiple of 2^-10 (there both arithmetics are the same function)\n"
           "  --lp-tie first|last, --lp-report   which optimal vertex of the stitching LP is used where the optimum is not unique, and how often that is\n"
           "  --no-realign      skip the re-alignment of the reads' bases around SNPs\n"
-          "  --pileup host|device   where alignment records become SNP calls (the CIGAR walk): on the host threads [default] or in one device call per ingest round; same files\n"
+          "  --pileup host|device|fused   where alignment records become SNP calls (the CIGAR walk): on the host threads [default] or in one device call per ingest round;\n"
+          "                    fused: that device call also re-aligns the calls (instead of the host loop that queues windows for the device); same files\n"
           "  --realign exact | block:STEP,RULE,TIE   how that re-alignment scores a window: exact [default] = the exact affine-gap alignment; block:... = a walk of a fixed\n"
           "                 8 x 8 block over the alignment matrix, shifted by STEP = 1 | 2 | 4 | 8 cells towards the larger border by RULE = max | sum, ties going\n"
           "                 TIE = right | down (e.g. block:8,max,right).  floria's block-aligner is a heuristic of this kind; which member is unknown, so one must be named\n"
@@ -213,8 +216,8 @@ int main(int argc, char** argv) {
             else if (a == "--realign") { parse_realign_spec(val(), o); have_realign = true; }
             else if (a == "--pileup") {
                 const std::string v = val();
-                if (v != "host" && v != "device") throw Error(FLORIA_E_INVALID, "--pileup takes host or device, not '" + v + "'");
-                o.pileup_device = v == "device";
+                if (v != "host" && v != "device" && v != "fused") throw Error(FLORIA_E_INVALID, "--pileup takes host or device (or fused: device, and the calls re-aligned there), not '" + v + "'");
+                o.pileup_device = v != "host"; o.pileup_fused = v == "fused";
             }
             else if (a == "--ingest-only") ingest_only = true;          // (tests) stop after ingest: needs no GPU
             else if (a == "--stitch-graph") stitch_graph = val();       // (tests) N / E lines of a hap graph -> F / P lines on stdout: needs no GPU
@@ -352,6 +355,8 @@ int main(int argc, char** argv) {
         size_t n_realign_device = 0, n_batches = 0, n_records = 0, n_segments = 0;
         size_t n_pileup_records = 0, n_pileup_bytes = 0, n_pileup_calls = 0;      // --pileup device
         double t_pileup = 0., t_pileup_kernels = 0., t_pileup_h2d = 0., t_pileup_d2h = 0.;
+        const bool fused = o.pileup_fused && !no_realign;                        // (--pileup fused --no-realign is --pileup device)
+        floria_realign_counts fused_counts = {};
         bool said_host_walk = false;
         // every contig that will be phased must be in the reference FASTA: said before anything is written, not when its batch comes up
         if (!ingest_only)
@@ -399,14 +404,16 @@ int main(int argc, char** argv) {
                 std::unique_ptr<RecordPileup> device_cells;                    // --pileup device: the round's CIGAR walks in one device call
                 if (o.pileup_device) {
                     const double tw = now_s();
-                    device_cells.reset(new RecordPileup(*session_holder, bam, vp, o, &todo[done], take));
+                    device_cells.reset(new RecordPileup(*session_holder, bam, vp, o, &todo[done], take, fused ? &fasta : nullptr));
                     t_pileup += now_s() - tw;
+                    fused_counts.cells += device_cells->counts.cells; fused_counts.in_bounds += device_cells->counts.in_bounds; fused_counts.shortcut += device_cells->counts.shortcut;
+                    fused_counts.scored += device_cells->counts.scored; fused_counts.changed += device_cells->counts.changed;
                     ++n_pileup_calls; n_pileup_records += device_cells->records_sent; n_pileup_bytes += device_cells->blob_bytes;
                     t_pileup_kernels += device_cells->kernel_ms * 1e-3; t_pileup_h2d += device_cells->h2d_ms * 1e-3; t_pileup_d2h += device_cells->d2h_ms * 1e-3;
                     if (!device_cells->host_contigs.empty() && !said_host_walk) {
                         said_host_walk = true;
-                        fprintf(stderr, "floria-hip: --pileup device: contig %s keeps the host walk (its SNP numbers are not their rank in position order, or a site has more than %d alleles); "
-                                        "this is said once\n", device_cells->host_contigs[0].c_str(), FLORIA_MAX_ALLELES);
+                        fprintf(stderr, "floria-hip: --pileup %s: contig %s keeps the host walk (its SNP numbers are not their rank in position order, or a site has more than %d alleles); "
+                                        "this is said once\n", o.pileup_fused ? "fused" : "device", device_cells->host_contigs[0].c_str(), FLORIA_MAX_ALLELES);
                     }
                 }
                 parallel_for(take, n_threads, [&](size_t i) {
@@ -534,8 +541,13 @@ int main(int argc, char** argv) {
         }
         }       // (next segment of the BAM)
         fprintf(stderr, "BAM: %zu records in %zu segments, %.3fs of inflate + decode, largest inflated buffer %zu MiB\n", n_records, n_segments, t_stream, stream.peak_buffer_bytes() >> 20);
+        if (!fused || n_realign_device)                                           // (fused: only the contigs that kept the host walk queue windows)
         fprintf(stderr, "Realignment: %zu calls scored on the device in %.3fs (inside the ingest time), scoring %s\n", n_realign_device, t_realign,
                 o.realign_walk ? ("fixed-block walk " + realign_spec(o)).c_str() : "exact affine-gap DP");
+        if (fused)
+            fprintf(stderr, "Realignment: %llu calls scored on the device behind the walk (%llu by the exact shortcut, %llu outside the window bounds), scoring %s\n",
+                    (unsigned long long)fused_counts.scored, (unsigned long long)fused_counts.shortcut, (unsigned long long)(fused_counts.cells - fused_counts.in_bounds),
+                    o.realign_walk ? ("fixed-block walk " + realign_spec(o)).c_str() : "exact affine-gap DP");
         if (o.pileup_device)
             fprintf(stderr, "Pileup on the device: %zu records, %zu blob bytes in %zu calls, %.3fs (inside the ingest time; device events: upload %.3fs, kernels %.3fs, download %.3fs)\n",
                     n_pileup_records, n_pileup_bytes, n_pileup_calls, t_pileup, t_pileup_h2d, t_pileup_kernels, t_pileup_d2h);

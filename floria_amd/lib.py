@@ -28,7 +28,7 @@ SYMBOLS = [
     "floria_hip_hapq", "floria_hip_hapq_batch",
     "floria_hip_contig_upload_batch", "floria_hip_host_alloc", "floria_hip_host_free", "floria_hip_set_option",
     "floria_hip_contig_download", "floria_hip_phase_pileups_batch",
-    "floria_hip_pileup_records", "floria_hip_record_cells_free",
+    "floria_hip_pileup_records", "floria_hip_record_cells_free", "floria_hip_pileup_records_realign",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -78,6 +78,8 @@ def load():
         L.floria_hip_pack_pileup.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.floria_hip_pileup_records.argtypes = [C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(C.POINTER(capi.CRecordCells))]
         L.floria_hip_record_cells_free.argtypes = [C.POINTER(capi.CRecordCells)]
+        L.floria_hip_pileup_records_realign.argtypes = [C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(capi.CRefSeqs), C.POINTER(capi.CRealignWalk),
+                                                        C.POINTER(C.POINTER(capi.CRecordCells)), C.POINTER(capi.CRealignCounts)]
         _LIB = L
     return _LIB
 
@@ -446,6 +448,15 @@ class FloriaHip:
         (pos int32 [n], flags uint16 [n], contig uint32 [n], cigar_off / seq_off / qual_off uint64 [n], n_cigar / l_seq uint32 [n]) against a SNP table
         (snp_off uint64 [n_contigs + 1], snp_pos int64, alleles uint8 [n_snps, 4], n_alleles uint8) -> numpy arrays
         (cell_off uint64 [n + 1], snp uint32, allele uint8, qual uint8, seq_pos uint32, ref_end int64 [n]).  Arrays that live in a PinnedArena go up by DMA."""
+        return self._pileup_records(blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles)
+
+    def pileup_records_realign(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, ref_off, ref_seq, walk=None):
+        """floria_hip_pileup_records_realign: pileup_records() with alignment::realign applied to the cells on the device.  ref_off uint64 [n_contigs + 1] and ref_seq
+        uint8 (or bytes) hold one reference sequence per contig of the SNP table (an empty one: the contig's cells stay as walked; ref_seq None: a null pointer); walk None = the exact DP, or
+        (step, rule, tie) / (block, step, rule, tie) as realign_walk() takes them.  -> (the six arrays of pileup_records, dict(cells, in_bounds, shortcut, scored, changed))."""
+        return self._pileup_records(blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=(ref_off, ref_seq), walk=walk)
+
+    def _pileup_records(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=None, walk=None):
         def arr(a, dt):
             return a if isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous else np.ascontiguousarray(a, dt)
         keep = [arr(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8), arr(pos, np.int32), arr(flags, np.uint16),
@@ -461,7 +472,23 @@ class FloriaHip:
                              capi.ptr(ncg, C.c_uint32), capi.ptr(so, C.c_uint64), capi.ptr(ls, C.c_uint32), capi.ptr(qo, C.c_uint64))
         S = capi.CSnpTable(len(soff) - 1, capi.ptr(soff, C.c_uint64), capi.ptr(sp, C.c_int64), capi.ptr(al, C.c_uint8), capi.ptr(na, C.c_uint8))
         out = C.POINTER(capi.CRecordCells)()
-        _check(load().floria_hip_pileup_records(self._h, C.byref(A), C.byref(S), C.byref(out)))
+        counts = None
+        if refs is None:
+            _check(load().floria_hip_pileup_records(self._h, C.byref(A), C.byref(S), C.byref(out)))
+        else:
+            roff = arr(refs[0], np.uint64)
+            rseq = arr(np.frombuffer(refs[1], np.uint8) if isinstance(refs[1], (bytes, bytearray, memoryview)) else (refs[1] if refs[1] is not None else []), np.uint8)
+            keep += [roff, rseq]
+            if len(roff) < 1 or (refs[1] is not None and int(roff.max()) > rseq.size):
+                raise FloriaHipError(capi.FLORIA_E_INVALID, "pileup_records_realign: ref_off needs n_contigs + 1 entries, the last at most len(ref_seq)")
+            F = capi.CRefSeqs(len(roff) - 1, capi.ptr(roff, C.c_uint64), capi.ptr(rseq, C.c_uint8) if rseq.size else None)
+            w = None
+            if walk is not None:
+                block, step, rule, tie = walk if len(walk) == 4 else (8,) + tuple(walk)
+                w = capi.CRealignWalk(int(block), int(step), {"max": 0, "sum": 1}.get(rule, rule), {"right": 0, "down": 1}.get(tie, tie))
+            cc = capi.CRealignCounts()
+            _check(load().floria_hip_pileup_records_realign(self._h, C.byref(A), C.byref(S), C.byref(F), C.byref(w) if w is not None else None, C.byref(out), C.byref(cc)))
+            counts = dict(cells=int(cc.cells), in_bounds=int(cc.in_bounds), shortcut=int(cc.shortcut), scored=int(cc.scored), changed=int(cc.changed))
         r = out.contents
         cell_off = capi.np_from(r.cell_off, n + 1, np.uint64)
         t = int(cell_off[n])
@@ -469,7 +496,7 @@ class FloriaHip:
                capi.np_from(r.seq_pos, t, np.uint32), capi.np_from(r.ref_end, n, np.int64))
         load().floria_hip_record_cells_free(out)
         del keep
-        return res
+        return res if refs is None else (res, counts)
 
     def hapq_batch(self, contigs, grp_contig, groups, ranges, snp_positions, block_length):
         """get_hapq for the haplosets of many contigs in one call -> (hapq uint8 [n], rel_err float64 [n], avg_err float64 [n_contigs])."""

@@ -389,6 +389,26 @@ typedef struct {               /* library-owned; record i owns cells [cell_off[i
 int  floria_hip_pileup_records(floria_hip_ctx* ctx, const floria_alignments* alignments, const floria_snp_table* snps, floria_record_cells** out);
 void floria_hip_record_cells_free(floria_record_cells* cells);
 
+/* ---- the same walk with alignment::realign (alignment.rs:7-64) applied to its cells before they leave the device ----------------------------------------------
+ * refs: one reference sequence per contig of the SNP table (contig c owns seq[seq_off[c] .. seq_off[c+1]); an empty one = the contig has no reference and none of
+ * its cells is realigned).  Every field of the result equals floria_hip_pileup_records' except `allele`.  For a cell of record i with SNP index k, G = snp_pos[k],
+ * p = the emitted seq_pos (hard-clip shift included, widened to 64 bits), L = l_seq[i] and R = the length of the contig's sequence:
+ *   - the allele stays as walked unless 16 <= G, G + 16 < R, 16 <= p and p + 16 < L (compared in 64 bits);
+ *   - q[j], j = 0..31, is the base of record i at index p - 16 + j (decoded with "=ACMGRSVTWYHKDBN"; anything but A, C, G, T becomes A), r[j] the upper-cased
+ *     reference byte at G - 16 + j, al[m] = alleles[4k + m] upper-cased for m < n_alleles[k]; h = the number of columns j != 16 with q[j] != r[j];
+ *   - h <= 2 and some al[m] == q[16]: the first such m; else h <= 1: 0; otherwise the first m with the maximal score of q against r with al[m] in column 16,
+ *     scored as floria_hip_realign does (walk == NULL) or as floria_hip_realign_walk does for that member (anything else is FLORIA_E_INVALID).
+ * counts (may be NULL): cells = all cells, in_bounds = those the bounds let through, shortcut / scored = how they were decided (in_bounds = shortcut + scored),
+ * changed = cells whose allele differs from the walked one.
+ * Validated on the host before any launch, beyond what floria_hip_pileup_records checks: refs->n_contigs == snps->n_contigs, non-decreasing seq_off, a non-null seq
+ * when any contig is non-empty, the walk member.  The reference bytes go up with the other inputs; the gather, scoring and scatter kernels
+ * (csrc/realign_gather_kernel.h) count into pileup_ms.  The call may reuse the buffer that holds the last phase_blocks* batch: like floria_hip_realign it ends that batch's
+ * residency (floria_hip_hap_graph then returns FLORIA_E_INVALID for it); floria_hip_pileup_records does not. */
+typedef struct { uint32_t n_contigs; const uint64_t* seq_off; /* [n_contigs+1] */ const uint8_t* seq; } floria_ref_seqs;
+typedef struct { uint64_t cells, in_bounds, shortcut, scored, changed; } floria_realign_counts;
+int  floria_hip_pileup_records_realign(floria_hip_ctx* ctx, const floria_alignments* alignments, const floria_snp_table* snps, const floria_ref_seqs* refs,
+                                       const floria_realign_walk* walk /* NULL = exact DP */, floria_record_cells** out, floria_realign_counts* counts /* may be NULL */);
+
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
 /* Self-test of a hardware assumption: the beam kernel screens the pruning test (global_clustering.rs:98) with an f32 evaluation of stable_binom_cdf_p_rev

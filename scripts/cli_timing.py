@@ -3,8 +3,8 @@
     python scripts/cli_timing.py [--contigs 60] [--scale 0.5] [--threads 16] [--sub-rate 0.12] [--realign exact|block:STEP,RULE,TIE ...] [--exe PATH] [--only batched]
 
 --realign (repeatable, needs --only or takes the batched run): the batched run once per scoring, in the order given, e.g. --realign exact --realign block:8,max,right
---pileup-compare N [--threads-list 16,1]: only the batched flow, --pileup host and --pileup device ALTERNATING, N runs each per thread count, then the median and the
-spread (min .. max) of the ingest time and of the wall time per route (profiles/pileup_device.md).
+--pileup-compare N [--threads-list 16,1]: only the batched flow, --pileup host, --pileup device and --pileup fused ALTERNATING, N runs each per thread count, then the
+median and the spread (min .. max) of the ingest time and of the wall time per route (profiles/pileup_device.md, profiles/pileup_fused.md).
 --realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
 
 Writes BAM / VCF / FASTA under $TMPDIR, runs the driver twice and prints its stage-time lines (stderr of floria-hip)."""
@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--exe", default=None, help="floria-hip binary to time (default: this tree's, built first)")
     ap.add_argument("--only", default=None, help="only the runs whose label contains this text")
     ap.add_argument("--arith-compare", action="store_true", help="only: the batched flow at -e 0.04 with --arith canonical against --arith reference (the default there)")
-    ap.add_argument("--pileup-compare", type=int, default=0, help="only: the batched flow with --pileup host and --pileup device alternating, this many runs each")
+    ap.add_argument("--pileup-compare", type=int, default=0, help="only: the batched flow with --pileup host, device and fused alternating, this many runs each")
     ap.add_argument("--threads-list", default=None, help="with --pileup-compare: comma-separated -t values (default: --threads)")
     a = ap.parse_args()
     if a.exe is None:
@@ -55,7 +55,7 @@ def main():
         runs = tuple((f"batched, --realign {spec}" + (" (again)" if spec in a.realign[:k] else ""), ["-t", str(a.threads), "--realign", spec]) for k, spec in enumerate(a.realign))
     if a.pileup_compare:
         threads = [int(x) for x in a.threads_list.split(",")] if a.threads_list else [a.threads]
-        runs = tuple((f"-t {t}, --pileup {route}, run {k + 1}", ["-t", str(t), "--pileup", route]) for t in threads for k in range(a.pileup_compare) for route in ("host", "device"))
+        runs = tuple((f"-t {t}, --pileup {route}, run {k + 1}", ["-t", str(t), "--pileup", route]) for t in threads for k in range(a.pileup_compare) for route in ("host", "device", "fused"))
     if a.only:
         runs = tuple(r for r in runs if a.only in r[0])
     stats = {}
