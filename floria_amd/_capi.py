@@ -94,6 +94,14 @@ class CRealignCounts(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("in_bounds", C.c_uint64), ("shortcut", C.c_uint64), ("scored", C.c_uint64), ("changed", C.c_uint64)]
 
 
+class CRecordSummary(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("cell_off", u64p), ("first_snp", u32p), ("last_snp", u32p), ("ref_end", i64p), ("counts", CRealignCounts), ("token", C.c_uint64)]
+
+
+class CFragmentPlan(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint32), ("frag_off", u64p), ("part_off", u64p), ("part_rec", u32p), ("set_order", u32p)]
+
+
 def ptr(a, ctype):
     """Pointer to a C-contiguous numpy array (the array must outlive the call)."""
     return a.ctypes.data_as(C.POINTER(ctype))

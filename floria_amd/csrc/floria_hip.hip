@@ -44,6 +44,7 @@
 #include "pileup_kernel.h"
 #include "realign_gather_kernel.h"
 #include "upload_kernel.h"
+#include "assemble_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -247,6 +248,13 @@ struct floria_hip_ctx {
     std::vector<Arena*> arena_cache;          // released batch arenas, reused by the next upload
     StagePool stage;                          // pinned staging ring for pageable sources
     DevBuf pile_in, pile_out;                 // floria_hip_pileup_records: blob + record arrays + SNP table + offsets, and the cell arrays
+    // the cells of the last floria_hip_pileup_records_resident call, still in pile_in / pile_out (floria_hip_assemble_contigs); res_token 0 = none
+    uint64_t res_token = 0;
+    const floria_record_summary* res_summary = nullptr;
+    uint32_t res_n_contigs = 0;
+    std::vector<uint32_t> res_contig;         // contig of every record (header-sized; the plan is validated against it)
+    const uint64_t* res_cell_off = nullptr; const uint32_t* res_snp = nullptr; const uint8_t *res_allele = nullptr, *res_qual = nullptr;
+    DevBuf asm_plan;                          // floria_hip_assemble_contigs: the fragment plan and the per-fragment cell counts / offsets
     uint32_t stage_threads = 8;
 };
 
@@ -972,7 +980,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -2465,10 +2473,13 @@ namespace {
 // The body of floria_hip_pileup_records and floria_hip_pileup_records_realign: upload, COUNT, offset scan, FILL, download.  With reference sequences (F) the cells'
 // alleles are realigned on the device between FILL and the download (realign_gather_kernel.h): DECIDE, one read of its counters, then — when anything is left
 // undecided — FILL of the work list, the scoring kernel (walk == null: the exact DP) and the scatter.  Without F nothing of that is allocated, uploaded or launched.
+// `resident` (floria_hip_pileup_records_resident): the cell arrays stay where FILL put them; only the per-record arrays come back, with the SNP of every record's
+// first / last cell (record_span_kernel) in the places of R->snp / R->seq_pos ([n] instead of [cells]).
 int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F, const floria_realign_walk* walk,
-                        floria_record_cells** out, floria_realign_counts* counts) {
+                        floria_record_cells** out, floria_realign_counts* counts, bool resident = false) {
     if (!ctx || !A || !S || !out) return fail(FLORIA_E_INVALID, "null argument");
     *out = nullptr;
+    ctx->res_token = 0; ctx->res_summary = nullptr;      // pile_in / pile_out are about to be rewritten: a residency ends here
     if (counts) *counts = floria_realign_counts{};
     if (int rc = pileup_validate(A, S)) return rc;
     if (F) { if (int rc = refs_validate(F, S)) return rc; }
@@ -2484,7 +2495,8 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
     if (!R->cell_off || !R->ref_end) return fail(FLORIA_E_NOMEM, "malloc");
     R->cell_off[0] = 0;
     uint64_t total = 0;
-    const auto alloc_cells = [R](uint64_t t) {
+    const auto alloc_cells = [R, resident, n](uint64_t t) {
+        if (resident) { R->snp = (uint32_t*)cells_bytes(4ull * n); R->seq_pos = (uint32_t*)cells_bytes(4ull * n); return R->snp && R->seq_pos ? 0 : fail(FLORIA_E_NOMEM, "malloc"); }
         R->snp = (uint32_t*)cells_bytes(4 * t); R->allele = (uint8_t*)cells_bytes(t); R->qual = (uint8_t*)cells_bytes(t); R->seq_pos = (uint32_t*)cells_bytes(4 * t);
         return R->snp && R->allele && R->qual && R->seq_pos ? 0 : fail(FLORIA_E_NOMEM, "malloc");
     };
@@ -2498,6 +2510,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
         const Seg s_blob = C.seg(A->blob_bytes), s_pos = C.seg(4ull * n), s_flag = C.seg(2ull * n), s_ctg = C.seg(4ull * n), s_co = C.seg(8ull * n), s_nc = C.seg(4ull * n),
                   s_so = C.seg(8ull * n), s_ls = C.seg(4ull * n), s_qo = C.seg(8ull * n), s_soff = C.seg(8ull * (nc + 1)), s_sp = C.seg(8 * n_snps), s_al = C.seg(4 * n_snps),
                   s_na = C.seg(n_snps), s_off = C.seg(8ull * ((uint64_t)n + 1)), s_tile = C.seg(8ull * n_tiles), s_re = C.seg(8ull * n);
+        const Seg s_f1 = C.seg(resident ? 4ull * n : 0), s_l1 = C.seg(resident ? 4ull * n : 0);
         const uint64_t ref_b = F ? F->seq_off[0] : 0, ref_bytes = F ? F->seq_off[nc] - ref_b : 0;
         const Seg s_roff = C.seg(F ? 8ull * (nc + 1) : 0), s_ref = C.seg(ref_bytes), s_cnt = C.seg(F ? 8ull * fl::RG_N_COUNTS : 0);
         if (int rc = C.place(ctx->pile_in)) return rc;
@@ -2581,9 +2594,18 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
                 T.end(t);
             }
         }
+        if (resident) {
+            t = T.begin(K_PILEUP);
+            hipLaunchKernelGGL(fl::record_span_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint64_t*)a.cell_off, (const uint32_t*)a.snp, C.at<uint32_t>(s_f1), C.at<uint32_t>(s_l1), n);
+            HIPCHK(hipGetLastError());
+            T.end(t);
+        }
         t = T.begin(K_D2H);
         if (F && total && hc[fl::RG_SCORED]) HIPCHK(hipMemcpyAsync(hc, C.at<uint64_t>(s_cnt), sizeof hc, hipMemcpyDeviceToHost, ctx->stream));      // (the scatter's share of `changed`)
-        if (total) {
+        if (resident) {
+            HIPCHK(hipMemcpyAsync(R->snp, C.at(s_f1), 4ull * n, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(R->seq_pos, C.at(s_l1), 4ull * n, hipMemcpyDeviceToHost, ctx->stream));
+        } else if (total) {
             HIPCHK(hipMemcpyAsync(R->snp, a.snp, 4 * total, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(R->allele, a.allele, total, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(R->qual, a.qual, total, hipMemcpyDeviceToHost, ctx->stream));
@@ -2599,7 +2621,12 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
             if (counts) { counts->in_bounds = hc[fl::RG_IN_BOUNDS]; counts->shortcut = hc[fl::RG_SHORTCUT]; counts->scored = hc[fl::RG_SCORED]; counts->changed = hc[fl::RG_CHANGED]; }
         }
         if (counts) counts->cells = total;
+        if (resident) {
+            ctx->res_contig.assign(A->contig, A->contig + n); ctx->res_n_contigs = nc;
+            ctx->res_cell_off = a.cell_off; ctx->res_snp = a.snp; ctx->res_allele = a.allele; ctx->res_qual = a.qual;
+        }
     }
+    if (resident && n == 0) { ctx->res_contig.clear(); ctx->res_n_contigs = nc; ctx->res_cell_off = nullptr; ctx->res_snp = nullptr; ctx->res_allele = nullptr; ctx->res_qual = nullptr; }
     guard.r = nullptr;
     *out = R;
     return 0;
@@ -2614,6 +2641,224 @@ int floria_hip_pileup_records_realign(floria_hip_ctx* ctx, const floria_alignmen
                                       floria_record_cells** out, floria_realign_counts* counts) {
     if (!F) return fail(FLORIA_E_INVALID, "null argument");
     return pileup_records_impl(ctx, A, S, F, walk, out, counts);
+}
+
+// ---- records -> cells -> resident contigs (assemble_kernel.h) ------------------------------------------------------------------------------------------------
+int floria_hip_pileup_records_resident(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F, const floria_realign_walk* walk,
+                                       floria_record_summary** out) {
+    if (!out) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    floria_record_summary* Y = (floria_record_summary*)calloc(1, sizeof(floria_record_summary));
+    if (!Y) return fail(FLORIA_E_NOMEM, "calloc");
+    floria_record_cells* R = nullptr;
+    if (int rc = pileup_records_impl(ctx, A, S, F, walk, &R, &Y->counts, true)) { free(Y); return rc; }
+    // (the impl leaves the records' first / last SNPs in the [n] arrays it allocated for R->snp / R->seq_pos; allele and qual were never allocated)
+    Y->n_records = R->n_records; Y->cell_off = R->cell_off; Y->first_snp = R->snp; Y->last_snp = R->seq_pos; Y->ref_end = R->ref_end;
+    free(R);
+    Y->token = ++ctx->token_counter;
+    ctx->res_token = Y->token; ctx->res_summary = Y;
+    *out = Y;
+    return 0;
+}
+
+void floria_hip_record_summary_free(floria_record_summary* s) {
+    if (!s) return;
+    g_big.put(s->cell_off); g_big.put(s->first_snp); g_big.put(s->last_snp); g_big.put(s->ref_end); free(s);
+}
+
+int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out) {
+    if (!ctx || !Y || !plan || !out || !plan->frag_off) return fail(FLORIA_E_INVALID, "null argument");
+    const uint32_t nc = plan->n_contigs;
+    for (uint32_t c = 0; c < nc; ++c) out[c] = nullptr;
+    if (!ctx->res_token || Y != ctx->res_summary || Y->token != ctx->res_token)
+        return fail(FLORIA_E_INVALID, "assemble: the record summary is not the context's live residency (a later floria_hip_pileup_records* call has replaced its cells)");
+    if (nc != ctx->res_n_contigs) return fail(FLORIA_E_INVALID, "assemble: the plan has " + std::to_string(nc) + " contigs, the resident pileup's SNP table has " + std::to_string(ctx->res_n_contigs));
+    if (nc == 0) return 0;
+    // ---- everything the host can check from the summary, before anything is launched ----
+    const uint32_t n_rec = Y->n_records;
+    if (plan->frag_off[0] != 0) return fail(FLORIA_E_INVALID, "assemble: frag_off does not start at 0");
+    for (uint32_t c = 0; c < nc; ++c) {
+        if (plan->frag_off[c + 1] < plan->frag_off[c]) return fail(FLORIA_E_INVALID, "assemble: frag_off decreases at contig " + std::to_string(c));
+        if (plan->frag_off[c + 1] - plan->frag_off[c] >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "more than 2^32 fragments in one contig");
+    }
+    const uint64_t NF = plan->frag_off[nc];
+    if (NF >= (1ull << 32) - fl::PILEUP_SCAN_TILE) return fail(FLORIA_E_UNSUPPORTED, "assemble: 2^32 and more fragments in one call");
+    if (NF && (!plan->part_off || !plan->part_rec)) return fail(FLORIA_E_INVALID, "null argument");
+    if (NF && plan->part_off[0] != 0) return fail(FLORIA_E_INVALID, "assemble: part_off does not start at 0");
+    std::vector<uint32_t> frag_ctg((size_t)NF);
+    for (uint32_t c = 0; c < nc; ++c)
+        for (uint64_t f = plan->frag_off[c]; f < plan->frag_off[c + 1]; ++f) {
+            frag_ctg[f] = c;
+            const uint64_t p0 = plan->part_off[f], p1 = plan->part_off[f + 1];
+            const auto where = [&]() { return "fragment " + std::to_string((unsigned long long)(f - plan->frag_off[c])) + " of contig " + std::to_string(c); };
+            if (p1 < p0) return fail(FLORIA_E_INVALID, "assemble: part_off decreases at " + where());
+            if (p1 == p0) return fail(FLORIA_E_INVALID, "assemble: " + where() + " has no part");
+            bool any = false;
+            for (uint64_t p = p0; p < p1; ++p) {
+                const uint32_t rec = plan->part_rec[p];
+                if (rec >= n_rec) return fail(FLORIA_E_INVALID, "assemble: " + where() + " names record " + std::to_string(rec) + " of " + std::to_string(n_rec));
+                if (ctx->res_contig[rec] != c) return fail(FLORIA_E_INVALID, "assemble: record " + std::to_string(rec) + " lies on contig " + std::to_string(ctx->res_contig[rec]) + ", " + where() + " does not");
+                any = any || Y->cell_off[rec + 1] > Y->cell_off[rec];
+            }
+            if (!any) return fail(FLORIA_E_INVALID, "assemble: the parts of " + where() + " have no cell (every read has >= 1 cell)");
+        }
+    const uint64_t NP = NF ? plan->part_off[NF] : 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t n = nc, nf32 = (uint32_t)NF;
+    const uint32_t n_tiles = (nf32 + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+    // ---- the plan goes up; COUNT, offset scan, the per-contig cell totals come back (the only round trip: the arena is sized from them) ----
+    Carve C;
+    const Seg s_po = C.seg(8 * (NF + 1)), s_pr = C.seg(4 * NP + 4), s_fc = C.seg(4 * NF + 4), s_fo = C.seg(8ull * (n + 1)), s_cnt = C.seg(8 * (NF + 1)), s_tile = C.seg(8ull * n_tiles + 8),
+              s_tot = C.seg(8ull * (n + 1)), s_cdev = C.seg(sizeof(fl::ContigDev) * n);
+    if (int rc = C.place(ctx->asm_plan)) return rc;
+    EventTimer T(ctx->stream);
+    ctx->timing = floria_timing{};
+    fl::AssembleArgs a{};
+    a.cell_off = ctx->res_cell_off; a.snp = ctx->res_snp; a.allele = ctx->res_allele; a.qual = ctx->res_qual;
+    a.part_off = C.at<const uint64_t>(s_po); a.part_rec = C.at<const uint32_t>(s_pr); a.frag_ctg = C.at<const uint32_t>(s_fc); a.frag_off = C.at<const uint64_t>(s_fo);
+    a.frag_cells = C.at<uint64_t>(s_cnt); a.n_frags = NF;
+    std::vector<uint64_t> cp(n + 1, 0);
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((NF + 3) / 4, (uint64_t)ctx->n_cu * 8));      // one wavefront per fragment, grid-stride beyond 8 workgroups per CU
+    int t = T.begin(K_H2D);
+    if (NF) { HIPCHK(C.up(s_po, plan->part_off, 8 * (NF + 1), ctx->stream)); HIPCHK(C.up(s_pr, plan->part_rec, 4 * NP, ctx->stream)); HIPCHK(C.up(s_fc, frag_ctg.data(), 4 * NF, ctx->stream)); }
+    HIPCHK(C.up(s_fo, plan->frag_off, 8ull * (n + 1), ctx->stream));
+    T.end(t);
+    if (NF) {
+        t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::assemble_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(fl::pileup_scan_tiles_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, a.frag_cells, C.at<uint64_t>(s_tile), nf32);
+        hipLaunchKernelGGL(fl::pileup_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, C.at<uint64_t>(s_tile), n_tiles, a.frag_cells + NF);
+        hipLaunchKernelGGL(fl::pileup_scan_add_kernel, dim3((nf32 + 255) / 256), dim3(256), 0, ctx->stream, a.frag_cells, C.at<const uint64_t>(s_tile), nf32);
+        hipLaunchKernelGGL(fl::assemble_totals_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, (const uint64_t*)a.frag_cells, a.frag_off, C.at<uint64_t>(s_tot), n + 1);
+        HIPCHK(hipGetLastError());
+        T.end(t);
+        t = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(cp.data(), C.at(s_tot), 8ull * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (cp[i + 1] < cp[i]) return fail(FLORIA_E_DEVICE, "assemble: the cell offsets do not ascend");
+        if (cp[i + 1] - cp[i] >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "more than 2^32 cells in one contig");
+    }
+    // ---- the arena, laid out as plan_upload lays out a CSR batch of these sizes ----
+    UploadPlan P;
+    P.n = n; P.n_chunks = 1; P.packed = false;
+    ctx->upload_epoch++;
+    P.rp.assign(n + 1, 0); P.cp = cp;
+    for (uint32_t i = 0; i < n; ++i) P.rp[i + 1] = plan->frag_off[i + 1];
+    const uint64_t R = P.R = NF, CC = P.C = cp[n];
+    P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
+    const bool any_so = plan->set_order != nullptr && CC != 0;
+    size_t cursor = 0;
+    auto seg = [&](size_t bytes) { const size_t o = cursor; cursor += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_ro = seg(4 * (R + n)), o_first = seg(4 * R), o_last = seg(4 * R), o_snp = seg(4 * CC + 16), o_aw = seg(4 * CC + 16), o_tw = seg(16 * R), o_meta = seg(32 * R);
+    const size_t o_so = any_so ? seg(4 * CC + 16) : 0;
+    Arena* AR = P.A = arena_get(ctx, cursor + 256);
+    if (!AR) return FLORIA_E_NOMEM;
+    AR->n_contigs = n; AR->R = R; AR->C = CC; AR->off_ro = o_ro; AR->off_first = o_first; AR->off_last = o_last; AR->read_prefix = P.rp; AR->host_meta = false;
+    char* D = P.D = AR->buf.as<char>();
+    size_t c2 = 0;
+    auto seg2 = [&](size_t bytes) { const size_t o = c2; c2 += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t t_al = seg2(CC + 16), t_q = seg2(CC + 16);
+    P.t_cd = seg2(sizeof(fl::UploadContig) * n); P.t_rp = seg2(8ull * (n + 1)); P.t_st = seg2(sizeof(fl::UploadStatus) * n);
+    const auto drop = [&](int rc) { sync_all(ctx); arena_put(AR); return rc; };
+    if (int rc = ctx->up_tmp.ensure(c2 + 256)) return drop(rc);
+    char* TT = P.T = ctx->up_tmp.as<char>();
+    P.ucd.resize(n); P.ust.resize(n); P.so_dev.assign(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        fl::UploadContig& u = P.ucd[i];
+        u.read_off = (const uint32_t*)(D + o_ro + 4 * (P.rp[i] + i)); u.first = (const uint32_t*)(D + o_first + 4 * P.rp[i]); u.last = (const uint32_t*)(D + o_last + 4 * P.rp[i]);
+        u.snp = (const uint32_t*)(D + o_snp + 4 * cp[i]); u.allele = (const uint8_t*)(TT + t_al + cp[i]); u.qual = (const uint8_t*)(TT + t_q + cp[i]);
+        u.cell_aw = (uint32_t*)(D + o_aw + 4 * cp[i]); u.tw = (uint64_t*)(D + o_tw + 16 * P.rp[i]); u.meta = (uint32_t*)(D + o_meta + 32 * P.rp[i]);
+        u.n_reads = (uint32_t)(P.rp[i + 1] - P.rp[i]); u.n_cells = (uint32_t)(cp[i + 1] - cp[i]);
+        P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
+        if (any_so && u.n_reads) P.so_dev[i] = (const uint32_t*)(D + o_so + 4 * cp[i]);
+    }
+    // ---- FILL writes the raw CSR arrays where an upload's DMA would have put them; then the upload's own validate + flatten launch ----
+    a.read_off = (uint32_t*)(D + o_ro); a.first = (uint32_t*)(D + o_first); a.last = (uint32_t*)(D + o_last);
+    a.out_snp = (uint32_t*)(D + o_snp); a.out_allele = (uint8_t*)(TT + t_al); a.out_qual = (uint8_t*)(TT + t_q);
+    uint64_t pinned_b = 0, staged_b = 0;
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    t = T.begin(K_H2D);
+    if (any_so) { std::vector<CopyRun> runs{{(const char*)plan->set_order, D + o_so, (size_t)(4 * CC)}}; rc = issue_copies(ctx, runs, &pinned_b, &staged_b); }
+    if (!rc) e = issue_tables(ctx, P, ctx->stream);
+    T.end(t);
+    if (!rc && e == hipSuccess && NF) {
+        t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::assemble_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        e = hipGetLastError();
+        T.end(t);
+    }
+    if (!rc && e == hipSuccess) { const int tk = T.begin(K_SEL); e = launch_flatten(ctx, P, 0, ctx->stream); T.end(tk); }
+    if (!rc && e == hipSuccess) { t = T.begin(K_D2H); e = hipMemcpyAsync(P.ust.data(), TT + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream); T.end(t); }
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (!rc && e != hipSuccess) rc = fail(FLORIA_E_DEVICE, std::string("assemble: ") + hipGetErrorString(e));
+    if (!rc) rc = finish_upload(ctx, P, out);
+    if (rc) { for (uint32_t c = 0; c < nc; ++c) out[c] = nullptr; return drop(rc); }
+    if (any_so) {                                          // the cell orders of the batch, now: a set_order that is no permutation is refused here, and "arith" = 1 reuses them
+        std::vector<fl::ContigDev> cdev(n); std::vector<uint64_t> ncells(n); uint32_t len_max = 1;
+        for (uint32_t i = 0; i < n; ++i) { cdev[i] = out[i]->dev; ncells[i] = out[i]->n_cells; len_max = std::max(len_max, out[i]->max_len); }
+        e = hipMemcpyAsync(C.at(s_cdev), cdev.data(), sizeof(fl::ContigDev) * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        rc = e != hipSuccess ? fail(FLORIA_E_DEVICE, std::string("assemble: ") + hipGetErrorString(e)) : cell_orders(ctx, C.at<const fl::ContigDev>(s_cdev), cdev, ncells, len_max);
+        if (rc) { sync_all(ctx); for (uint32_t c = 0; c < nc; ++c) { floria_hip_contig_free(out[c]); out[c] = nullptr; } return rc; }      // (the handles own the arena by now)
+    }
+    ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.select_ms = T.sum(K_SEL); ctx->timing.total_ms = T.span();
+    ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
+    return 0;
+}
+
+// ---- allele tables of haplosets (stats_kernel.h: alleles_kernel) ------------------------------------------------------------------------------------------------
+int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
+                                const uint32_t* grp_read, const uint32_t* grp_range, uint32_t n_groups, const uint64_t* pos_off, uint32_t* counts) {
+    if (!ctx || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range || !pos_off))) return fail(FLORIA_E_INVALID, "null argument");
+    if (n_groups == 0) return 0;
+    if (grp_off[n_groups] && !grp_read) return fail(FLORIA_E_INVALID, "null argument");
+    std::vector<fl::ContigDev> cdev(n_contigs);
+    for (uint32_t i = 0; i < n_contigs; ++i) {
+        if (!contigs[i] || contigs[i]->ctx != ctx) return fail(FLORIA_E_INVALID, "bad contig handle");
+        cdev[i] = contigs[i]->dev;
+    }
+    std::vector<uint32_t> gc(n_groups, 0);
+    std::vector<uint64_t> hoff(n_groups + 1, 0);
+    if (pos_off[0] != 0) return fail(FLORIA_E_INVALID, "haploset_alleles: pos_off does not start at 0");
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        gc[g] = grp_contig ? grp_contig[g] : 0;
+        if (gc[g] >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
+        if (grp_off[g + 1] < grp_off[g]) return fail(FLORIA_E_INVALID, "grp_off decreases");
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) if (grp_read[i] >= contigs[gc[g]]->n_reads) return fail(FLORIA_E_INVALID, "group read id out of range");
+        const uint32_t lo = grp_range[2 * g], hi = grp_range[2 * g + 1];
+        const uint64_t len = hi >= lo ? (uint64_t)(hi - lo) + 1 : 0;
+        if (pos_off[g + 1] < pos_off[g] || pos_off[g + 1] - pos_off[g] != len)
+            return fail(FLORIA_E_INVALID, "haploset_alleles: pos_off is not the prefix sum of the range lengths at group " + std::to_string(g));
+        hoff[g + 1] = 4 * pos_off[g + 1];
+    }
+    const uint64_t n_counts = hoff[n_groups];
+    if (n_counts == 0) return 0;
+    if (!counts) return fail(FLORIA_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->batch_token = 0;                                  // misc is about to be overwritten (floria_hip_hap_graph checks the token)
+    const uint64_t n_reads_tot = grp_off[n_groups];
+    Carve C;
+    const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4ull * n_reads_tot + 4),
+              s_rg = C.seg(8ull * n_groups), s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * n_counts + 4);
+    int rc = C.place(ctx->misc); if (rc) return rc;
+    HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, gc.data(), 4ull * n_groups, ctx->stream));
+    HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4ull * n_reads_tot, ctx->stream));
+    HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, ctx->stream)); HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
+    HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
+    fl::StatsArgs a{};
+    a.contigs = C.at<const fl::ContigDev>(s_cd); a.grp_contig = C.at<const uint32_t>(s_gc); a.grp_off = C.at<const uint64_t>(s_go);
+    a.grp_read = C.at<const uint32_t>(s_gr); a.grp_range = C.at<const uint32_t>(s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
+    a.hist = C.at<uint32_t>(s_h); a.out = nullptr; a.n_groups = n_groups;
+    hipLaunchKernelGGL(fl::alleles_kernel, dim3(n_groups), dim3(256), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(counts, C.at(s_h), 4ull * n_counts, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // ---- get_hapq (part_block_manip.rs:517-616) for the haplosets of many contigs (the reference calls it once per contig) ----------

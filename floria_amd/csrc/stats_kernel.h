@@ -21,6 +21,22 @@ struct StatsArgs {
     uint32_t  n_groups;
 };
 
+// the unit-count histogram of haploset gi over its inclusive SNP range [lo, hi] (hi >= lo): hist[(snp - lo) * A + allele] += 1 for every cell of its reads inside the
+// range; 256 threads, 16 lanes per read.  Shared by stats_kernel and alleles_kernel.
+template <int A>
+__device__ __forceinline__ void haploset_hist_build(const StatsArgs& g, const ContigDev& cd, uint32_t gi, uint32_t lo, uint32_t hi, uint32_t* hist, uint32_t tid) {
+    const uint32_t grp = tid >> 4, sub = tid & 15;
+    const uint64_t r0 = g.grp_off[gi], r1 = g.grp_off[gi + 1];
+    for (uint64_t i = r0 + grp; i < r1; i += 16) {                    // 16 lanes per read
+        const uint32_t r = g.grp_read[i];
+        const uint32_t cb = G(cd.read_off)[r], ce = G(cd.read_off)[r + 1];
+        for (uint32_t c = cb + sub; c < ce; c += 16) {
+            const uint32_t sn = G(cd.cell_snp)[c];
+            if (sn >= lo && sn <= hi) atomicAdd(&hist[(uint64_t)(sn - lo) * A + (G(cd.cell_aw)[c] >> 28)], 1u);
+        }
+    }
+}
+
 template <int A>
 __global__ __launch_bounds__(256) void stats_kernel(StatsArgs g) {
     __shared__ unsigned long long s_sup, s_err;
@@ -33,16 +49,7 @@ __global__ __launch_bounds__(256) void stats_kernel(StatsArgs g) {
     if (tid == 0) { s_sup = 0; s_err = 0; s_nz = 0; }
     __syncthreads();
     if (hi >= lo) {
-        const uint32_t grp = tid >> 4, sub = tid & 15;
-        const uint64_t r0 = g.grp_off[gi], r1 = g.grp_off[gi + 1];
-        for (uint64_t i = r0 + grp; i < r1; i += 16) {                    // 16 lanes per read
-            const uint32_t r = g.grp_read[i];
-            const uint32_t cb = G(cd.read_off)[r], ce = G(cd.read_off)[r + 1];
-            for (uint32_t c = cb + sub; c < ce; c += 16) {
-                const uint32_t sn = G(cd.cell_snp)[c];
-                if (sn >= lo && sn <= hi) atomicAdd(&hist[(uint64_t)(sn - lo) * A + (G(cd.cell_aw)[c] >> 28)], 1u);
-            }
-        }
+        haploset_hist_build<A>(g, cd, gi, lo, hi, hist, tid);
         __syncthreads();
         unsigned long long sup = 0, err = 0;
         uint32_t nz = 0;
@@ -72,6 +79,17 @@ __global__ __launch_bounds__(256) void stats_kernel(StatsArgs g) {
         g.out[4 * (uint64_t)gi + 2] = errors;
         g.out[4 * (uint64_t)gi + 3] = total_support;
     }
+}
+
+// floria_hip_haploset_alleles: the same histogram as the RESULT — set_to_seq_dict(.., false) restricted to the haploset's range, what write_fragset_haplotypes
+// (file_writer.rs:308-369) iterates — always four counts per position (hist_off[g] = 4 * pos_off[g]).  Consensus and formatting stay on the host.
+__global__ __launch_bounds__(256) void alleles_kernel(StatsArgs g) {
+    const uint32_t gi = blockIdx.x;
+    if (gi >= g.n_groups) return;
+    const uint32_t lo = g.grp_range[2 * gi], hi = g.grp_range[2 * gi + 1];
+    if (hi < lo) return;
+    const ContigDev cd = g.contigs[g.grp_contig[gi]];
+    haploset_hist_build<4>(g, cd, gi, lo, hi, g.hist + g.hist_off[gi], threadIdx.x);
 }
 
 }  // namespace fl

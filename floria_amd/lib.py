@@ -29,6 +29,7 @@ SYMBOLS = [
     "floria_hip_contig_upload_batch", "floria_hip_host_alloc", "floria_hip_host_free", "floria_hip_set_option",
     "floria_hip_contig_download", "floria_hip_phase_pileups_batch",
     "floria_hip_pileup_records", "floria_hip_record_cells_free", "floria_hip_pileup_records_realign",
+    "floria_hip_pileup_records_resident", "floria_hip_record_summary_free", "floria_hip_assemble_contigs", "floria_hip_haploset_alleles",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -61,7 +62,7 @@ def load():
         L.floria_hip_last_error.restype = C.c_char_p
         L.floria_hip_version.restype = C.c_char_p
         for s in ("floria_hip_destroy", "floria_hip_ranges_free", "floria_hip_contig_free", "floria_hip_block_result_free", "floria_hip_groups_free",
-                  "floria_hip_groups_array_free", "floria_hip_hap_graph_free", "floria_hip_record_cells_free"):
+                  "floria_hip_groups_array_free", "floria_hip_hap_graph_free", "floria_hip_record_cells_free", "floria_hip_record_summary_free"):
             getattr(L, s).restype = None
         L.floria_hip_destroy.argtypes = [C.c_void_p]
         L.floria_hip_contig_free.argtypes = [C.c_void_p]
@@ -80,6 +81,11 @@ def load():
         L.floria_hip_record_cells_free.argtypes = [C.POINTER(capi.CRecordCells)]
         L.floria_hip_pileup_records_realign.argtypes = [C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(capi.CRefSeqs), C.POINTER(capi.CRealignWalk),
                                                         C.POINTER(C.POINTER(capi.CRecordCells)), C.POINTER(capi.CRealignCounts)]
+        L.floria_hip_pileup_records_resident.argtypes = [C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(capi.CRefSeqs), C.POINTER(capi.CRealignWalk),
+                                                         C.POINTER(C.POINTER(capi.CRecordSummary))]
+        L.floria_hip_record_summary_free.argtypes = [C.POINTER(capi.CRecordSummary)]
+        L.floria_hip_assemble_contigs.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(C.c_void_p)]
+        L.floria_hip_haploset_alleles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u32p, C.c_uint32, capi.u64p, capi.u32p]
         _LIB = L
     return _LIB
 
@@ -249,6 +255,34 @@ class ContigBatch:
             for i in range(self.n):
                 L.floria_hip_contig_free(C.c_void_p(self._arr[i]))
             self._arr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class RecordSummary:
+    """floria_record_summary of one FloriaHip.pileup_records_resident call: numpy copies of the per-record arrays (cell_off uint64 [n + 1], first_snp / last_snp
+    uint32 [n], ref_end int64 [n]), the realign counts, and the library-owned struct itself, which FloriaHip.assemble_contigs hands back to the library.  The cells
+    stay on the device until the context's next pileup_records* call."""
+
+    def __init__(self, ctx, cptr, n):
+        self.ctx, self._p = ctx, cptr
+        r = cptr.contents
+        self.n_records = n
+        self.cell_off = capi.np_from(r.cell_off, n + 1, np.uint64)
+        self.first_snp = capi.np_from(r.first_snp, n, np.uint32)
+        self.last_snp = capi.np_from(r.last_snp, n, np.uint32)
+        self.ref_end = capi.np_from(r.ref_end, n, np.int64)
+        self.counts = {f: int(getattr(r.counts, f)) for f, _ in capi.CRealignCounts._fields_}
+        self.token = int(r.token)
+
+    def free(self):
+        if self._p is not None:
+            load().floria_hip_record_summary_free(self._p)
+            self._p = None
 
     def __del__(self):
         try:
@@ -456,7 +490,45 @@ class FloriaHip:
         (step, rule, tie) / (block, step, rule, tie) as realign_walk() takes them.  -> (the six arrays of pileup_records, dict(cells, in_bounds, shortcut, scored, changed))."""
         return self._pileup_records(blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=(ref_off, ref_seq), walk=walk)
 
-    def _pileup_records(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=None, walk=None):
+    def pileup_records_resident(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, ref_off=None, ref_seq=None, walk=None):
+        """floria_hip_pileup_records_resident: pileup_records() (ref_off None) or pileup_records_realign() whose cells stay on the device -> RecordSummary
+        (free() it when the fragments are assembled).  Any later pileup_records* call on this context ends the residency."""
+        return self._pileup_records(blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles,
+                                    refs=None if ref_off is None else (ref_off, ref_seq), walk=walk, resident=True)
+
+    def assemble_contigs(self, summary, frag_off, part_off, part_rec, set_order=None):
+        """floria_hip_assemble_contigs: the fragment plan (frag_off uint64 [n_contigs + 1], part_off uint64 [n_frags + 1], part_rec uint32 record indices in merge
+        order, optional set_order uint32 over the merged cells of all contigs) -> one ResidentContig per contig, usable wherever uploaded ones are."""
+        fo = np.ascontiguousarray(frag_off, np.uint64); po = np.ascontiguousarray(part_off, np.uint64); pr = np.ascontiguousarray(part_rec, np.uint32)
+        if len(fo) < 1 or len(po) != int(fo[-1]) + 1 or (len(po) and len(pr) < int(po.max())):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: frag_off needs n_contigs + 1 entries, part_off n_frags + 1, part_rec part_off[-1]")
+        so = None if set_order is None else np.ascontiguousarray(set_order, np.uint32)
+        n = len(fo) - 1
+        plan = capi.CFragmentPlan(n, capi.ptr(fo, C.c_uint64), capi.ptr(po, C.c_uint64), capi.ptr(pr, C.c_uint32), None if so is None else capi.ptr(so, C.c_uint32))
+        hs = (C.c_void_p * max(n, 1))()
+        if summary._p is None:
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: the record summary has been freed")
+        _check(load().floria_hip_assemble_contigs(self._h, summary._p, C.byref(plan), hs))
+        return [ResidentContig(self, handle=C.c_void_p(hs[i]), n_reads=int(fo[i + 1] - fo[i])) for i in range(n)]
+
+    def haploset_alleles(self, contigs, grp_contig, groups, ranges):
+        """floria_hip_haploset_alleles: per haploset (read-id list + inclusive SNP range, as haploset_stats takes them) the number of its reads calling each allele
+        at every SNP of its range -> (pos_off uint64 [n_groups + 1], counts uint32 [pos_off[-1], 4]): row pos_off[g] + (p - lo_g) is SNP p of group g."""
+        arr = (C.c_void_p * len(contigs))(*[c._h for c in contigs])
+        gc = np.ascontiguousarray(grp_contig, np.uint32)
+        off = np.zeros(len(groups) + 1, np.uint64)
+        off[1:] = np.cumsum([len(g) for g in groups])
+        reads = np.ascontiguousarray(np.concatenate([np.asarray(g, np.uint32) for g in groups] + [np.zeros(0, np.uint32)]), np.uint32)
+        rng = np.ascontiguousarray(np.asarray(ranges, np.uint32).reshape(-1))
+        lens = [max(0, int(hi) - int(lo) + 1) for lo, hi in np.asarray(ranges, np.int64).reshape(-1, 2)]
+        pos_off = np.zeros(len(groups) + 1, np.uint64)
+        pos_off[1:] = np.cumsum(lens)
+        counts = np.zeros((int(pos_off[-1]), 4), np.uint32)
+        _check(load().floria_hip_haploset_alleles(self._h, arr, C.c_uint32(len(contigs)), capi.ptr(gc, C.c_uint32), capi.ptr(off, C.c_uint64), capi.ptr(reads, C.c_uint32),
+                                                  capi.ptr(rng, C.c_uint32), C.c_uint32(len(groups)), capi.ptr(pos_off, C.c_uint64), capi.ptr(counts, C.c_uint32)))
+        return pos_off, counts
+
+    def _pileup_records(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=None, walk=None, resident=False):
         def arr(a, dt):
             return a if isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous else np.ascontiguousarray(a, dt)
         keep = [arr(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8), arr(pos, np.int32), arr(flags, np.uint16),
@@ -473,6 +545,11 @@ class FloriaHip:
         S = capi.CSnpTable(len(soff) - 1, capi.ptr(soff, C.c_uint64), capi.ptr(sp, C.c_int64), capi.ptr(al, C.c_uint8), capi.ptr(na, C.c_uint8))
         out = C.POINTER(capi.CRecordCells)()
         counts = None
+        if resident:
+            out = C.POINTER(capi.CRecordSummary)()
+        if refs is None and resident:
+            _check(load().floria_hip_pileup_records_resident(self._h, C.byref(A), C.byref(S), None, None, C.byref(out)))
+            return RecordSummary(self, out, n)
         if refs is None:
             _check(load().floria_hip_pileup_records(self._h, C.byref(A), C.byref(S), C.byref(out)))
         else:
@@ -486,6 +563,9 @@ class FloriaHip:
             if walk is not None:
                 block, step, rule, tie = walk if len(walk) == 4 else (8,) + tuple(walk)
                 w = capi.CRealignWalk(int(block), int(step), {"max": 0, "sum": 1}.get(rule, rule), {"right": 0, "down": 1}.get(tie, tie))
+            if resident:
+                _check(load().floria_hip_pileup_records_resident(self._h, C.byref(A), C.byref(S), C.byref(F), C.byref(w) if w is not None else None, C.byref(out)))
+                return RecordSummary(self, out, n)
             cc = capi.CRealignCounts()
             _check(load().floria_hip_pileup_records_realign(self._h, C.byref(A), C.byref(S), C.byref(F), C.byref(w) if w is not None else None, C.byref(out), C.byref(cc)))
             counts = dict(cells=int(cc.cells), in_bounds=int(cc.in_bounds), shortcut=int(cc.shortcut), scored=int(cc.scored), changed=int(cc.changed))

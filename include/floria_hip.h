@@ -409,6 +409,69 @@ typedef struct { uint64_t cells, in_bounds, shortcut, scored, changed; } floria_
 int  floria_hip_pileup_records_realign(floria_hip_ctx* ctx, const floria_alignments* alignments, const floria_snp_table* snps, const floria_ref_seqs* refs,
                                        const floria_realign_walk* walk /* NULL = exact DP */, floria_record_cells** out, floria_realign_counts* counts /* may be NULL */);
 
+/* ---- records -> cells -> RESIDENT CONTIGS: the cells never leave the device ----------------------------------------------------------------------------------------
+ * floria_hip_pileup_records_resident is floria_hip_pileup_records (refs == NULL: the walk alone) or floria_hip_pileup_records_realign (refs given; walk as there,
+ * NULL = exact DP) with the same inputs, the same validation and the same kernels, but the per-cell arrays (snp, allele, qual, seq_pos) are NOT copied back: they
+ * stay in the context's pileup buffers for floria_hip_assemble_contigs.  The library-owned summary holds what a host needs to plan fragments (header-sized, per
+ * record): cell_off, the SNP of the record's first / last cell (0 / 0 for a record without cells), ref_end, and the realign counts (cells alone without refs).
+ * Every value equals what floria_hip_pileup_records[_realign] returns for the same inputs.
+ * RESIDENCY.  The context remembers `token`; the cells stay valid until the NEXT floria_hip_pileup_records, floria_hip_pileup_records_realign or
+ * floria_hip_pileup_records_resident call on the context (each of them rewrites the pileup buffers, whether it succeeds or not) or floria_hip_destroy.  Nothing else
+ * ends it: uploads, floria_hip_phase_*, floria_hip_reassign*, floria_hip_hap_graph, floria_hip_haploset_*, floria_hip_hapq*, floria_hip_realign* and
+ * floria_hip_assemble_contigs itself work in other buffers, so one residency can be assembled any number of times.  Like floria_hip_pileup_records_realign the call
+ * may end the residency of the last phase_blocks* batch (floria_hip_hap_graph) when refs are given.  The summary must stay alive (not freed) while it is used. */
+typedef struct {
+    uint32_t  n_records;
+    uint64_t* cell_off;        /* [n+1] record i owns cells [cell_off[i], cell_off[i+1]) of the resident arrays       */
+    uint32_t* first_snp;       /* [n]   1-based SNP index of the record's first cell, 0 if it has none                */
+    uint32_t* last_snp;        /* [n]   ... of its last cell, 0 if it has none                                        */
+    int64_t*  ref_end;         /* [n]   as floria_record_cells::ref_end                                               */
+    floria_realign_counts counts;   /* as floria_hip_pileup_records_realign reports them; without refs only `cells`   */
+    uint64_t  token;           /* identifies the device-resident cells (floria_hip_assemble_contigs)                  */
+} floria_record_summary;
+int  floria_hip_pileup_records_resident(floria_hip_ctx* ctx, const floria_alignments* alignments, const floria_snp_table* snps, const floria_ref_seqs* refs /* NULL = walk only */,
+                                        const floria_realign_walk* walk /* NULL = exact DP */, floria_record_summary** out);
+void floria_hip_record_summary_free(floria_record_summary* s);
+
+/* A fragment plan: which records of the resident call form a fragment (a `Frag` after combine_frags, file_reader.rs:539-541 and :636-639), in which order they
+ * are merged, and in which order the fragments of a contig stand.  All of it follows from names, flags and the per-record spans of the summary. */
+typedef struct {
+    uint32_t        n_contigs;   /* == the SNP table's n_contigs of the resident pileup call; plan contig c is table contig c */
+    const uint64_t* frag_off;    /* [n_contigs+1]  fragments of contig c, in the pileup's read order (Frag::cmp) */
+    const uint64_t* part_off;    /* [n_frags+1]    into part_rec */
+    const uint32_t* part_rec;    /* record indices of the resident call, in MERGE order: the first is the base, each later one is `extend`ed onto it */
+    const uint32_t* set_order;   /* optional, NULL = not given: as floria_pileup::set_order, indexed by the MERGED cells of all contigs back to back */
+} floria_fragment_plan;
+
+/* combine_frags on the device: out[c] (c < plan->n_contigs) receives a resident contig whose read r is fragment frag_off[c] + r of the plan.
+ *   - a fragment's cells: one cell per SNP that occurs in any of its parts, in ascending SNP order; allele and qual of a SNP come from the LAST part in list order
+ *     that has it (`seq_dict.extend`: the later record's call overwrites the earlier one);
+ *   - first / last: the smallest / largest merged SNP (= the min of the parts' firsts / max of their lasts; a part without cells changes neither);
+ *   - seq_pos and ref_end are not part of a contig; records the plan does not name are unused; a record may appear anywhere, any number of times; parts need not
+ *     be in genome order.
+ * The handles are indistinguishable from those floria_hip_contig_upload_batch returns for the equivalent floria_pileup array: every floria_hip_contig_download
+ * field has the same bytes, the derived properties (biallelic / q = 0 routing, set_order in "arith" = 1, one arena for the batch) are the same, each is freed with
+ * floria_hip_contig_free and every entry point that takes a contig takes them.  The merged cells are written into an arena laid out as an upload's
+ * (csrc/assemble_kernel.h) and then validated and flattened by the upload's own kernel, so everything a host upload validates is validated here with the same
+ * messages: Frag::cmp order of the fragments, ascending cells, 1-based SNPs, allele <= 3.  A contig without fragments is a pileup with n_reads == 0.
+ * Checked on the host before anything is launched, FLORIA_E_INVALID each: a null argument; `resident` is not the context's live residency (see above); n_contigs
+ * differs from the resident call's; frag_off / part_off not starting at 0 or not ascending; a fragment with no part; a part_rec index >= n_records; a part whose
+ * record belongs to another contig than its fragment; a fragment whose parts have no cell at all ("every read has >= 1 cell").  FLORIA_E_UNSUPPORTED: 2^32 and more
+ * cells in one contig (as upload), 2^32 and more fragments.  With a set_order the cell orders are computed at once (the kernels "arith" = 1 runs before S1) and one
+ * that is not a permutation of a fragment's cell indices is FLORIA_E_INVALID with the message S1 gives for an uploaded one.  On error no handle is returned and the
+ * residency stays.  floria_hip_last_timing then reports pileup_ms (merge passes + scan), select_ms (flatten), h2d_ms, d2h_ms, total_ms. */
+int  floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary* resident, const floria_fragment_plan* plan, floria_hip_contig** out /* [n_contigs] */);
+
+/* Allele tables of haplosets for a host that holds no cells (the allele strings of .vartigs / vartig_info.txt): the groups are given as for
+ * floria_hip_haploset_stats; counts[4 * (pos_off[g] + (p - lo_g)) + a] = the number of group g's reads that call allele a at SNP p of its inclusive range
+ * [lo_g, hi_g] — set_to_seq_dict(.., false) restricted to the range, what write_fragset_haplotypes (file_writer.rs:308-369) iterates.  pos_off [n_groups+1] is the
+ * caller's prefix sum of the range lengths (hi - lo + 1, 0 for a group with hi < lo; anything else is FLORIA_E_INVALID); counts has 4 * pos_off[n_groups] entries.
+ * Cells outside the range are ignored; a group with hi < lo or without reads contributes nothing.  Consensus and formatting stay on the host.  Like
+ * floria_hip_haploset_stats the call works in the buffer that holds the last phase_blocks* batch and ends that batch's residency (floria_hip_hap_graph). */
+int  floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                                 const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
+                                 const uint32_t* grp_range, uint32_t n_groups, const uint64_t* pos_off, uint32_t* counts);
+
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
 /* Self-test of a hardware assumption: the beam kernel screens the pruning test (global_clustering.rs:98) with an f32 evaluation of stable_binom_cdf_p_rev
