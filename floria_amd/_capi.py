@@ -102,6 +102,11 @@ class CFragmentPlan(C.Structure):
     _fields_ = [("n_contigs", C.c_uint32), ("frag_off", u64p), ("part_off", u64p), ("part_rec", u32p), ("set_order", u32p)]
 
 
+class CMonoResult(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint32), ("read_off", u64p), ("old_read", u32p), ("removed", u8p),
+                ("n_removed_snps", C.c_uint64), ("n_removed_cells", C.c_uint64), ("n_dropped_reads", C.c_uint64)]
+
+
 def ptr(a, ctype):
     """Pointer to a C-contiguous numpy array (the array must outlive the call)."""
     return a.ctypes.data_as(C.POINTER(ctype))

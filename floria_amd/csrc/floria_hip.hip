@@ -45,6 +45,7 @@
 #include "realign_gather_kernel.h"
 #include "upload_kernel.h"
 #include "assemble_kernel.h"
+#include "mono_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -255,6 +256,8 @@ struct floria_hip_ctx {
     std::vector<uint32_t> res_contig;         // contig of every record (header-sized; the plan is validated against it)
     const uint64_t* res_cell_off = nullptr; const uint32_t* res_snp = nullptr; const uint8_t *res_allele = nullptr, *res_qual = nullptr;
     DevBuf asm_plan;                          // floria_hip_assemble_contigs: the fragment plan and the per-fragment cell counts / offsets
+    double mono_ms[6] = {};                   // the last floria_hip_drop_monomorphic call's device time by kind (floria_hip_mono_timing)
+    DevBuf mono_buf;                          // floria_hip_drop_monomorphic: the per-SNP tables, the per-read survivor words and the call's small tables
     uint32_t stage_threads = 8;
 };
 
@@ -980,7 +983,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->mono_buf}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -1159,6 +1162,29 @@ struct UploadPlan {
     bool all_pinned = false;
 };
 
+// Where the regions of a batch arena lie, for R reads and C cells in n contigs: the ONE definition every producer of resident contigs uses (plan_upload,
+// floria_hip_assemble_contigs, floria_hip_drop_monomorphic), so that their handles cannot differ in layout.  16-B tails: the beam kernel's LDS-DMA moves cells in
+// 16-B pieces.  The set-order region exists only when some contig carries one.
+struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, bytes = 0; };
+ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so) {
+    ArenaLayout Y;
+    size_t cursor = 0;
+    auto seg = [&](size_t bytes) { const size_t o = cursor; cursor += (bytes + 255) & ~(size_t)255; return o; };
+    Y.o_ro = seg(4 * (R + n)); Y.o_first = seg(4 * R); Y.o_last = seg(4 * R); Y.o_snp = seg(4 * C + 16); Y.o_aw = seg(4 * C + 16); Y.o_tw = seg(16 * R); Y.o_meta = seg(32 * R);
+    Y.o_so = any_so ? seg(4 * C + 16) : 0;
+    Y.bytes = cursor;
+    return Y;
+}
+// ... and contig i's views into them (rp / cp: reads / cells before every contig); the transient raw allele / qual pointers are the caller's
+void arena_contig(const ArenaLayout& Y, char* D, const std::vector<uint64_t>& rp, const std::vector<uint64_t>& cp, uint32_t i, fl::UploadContig& u) {
+    u.read_off = (const uint32_t*)(D + Y.o_ro + 4 * (rp[i] + i)); u.first = (const uint32_t*)(D + Y.o_first + 4 * rp[i]); u.last = (const uint32_t*)(D + Y.o_last + 4 * rp[i]);
+    u.snp = (const uint32_t*)(D + Y.o_snp + 4 * cp[i]); u.cell_aw = (uint32_t*)(D + Y.o_aw + 4 * cp[i]); u.tw = (uint64_t*)(D + Y.o_tw + 16 * rp[i]); u.meta = (uint32_t*)(D + Y.o_meta + 32 * rp[i]);
+    u.n_reads = (uint32_t)(rp[i + 1] - rp[i]); u.n_cells = (uint32_t)(cp[i + 1] - cp[i]);
+}
+void arena_describe(Arena* A, const ArenaLayout& Y, uint32_t n, uint64_t R, uint64_t C, const std::vector<uint64_t>& rp) {
+    A->n_contigs = n; A->R = R; A->C = C; A->off_ro = Y.o_ro; A->off_first = Y.o_first; A->off_last = Y.o_last; A->read_prefix = rp; A->host_meta = false;
+}
+
 // (a batch is either CSR pileups or packed ones: `pk` non-null selects the compact wire form, expanded on the device)
 int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_pileup_packed* pk, uint32_t n, uint32_t n_chunks, UploadPlan& P) {
     P.n = n; P.packed = pk != nullptr;
@@ -1202,16 +1228,13 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
         for (uint32_t h = g + 1; h < n_chunks; ++h) P.chunk_first[h] = n;          // (fewer non-empty chunks than asked for)
     }
     // ---- arena layout -------------------------------------------------------------------------------------------------------
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { const size_t o = cursor; cursor += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_ro = seg(4 * (R + n)), o_first = seg(4 * R), o_last = seg(4 * R), o_snp = seg(4 * C + 16), o_aw = seg(4 * C + 16),      // 16-B tails: the
-                 o_tw = seg(16 * R), o_meta = seg(32 * R);                                              // beam kernel's LDS-DMA moves cells in 16-B pieces
-    bool any_so = false;
+    bool any_so = false;                                                                                // host-given set orders (optional, the reference-arithmetic mode reads them)
     for (uint32_t i = 0; i < n; ++i) any_so = any_so || (pileups[i].n_reads && pileups[i].set_order);
-    const size_t o_so = any_so ? seg(4 * C + 16) : 0;                                                   // host-given set orders (optional, the reference-arithmetic mode reads them)
-    Arena* A = P.A = arena_get(ctx, cursor + 256);
+    const ArenaLayout Y = layout_arena(R, C, n, any_so);
+    const size_t o_ro = Y.o_ro, o_first = Y.o_first, o_last = Y.o_last, o_snp = Y.o_snp, o_so = Y.o_so;
+    Arena* A = P.A = arena_get(ctx, Y.bytes + 256);
     if (!A) return FLORIA_E_NOMEM;
-    A->n_contigs = n; A->R = R; A->C = C; A->off_ro = o_ro; A->off_first = o_first; A->off_last = o_last; A->read_prefix = P.rp; A->host_meta = false;
+    arena_describe(A, Y, n, R, C, P.rp);
     char* D = P.D = A->buf.as<char>();
     // transient: raw allele / qual bytes, the kernel's contig table, prefix and status
     size_t c2 = 0;
@@ -1268,10 +1291,8 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
             }
     for (uint32_t i = 0; i < n; ++i) {
         fl::UploadContig& u = P.ucd[i];
-        u.read_off = (const uint32_t*)(D + o_ro + 4 * (P.rp[i] + i)); u.first = (const uint32_t*)(D + o_first + 4 * P.rp[i]); u.last = (const uint32_t*)(D + o_last + 4 * P.rp[i]);
-        u.snp = (const uint32_t*)(D + o_snp + 4 * P.cp[i]); u.allele = (const uint8_t*)(T + t_al + P.cp[i]); u.qual = (const uint8_t*)(T + t_q + P.cp[i]);
-        u.cell_aw = (uint32_t*)(D + o_aw + 4 * P.cp[i]); u.tw = (uint64_t*)(D + o_tw + 16 * P.rp[i]); u.meta = (uint32_t*)(D + o_meta + 32 * P.rp[i]);
-        u.n_reads = pileups[i].n_reads; u.n_cells = (uint32_t)(P.cp[i + 1] - P.cp[i]);
+        arena_contig(Y, D, P.rp, P.cp, i, u);
+        u.allele = (const uint8_t*)(T + t_al + P.cp[i]); u.qual = (const uint8_t*)(T + t_q + P.cp[i]);
         P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
     }
     P.so_dev.assign(n, nullptr);
@@ -2751,13 +2772,11 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     const uint64_t R = P.R = NF, CC = P.C = cp[n];
     P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
     const bool any_so = plan->set_order != nullptr && CC != 0;
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { const size_t o = cursor; cursor += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_ro = seg(4 * (R + n)), o_first = seg(4 * R), o_last = seg(4 * R), o_snp = seg(4 * CC + 16), o_aw = seg(4 * CC + 16), o_tw = seg(16 * R), o_meta = seg(32 * R);
-    const size_t o_so = any_so ? seg(4 * CC + 16) : 0;
-    Arena* AR = P.A = arena_get(ctx, cursor + 256);
+    const ArenaLayout AL = layout_arena(R, CC, n, any_so);
+    const size_t o_ro = AL.o_ro, o_first = AL.o_first, o_last = AL.o_last, o_snp = AL.o_snp, o_so = AL.o_so;
+    Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
     if (!AR) return FLORIA_E_NOMEM;
-    AR->n_contigs = n; AR->R = R; AR->C = CC; AR->off_ro = o_ro; AR->off_first = o_first; AR->off_last = o_last; AR->read_prefix = P.rp; AR->host_meta = false;
+    arena_describe(AR, AL, n, R, CC, P.rp);
     char* D = P.D = AR->buf.as<char>();
     size_t c2 = 0;
     auto seg2 = [&](size_t bytes) { const size_t o = c2; c2 += (bytes + 255) & ~(size_t)255; return o; };
@@ -2769,10 +2788,8 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     P.ucd.resize(n); P.ust.resize(n); P.so_dev.assign(n, nullptr);
     for (uint32_t i = 0; i < n; ++i) {
         fl::UploadContig& u = P.ucd[i];
-        u.read_off = (const uint32_t*)(D + o_ro + 4 * (P.rp[i] + i)); u.first = (const uint32_t*)(D + o_first + 4 * P.rp[i]); u.last = (const uint32_t*)(D + o_last + 4 * P.rp[i]);
-        u.snp = (const uint32_t*)(D + o_snp + 4 * cp[i]); u.allele = (const uint8_t*)(TT + t_al + cp[i]); u.qual = (const uint8_t*)(TT + t_q + cp[i]);
-        u.cell_aw = (uint32_t*)(D + o_aw + 4 * cp[i]); u.tw = (uint64_t*)(D + o_tw + 16 * P.rp[i]); u.meta = (uint32_t*)(D + o_meta + 32 * P.rp[i]);
-        u.n_reads = (uint32_t)(P.rp[i + 1] - P.rp[i]); u.n_cells = (uint32_t)(cp[i + 1] - cp[i]);
+        arena_contig(AL, D, P.rp, cp, i, u);
+        u.allele = (const uint8_t*)(TT + t_al + cp[i]); u.qual = (const uint8_t*)(TT + t_q + cp[i]);
         P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
         if (any_so && u.n_reads) P.so_dev[i] = (const uint32_t*)(D + o_so + 4 * cp[i]);
     }
@@ -2808,6 +2825,200 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     }
     ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.select_ms = T.sum(K_SEL); ctx->timing.total_ms = T.span();
     ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
+    return 0;
+}
+
+// ---- remove_monomorphic_allele (utils_frags.rs:713-772) on resident contigs (mono_kernel.h) ----------------------------------------------------------------------
+int floria_hip_mono_timing(const floria_hip_ctx* ctx, double* ms6) {
+    if (!ctx || !ms6) return fail(FLORIA_E_INVALID, "null argument");
+    for (int k = 0; k < 6; ++k) ms6[k] = ctx->mono_ms[k];
+    return 0;
+}
+
+void floria_hip_mono_result_free(floria_mono_result* r) {
+    if (!r) return;
+    free(r->read_off); free(r->old_read); free(r->removed); free(r);
+}
+
+int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n, const uint64_t* snp_off, double error, int with_set_order,
+                                floria_hip_contig** out, floria_mono_result** res) {
+    if (res) *res = nullptr;
+    if (out) for (uint32_t c = 0; c < n; ++c) out[c] = nullptr;
+    if (!ctx || !out || !snp_off || (n && !contigs)) return fail(FLORIA_E_INVALID, "null argument");
+    // ---- everything the host can tell, before anything is launched ----
+    for (uint32_t c = 0; c < n; ++c) {
+        if (!contigs[c]) return fail(FLORIA_E_INVALID, "null argument");
+        if (contigs[c]->ctx != ctx) return fail(FLORIA_E_INVALID, "drop_monomorphic: contig " + std::to_string(c) + " belongs to another context");
+    }
+    if (snp_off[0] != 0) return fail(FLORIA_E_INVALID, "drop_monomorphic: snp_off does not start at 0");
+    for (uint32_t c = 0; c < n; ++c) if (snp_off[c + 1] < snp_off[c]) return fail(FLORIA_E_INVALID, "drop_monomorphic: snp_off decreases at contig " + std::to_string(c));
+    if (!std::isfinite(error)) return fail(FLORIA_E_INVALID, "drop_monomorphic: error is not finite");
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<uint64_t> rp(n + 1, 0), cpi(n + 1, 0);          // input reads / cells before contig c
+    for (uint32_t c = 0; c < n; ++c) {
+        const floria_hip_contig* k = contigs[c];
+        if (int rc = host_meta(k)) return rc;
+        uint32_t hi = 0;
+        for (uint32_t r = 0; r < k->n_reads; ++r) hi = std::max(hi, k->h_last[r]);
+        if ((uint64_t)hi > snp_off[c + 1] - snp_off[c])
+            return fail(FLORIA_E_INVALID, "drop_monomorphic: contig " + std::to_string(c) + " has a read that ends at SNP " + std::to_string(hi) + ", its SNP count is " + std::to_string((unsigned long long)(snp_off[c + 1] - snp_off[c])));
+        rp[c + 1] = rp[c] + k->n_reads; cpi[c + 1] = cpi[c] + k->n_cells;
+    }
+    const uint64_t Rin = rp[n], S = snp_off[n];
+    floria_mono_result* M = nullptr;                          // (allocated behind the last launch: nothing to release on the error paths before it)
+    const auto give_up = [&](int rc) { floria_hip_mono_result_free(M); M = nullptr; return rc; };
+    const auto new_result = [&](uint64_t n_out, uint64_t n_mask) {
+        M = (floria_mono_result*)calloc(1, sizeof(floria_mono_result));
+        if (!M) return false;
+        M->n_contigs = n;
+        M->read_off = (uint64_t*)calloc(n + 1, 8); M->old_read = (uint32_t*)calloc(n_out + 1, 4); M->removed = (uint8_t*)calloc(n_mask + 1, 1);
+        return M->read_off && M->old_read && M->removed;
+    };
+    if (n == 0) {
+        if (res) { if (!new_result(0, 0)) return give_up(fail(FLORIA_E_NOMEM, "calloc")); *res = M; }
+        return 0;
+    }
+    EventTimer T(ctx->stream);
+    ctx->timing = floria_timing{};
+    enum { K_CLEAR = 20, K_COUNT = 21, K_DECIDE = 22, K_FCOUNT = 23, K_FILL = 24, K_ORDER = 25 };      // (the device work of pileup_ms, one kind each: floria_hip_mono_timing)
+    // ---- the input contigs' set orders, through S1's own path and before the new arena makes the cached ones stale ----
+    Carve C;
+    const Seg s_mc = C.seg(sizeof(fl::MonoContig) * n), s_rp = C.seg(8ull * (n + 1)), s_so = C.seg(8ull * (n + 1)), s_ws = C.seg(32 * S + 32), s_zk = C.seg(4 * S + 4), s_rm = C.seg(S + 16),
+              s_nr = C.seg(8ull * n), s_k3 = C.seg(12 * Rin + 16), s_cdev = C.seg(sizeof(fl::ContigDev) * n), s_uc = C.seg(sizeof(fl::UploadContig) * n), s_op = C.seg(8ull * (n + 1)),
+              s_or = C.seg(4 * Rin + 16), s_st = C.seg(sizeof(fl::UploadStatus) * n), s_sop = C.seg(8ull * n);
+    if (int rc = C.place(ctx->mono_buf)) return give_up(rc);
+    int t = 0;
+    if (with_set_order && Rin) {
+        std::vector<fl::ContigDev> cdev(n); std::vector<uint64_t> ncells(n); uint32_t len_max = 1;
+        for (uint32_t i = 0; i < n; ++i) { cdev[i] = contigs[i]->dev; ncells[i] = contigs[i]->n_cells; len_max = std::max(len_max, contigs[i]->max_len); }
+        t = T.begin(K_H2D);
+        HIPCHK(C.up(s_cdev, cdev.data(), sizeof(fl::ContigDev) * n, ctx->stream));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        t = T.begin(K_ORDER);
+        const int orc = cell_orders(ctx, C.at<const fl::ContigDev>(s_cdev), cdev, ncells, len_max);
+        T.end(t);
+        if (orc) { sync_all(ctx); return give_up(orc); }
+    }
+    // ---- count, decide, COUNT: three words per input read come back ----
+    std::vector<fl::MonoContig> mc(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const floria_hip_contig* k = contigs[i];
+        fl::MonoContig& m = mc[i];
+        m.read_off = k->dev.read_off; m.snp = k->dev.cell_snp; m.cell_aw = k->dev.cell_aw; m.snp_base = snp_off[i]; m.ord_base = cpi[i];
+        m.n_reads = k->n_reads; m.n_cells = (uint32_t)k->n_cells; m.n_snps = (uint32_t)std::min<uint64_t>(snp_off[i + 1] - snp_off[i], 0xffffffffull); m.pad = 0;
+    }
+    fl::MonoArgs a{};
+    a.contigs = C.at<const fl::MonoContig>(s_mc); a.read_prefix = C.at<const uint64_t>(s_rp); a.snp_off = C.at<const uint64_t>(s_so); a.wsum = C.at<unsigned long long>(s_ws);
+    a.zero_key = C.at<uint32_t>(s_zk); a.removed = C.at<uint8_t>(s_rm); a.n_removed = C.at<unsigned long long>(s_nr); a.keep3 = C.at<uint32_t>(s_k3);
+    a.error = error; a.n_reads_in = Rin; a.n_snps_total = S; a.n_contigs = n;
+    t = T.begin(K_H2D);
+    HIPCHK(C.up(s_mc, mc.data(), sizeof(fl::MonoContig) * n, ctx->stream)); HIPCHK(C.up(s_rp, rp.data(), 8ull * (n + 1), ctx->stream)); HIPCHK(C.up(s_so, snp_off, 8ull * (n + 1), ctx->stream));
+    T.end(t);
+    t = T.begin(K_CLEAR);
+    HIPCHK(hipMemsetAsync(C.at(s_ws), 0, s_ws.bytes, ctx->stream)); HIPCHK(hipMemsetAsync(C.at(s_zk), 0, s_zk.bytes, ctx->stream));
+    HIPCHK(hipMemsetAsync(C.at(s_rm), 0, s_rm.bytes, ctx->stream)); HIPCHK(hipMemsetAsync(C.at(s_nr), 0, 8ull * n, ctx->stream));
+    T.end(t);
+    const unsigned wgs_in = (unsigned)((Rin + fl::UP_READS_PER_WG - 1) / fl::UP_READS_PER_WG);
+    std::vector<uint32_t> k3(3 * Rin);
+    std::vector<unsigned long long> n_rm(n, 0);
+    if (Rin) {
+        t = T.begin(K_COUNT); hipLaunchKernelGGL(fl::mono_count_kernel, dim3(wgs_in), dim3(64), 0, ctx->stream, a); T.end(t);
+        HIPCHK(hipGetLastError());
+        if (S) { t = T.begin(K_DECIDE); hipLaunchKernelGGL(fl::mono_decide_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, a); T.end(t); }
+        HIPCHK(hipGetLastError());
+        t = T.begin(K_FCOUNT); hipLaunchKernelGGL(fl::mono_filter_kernel<false>, dim3(wgs_in), dim3(64), 0, ctx->stream, a); T.end(t);
+        HIPCHK(hipGetLastError());
+        t = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(k3.data(), C.at(s_k3), 12 * Rin, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(n_rm.data(), C.at(s_nr), 8ull * n, hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    // ---- the host's part: drop the empty reads, Frag::cmp with the old index, prefix sums ----
+    UploadPlan P;
+    P.n = n; P.n_chunks = 1; P.packed = false;
+    P.rp.assign(n + 1, 0); P.cp.assign(n + 1, 0);
+    std::vector<uint32_t> old_read; old_read.reserve(Rin);
+    std::vector<uint32_t> ro_all;                              // the output contigs' read_off arrays as the arena holds them: contig c's [n_reads + 1] entries start at rp[c] + c
+    uint64_t kept_cells = 0;
+    for (uint32_t c = 0; c < n; ++c) {
+        const uint32_t* k = k3.data() + 3 * rp[c];
+        const size_t at = old_read.size();
+        for (uint32_t r = 0; r < contigs[c]->n_reads; ++r) if (k[3 * (size_t)r]) old_read.push_back(r);
+        std::stable_sort(old_read.begin() + at, old_read.end(), [&](uint32_t x, uint32_t y) {
+            const uint32_t fx = k[3 * (size_t)x + 1], fy = k[3 * (size_t)y + 1], lx = k[3 * (size_t)x + 2], ly = k[3 * (size_t)y + 2];
+            return fx != fy ? fx < fy : lx > ly;
+        });
+        uint64_t cells = 0;
+        ro_all.push_back(0);
+        for (size_t i = at; i < old_read.size(); ++i) { cells += k[3 * (size_t)old_read[i]]; ro_all.push_back((uint32_t)cells); }
+        if (cells > contigs[c]->n_cells) return give_up(fail(FLORIA_E_DEVICE, "drop_monomorphic: a contig's surviving cells outnumber its cells"));
+        P.rp[c + 1] = old_read.size(); P.cp[c + 1] = P.cp[c] + cells;
+        kept_cells += cells;
+    }
+    const uint64_t R = P.R = P.rp[n], CC = P.C = P.cp[n];
+    // ---- the arena, laid out as plan_upload lays out a CSR batch of these sizes ----
+    ctx->upload_epoch++;
+    P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
+    const bool any_so = with_set_order != 0 && CC != 0;
+    const ArenaLayout AL = layout_arena(R, CC, n, any_so);
+    Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
+    if (!AR) return give_up(FLORIA_E_NOMEM);
+    arena_describe(AR, AL, n, R, CC, P.rp);
+    char* D = P.D = AR->buf.as<char>();
+    const auto drop = [&](int rc) { sync_all(ctx); arena_put(AR); for (uint32_t c = 0; c < n; ++c) out[c] = nullptr; return give_up(rc); };
+    P.ucd.resize(n); P.ust.resize(n); P.so_dev.assign(n, nullptr);
+    std::vector<uint32_t*> sop(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        fl::UploadContig& u = P.ucd[i];
+        arena_contig(AL, D, P.rp, P.cp, i, u);
+        u.allele = nullptr; u.qual = nullptr;                   // (the raw bytes of an upload do not exist here: FILL writes the resident form)
+        P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
+        if (any_so && u.n_reads) { sop[i] = (uint32_t*)(D + AL.o_so + 4 * P.cp[i]); P.so_dev[i] = sop[i]; }
+    }
+    a.out = C.at<const fl::UploadContig>(s_uc); a.out_prefix = C.at<const uint64_t>(s_op); a.old_read = C.at<const uint32_t>(s_or); a.status = C.at<fl::UploadStatus>(s_st);
+    a.Rq1 = ctx->d_hash.as<uint64_t>(); a.Rq2 = ctx->d_hash.as<uint64_t>() + 2ull * ctx->hash_len;
+    a.out_set_order = C.at<uint32_t* const>(s_sop); a.ord = ctx->cur_ord; a.n_reads_out = R;
+    hipError_t e = hipSuccess;
+    t = T.begin(K_H2D);
+    e = C.up(s_uc, P.ucd.data(), sizeof(fl::UploadContig) * n, ctx->stream);
+    if (e == hipSuccess) e = C.up(s_op, P.rp.data(), 8ull * (n + 1), ctx->stream);
+    if (e == hipSuccess) e = C.up(s_or, old_read.data(), 4 * R, ctx->stream);
+    if (e == hipSuccess) e = C.up(s_st, P.ust.data(), sizeof(fl::UploadStatus) * n, ctx->stream);
+    if (e == hipSuccess) e = C.up(s_sop, sop.data(), 8ull * n, ctx->stream);
+    if (e == hipSuccess && R) e = hipMemcpyAsync(D + AL.o_ro, ro_all.data(), 4 * ro_all.size(), hipMemcpyHostToDevice, ctx->stream);
+    T.end(t);
+    if (e == hipSuccess && R) {
+        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((R + 3) / 4, (uint64_t)ctx->n_cu * 8));      // one wavefront per output read, grid-stride beyond 8 workgroups per CU
+        t = T.begin(K_FILL);
+        hipLaunchKernelGGL(fl::mono_filter_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        T.end(t);
+        if (any_so) { t = T.begin(K_ORDER); hipLaunchKernelGGL(fl::mono_order_kernel, dim3(grid), dim3(256), 0, ctx->stream, a); T.end(t); }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        t = T.begin(K_D2H);
+        e = hipMemcpyAsync(P.ust.data(), C.at(s_st), sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && res) {
+            if (!new_result(R, S)) { T.end(t); return drop(fail(FLORIA_E_NOMEM, "calloc")); }
+            if (S) e = hipMemcpyAsync(M->removed, C.at(s_rm), S, hipMemcpyDeviceToHost, ctx->stream);
+        }
+        T.end(t);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return drop(fail(e == hipErrorOutOfMemory ? FLORIA_E_NOMEM : FLORIA_E_DEVICE, std::string("drop_monomorphic: ") + hipGetErrorString(e)));
+    if (M) {
+        memcpy(M->read_off, P.rp.data(), 8ull * (n + 1));
+        if (R) memcpy(M->old_read, old_read.data(), 4 * R);
+        for (uint32_t c = 0; c < n; ++c) M->n_removed_snps += n_rm[c];
+        M->n_removed_cells = cpi[n] - kept_cells; M->n_dropped_reads = Rin - R;
+    }
+    if (int rc = finish_upload(ctx, P, out)) return drop(rc);
+    ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.total_ms = T.span();
+    const int kinds[6] = {K_CLEAR, K_COUNT, K_DECIDE, K_FCOUNT, K_FILL, K_ORDER};
+    for (int k = 0; k < 6; ++k) { ctx->mono_ms[k] = T.sum(kinds[k]); ctx->timing.pileup_ms += ctx->mono_ms[k]; }
+    if (res) *res = M;
     return 0;
 }
 

@@ -30,6 +30,7 @@ SYMBOLS = [
     "floria_hip_contig_download", "floria_hip_phase_pileups_batch",
     "floria_hip_pileup_records", "floria_hip_record_cells_free", "floria_hip_pileup_records_realign",
     "floria_hip_pileup_records_resident", "floria_hip_record_summary_free", "floria_hip_assemble_contigs", "floria_hip_haploset_alleles",
+    "floria_hip_drop_monomorphic", "floria_hip_mono_result_free", "floria_hip_mono_timing",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -62,7 +63,7 @@ def load():
         L.floria_hip_last_error.restype = C.c_char_p
         L.floria_hip_version.restype = C.c_char_p
         for s in ("floria_hip_destroy", "floria_hip_ranges_free", "floria_hip_contig_free", "floria_hip_block_result_free", "floria_hip_groups_free",
-                  "floria_hip_groups_array_free", "floria_hip_hap_graph_free", "floria_hip_record_cells_free", "floria_hip_record_summary_free"):
+                  "floria_hip_groups_array_free", "floria_hip_hap_graph_free", "floria_hip_record_cells_free", "floria_hip_record_summary_free", "floria_hip_mono_result_free"):
             getattr(L, s).restype = None
         L.floria_hip_destroy.argtypes = [C.c_void_p]
         L.floria_hip_contig_free.argtypes = [C.c_void_p]
@@ -85,6 +86,9 @@ def load():
                                                          C.POINTER(C.POINTER(capi.CRecordSummary))]
         L.floria_hip_record_summary_free.argtypes = [C.POINTER(capi.CRecordSummary)]
         L.floria_hip_assemble_contigs.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(C.c_void_p)]
+        L.floria_hip_drop_monomorphic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u64p, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(capi.CMonoResult))]
+        L.floria_hip_mono_result_free.argtypes = [C.POINTER(capi.CMonoResult)]
+        L.floria_hip_mono_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.floria_hip_haploset_alleles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u32p, C.c_uint32, capi.u64p, capi.u32p]
         _LIB = L
     return _LIB
@@ -510,6 +514,32 @@ class FloriaHip:
             raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: the record summary has been freed")
         _check(load().floria_hip_assemble_contigs(self._h, summary._p, C.byref(plan), hs))
         return [ResidentContig(self, handle=C.c_void_p(hs[i]), n_reads=int(fo[i + 1] - fo[i])) for i in range(n)]
+
+    def drop_monomorphic(self, contigs, snp_counts, error, with_set_order=False):
+        """floria_hip_drop_monomorphic: remove_monomorphic_allele (utils_frags.rs:713-772) on resident contigs (a list of ResidentContigs or a ContigBatch) whose
+        SNP counts are snp_counts -> (ContigBatch of the filtered contigs, dict(read_off uint64 [n + 1], old_read uint32, removed uint8 [sum of snp_counts],
+        n_removed_snps, n_removed_cells, n_dropped_reads)).  The inputs stay as they are."""
+        n = len(contigs)
+        arr = contigs._arr if isinstance(contigs, ContigBatch) else (C.c_void_p * max(n, 1))(*[c._h for c in contigs])
+        if len(np.atleast_1d(snp_counts)) != n:
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "drop_monomorphic: one SNP count per contig")
+        so = np.zeros(n + 1, np.uint64)
+        so[1:] = np.cumsum(np.asarray(snp_counts, np.uint64), dtype=np.uint64)
+        hs = (C.c_void_p * max(n, 1))()
+        out = C.POINTER(capi.CMonoResult)()
+        _check(load().floria_hip_drop_monomorphic(self._h, arr, C.c_uint32(n), capi.ptr(so, C.c_uint64), C.c_double(error), C.c_int(1 if with_set_order else 0), hs, C.byref(out)))
+        r = out.contents
+        read_off = capi.np_from(r.read_off, n + 1, np.uint64)
+        result = dict(read_off=read_off, old_read=capi.np_from(r.old_read, int(read_off[-1]), np.uint32), removed=capi.np_from(r.removed, int(so[-1]), np.uint8),
+                      n_removed_snps=int(r.n_removed_snps), n_removed_cells=int(r.n_removed_cells), n_dropped_reads=int(r.n_dropped_reads))
+        load().floria_hip_mono_result_free(out)
+        return ContigBatch(self, hs, n), result
+
+    def mono_timing(self):
+        """floria_hip_mono_timing: the device ms of the last drop_monomorphic call by kind"""
+        ms = (C.c_double * 6)()
+        _check(load().floria_hip_mono_timing(self._h, ms))
+        return dict(zip(("clear_ms", "count_ms", "decide_ms", "filter_count_ms", "filter_fill_ms", "order_ms"), [float(x) for x in ms]))
 
     def haploset_alleles(self, contigs, grp_contig, groups, ranges):
         """floria_hip_haploset_alleles: per haploset (read-id list + inclusive SNP range, as haploset_stats takes them) the number of its reads calling each allele

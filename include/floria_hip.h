@@ -462,6 +462,46 @@ typedef struct {
  * residency stays.  floria_hip_last_timing then reports pileup_ms (merge passes + scan), select_ms (flatten), h2d_ms, d2h_ms, total_ms. */
 int  floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary* resident, const floria_fragment_plan* plan, floria_hip_contig** out /* [n_contigs] */);
 
+/* ---- remove_monomorphic_allele (utils_frags.rs:713-772, --ignore-monomorphic; called at floria.rs:315-317) on resident contigs: no cell crosses the link ------------
+ * contigs[0..n_contigs) are resident contigs of this context from any source (single uploads, an upload batch, floria_hip_assemble_contigs; they need not share an
+ * arena); snp_off is the prefix sum of their SNP counts (contig c has SNPs 1 .. snp_off[c+1] - snp_off[c]).  Literal to the reference:
+ *   counts    per SNP and allele 0..3 the sum of the cells' weights — the Q24 field of CELL_AW, i.e. phred_scale (utils_frags.rs:702-711) as an exact integer, so
+ *             the sum is exact and order-free — and whether any cell calls the allele at all: a q = 0 cell weighs 0 but still makes its allele a key of the
+ *             reference's map;
+ *   decision  no allele present: the SNP stays (it is not in the map); exactly one: removed; otherwise, with v0 >= v1 the two largest sums as f64
+ *             ((double)S * 2^-24, exact below 2^53), removed iff v0 * error > v1, strictly, in f64: equality keeps the SNP;
+ *   reads     a read keeps its cells at surviving SNPs, in order, CELL_AW unchanged; first / last become its first / last surviving SNP; a read left without cells
+ *             is dropped; the survivors are ordered by (new first ascending, new last descending, old read index ascending) — Frag::cmp with the old counter_id —
+ *             and renumbered.
+ * out[0..n_contigs) receive the output contigs: ONE new batch arena laid out as an upload's, every floria_hip_contig_download field (TW and META recomputed from
+ * the surviving cells) byte for byte what floria_hip_contig_upload_batch produces for the equivalent filtered pileups, the derived properties (cells, longest read,
+ * biallelic / q = 0 routing: "some surviving weight is 0") the same; each is freed with floria_hip_contig_free.  A contig that loses every read, or had none, yields
+ * a handle with n_reads == 0.  The inputs are not touched and stay the caller's.
+ * with_set_order != 0: every output contig carries a set_order (floria_pileup::set_order): per read the input read's iteration order — the host-given one where the
+ * input contig has a set_order, else the one the library emulates for a one-walk set (csrc/arith_kernel.h) — with the removed cells deleted and the remaining
+ * indices renumbered, which is what the reference's set holds (`remove` moves no other key, utils_frags.rs:745-755).  A host-given input order that is no
+ * permutation is FLORIA_E_INVALID with S1's message.  with_set_order == 0: the outputs carry none, and "arith" = 1 on them then emulates a one-walk set of the
+ * CUT-DOWN cells, which is NOT the reference's function for a read that lost cells (its set keeps the layout it had with the removed keys in it).
+ * res (may be NULL) receives the library-owned map back to the inputs (floria_hip_mono_result_free).
+ * Refused before any launch, FLORIA_E_INVALID each: a null argument; a contig of another context; snp_off not starting at 0 or descending; a non-finite error; a
+ * contig with a read whose `last` exceeds its SNP count (the message names the contig).  On error no handle is returned.
+ * floria_hip_last_timing then reports pileup_ms (all device work of the call: see floria_hip_mono_timing), h2d_ms, d2h_ms, total_ms. */
+typedef struct {
+    uint32_t  n_contigs;
+    uint64_t* read_off;     /* [n_contigs+1] reads of output contig c are old_read[read_off[c] .. read_off[c+1])            */
+    uint32_t* old_read;     /* [read_off[n]] output read r of contig c was input read old_read[read_off[c]+r] of contig c   */
+    uint8_t*  removed;      /* [snp_off[n]]  removed[snp_off[c] + s-1] = 1 iff SNP s (1-based) of contig c was removed      */
+    uint64_t  n_removed_snps, n_removed_cells, n_dropped_reads;
+} floria_mono_result;
+int  floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                                 const uint64_t* snp_off /* [n_contigs+1], prefix sums of the contigs' SNP counts */,
+                                 double error, int with_set_order,
+                                 floria_hip_contig** out /* [n_contigs] */, floria_mono_result** res /* may be NULL */);
+void floria_hip_mono_result_free(floria_mono_result* r);
+/* pileup_ms of the context's last floria_hip_drop_monomorphic call by kind, in ms (hipEvents): ms6[0] clearing the tables, [1] the count pass, [2] the decision,
+ * [3] filter COUNT, [4] filter FILL, [5] the set orders (the input orders through S1's kernels + their filtering; 0 without with_set_order). */
+int  floria_hip_mono_timing(const floria_hip_ctx* ctx, double* ms6);
+
 /* Allele tables of haplosets for a host that holds no cells (the allele strings of .vartigs / vartig_info.txt): the groups are given as for
  * floria_hip_haploset_stats; counts[4 * (pos_off[g] + (p - lo_g)) + a] = the number of group g's reads that call allele a at SNP p of its inclusive range
  * [lo_g, hi_g] — set_to_seq_dict(.., false) restricted to the range, what write_fragset_haplotypes (file_writer.rs:308-369) iterates.  pos_off [n_groups+1] is the
