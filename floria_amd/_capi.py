@@ -8,6 +8,7 @@ FLORIA_E_INVALID = -1
 FLORIA_E_DEVICE = -2
 FLORIA_E_NOMEM = -3
 FLORIA_E_UNSUPPORTED = -4
+FLORIA_FIELD_SET_ORDER = 7      # floria_hip_contig_download: uint32 [n_cells] of a contig that carries a set_order
 FLORIA_MAX_ALLELES = 4
 FLORIA_MAX_PLOIDY = 16
 

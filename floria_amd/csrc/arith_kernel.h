@@ -98,6 +98,35 @@ struct FxTable {
         if (growth_left == 0) reserve(1, spare_c, spare_s);
         put(key);
     }
+    // RawTable::find: the bucket that holds `key`, ~0u if no bucket does.  Group after group along the probe sequence: a control byte equal to the key's tag whose
+    // bucket holds the key is a hit, a group with an EMPTY byte ends the search (nothing is ever removed: no DELETED bytes).  At most one step per group of the table.
+    __device__ uint32_t find(uint32_t key) const {
+        if (buckets == 0) return ~0u;
+        const uint64_t h = hash_of(key);
+        const uint32_t h2 = (uint32_t)(h >> 57), mask = buckets - 1;
+        uint32_t pos = (uint32_t)h & mask, stride = 0;
+        for (uint32_t step = 0; step < (buckets < FX_W ? 1u : buckets / FX_W); ++step) {
+            uint32_t free_bits = 0, tag_bits = 0;
+#pragma unroll
+            for (uint32_t x = 0; x < FX_W; ++x) { const uint32_t c = ctrl[pos + x]; free_bits |= (c >> 7) << x; tag_bits |= (uint32_t)(c == h2) << x; }
+            while (tag_bits) {
+                const uint32_t idx = (pos + (uint32_t)__builtin_ctz(tag_bits)) & mask;      // (a hit in the mirrored tail of a small table is its bucket in group 0)
+                tag_bits &= tag_bits - 1;
+                if (slot[idx] == key) return idx;
+            }
+            if (free_bits) return ~0u;
+            stride += FX_W; pos = (pos + stride) & mask;
+        }
+        return ~0u;
+    }
+    // HashSet::insert (find_or_find_insert_slot): room for one key is reserved BEFORE the key is looked up, so a key the table already holds can still grow a
+    // full table.  -> true if the key is new.  The table must be bound (an unallocated set is bound by its first reserve).
+    __device__ bool insert(uint32_t key, uint8_t*& spare_c, uint32_t*& spare_s) {
+        reserve(1, spare_c, spare_s);
+        if (find(key) != ~0u) return false;
+        put(key);
+        return true;
+    }
 };
 
 // The same table driven by a whole WAVEFRONT (every argument and member is wave-uniform; all 64 lanes must call): a probe group's 16 control bytes are
@@ -173,6 +202,32 @@ struct FxWave {
     __device__ void insert_new(uint32_t key, uint8_t*& spare_c, uint32_t*& spare_s, uint32_t lane) {
         if (growth_left == 0) reserve(1, spare_c, spare_s, lane);
         put(key, lane);
+    }
+    // FxTable::find by the wavefront: lane x < 16 compares control byte x of the group with the key's tag and, where they match, the bucket's key; one ballot for
+    // the hit, one for the EMPTY byte that ends the search.  At most one step per group of the table.
+    __device__ uint32_t find(uint32_t key, uint32_t lane) const {
+        if (buckets == 0) return ~0u;
+        const uint64_t h = FxTable::hash_of(key);
+        const uint32_t h2 = (uint32_t)(h >> 57), mask = buckets - 1;
+        uint32_t pos = (uint32_t)h & mask, stride = 0;
+        for (uint32_t step = 0; step < (buckets < FX_W ? 1u : buckets / FX_W); ++step) {
+            const bool in = lane < FX_W;
+            const uint32_t c = in ? ctrl[pos + lane] : 0xffu;
+            const bool hit = in && c == h2 && slot[(pos + lane) & mask] == key;
+            const uint64_t hm = __ballot(hit);
+            if (hm) return (pos + (uint32_t)__builtin_ctzll(hm)) & mask;
+            if (__ballot(in && (c & 0x80u) != 0u)) return ~0u;
+            stride += FX_W; pos = (pos + stride) & mask;
+        }
+        return ~0u;
+    }
+    // FxTable::insert by the wavefront (reserve(1), the lookup, put)
+    __device__ bool insert(uint32_t key, uint8_t*& spare_c, uint32_t*& spare_s, uint32_t lane) {
+        reserve(1, spare_c, spare_s, lane);
+        if (find(key, lane) != ~0u) return false;
+        put(key, lane);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // (lane 0 stored; the next probe's loads are other lanes')
+        return true;
     }
 
     // ---- many insertions per round (control bytes in LDS, tables of at least one full group) -------------------------------------------------

@@ -45,6 +45,7 @@
 #include "realign_gather_kernel.h"
 #include "upload_kernel.h"
 #include "assemble_kernel.h"
+#include "assemble_order_kernel.h"
 #include "mono_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
@@ -186,6 +187,7 @@ struct Knobs {
     uint32_t no_bulk = 0;         // (tests) beam_slab_kernel: every step through the general insert path (entry table, duplicate test, evictions)
     uint32_t fx_tags = 0;         // (A/B) reference arithmetic: cap on the words of a position map's claim table (0 = as many as cost no workgroup per CU)
     uint32_t arith_ow6 = 0;       // (A/B) ... the optimise kernel compiled for six waves per SIMD at every ploidy
+    uint32_t asm_order_general = 0;      // (tests) floria_hip_assemble_contigs_ordered: every fragment's set order through the general kernel (assemble_order_kernel.h)
     uint32_t arith_replay = 0;    // (tests) reference arithmetic: replay every position map insertion by insertion (the home-bucket rule of optimize_kernel.h off)
     uint32_t arith_hbm = 0;       // (tests) reference arithmetic: position-map tables and first-insertion keys in HBM scratch even where they fit into LDS
     uint32_t opt_block_order = 0; // (A/B, tests) optimise: the build / distance passes visit the reads in block order instead of longest first
@@ -256,6 +258,7 @@ struct floria_hip_ctx {
     std::vector<uint32_t> res_contig;         // contig of every record (header-sized; the plan is validated against it)
     const uint64_t* res_cell_off = nullptr; const uint32_t* res_snp = nullptr; const uint8_t *res_allele = nullptr, *res_qual = nullptr;
     DevBuf asm_plan;                          // floria_hip_assemble_contigs: the fragment plan and the per-fragment cell counts / offsets
+    DevBuf asm_ord_scr;                       // floria_hip_assemble_contigs_ordered: the general kernel's tables
     double mono_ms[6] = {};                   // the last floria_hip_drop_monomorphic call's device time by kind (floria_hip_mono_timing)
     DevBuf mono_buf;                          // floria_hip_drop_monomorphic: the per-SNP tables, the per-read survivor words and the call's small tables
     uint32_t stage_threads = 8;
@@ -983,7 +986,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->mono_buf}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -1030,6 +1033,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "tail_waves") K.tail_waves = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 16));
     else if (k == "arith_hbm") K.arith_hbm = value != 0;
     else if (k == "arith_replay") { K.arith_replay = value != 0; ctx->ord_epoch = ~0ull; }      // (the cell orders are computed again, the long way or the short one)
+    else if (k == "asm_order_general") K.asm_order_general = value != 0;
     else if (k == "fx_tags") { if (value != 0 && (value < (int64_t)fl::FX_TAGS_MIN || value > (int64_t)fl::FX_TAGS_MAX || (value & (value - 1)))) return fail(FLORIA_E_INVALID, "fx_tags: 0 | a power of two in 128..1024"); K.fx_tags = (uint32_t)value; }
     else if (k == "arith_ow6") K.arith_ow6 = value != 0;
     else if (k == "s2_assign_only") K.s2_assign_only = value != 0;
@@ -1508,6 +1512,9 @@ int floria_hip_contig_download(const floria_hip_contig* c, int field, void* dst,
         case FLORIA_FIELD_CELL_AW:  src = c->dev.cell_aw;  have = 4ull * c->n_cells; break;
         case FLORIA_FIELD_TW:       src = c->dev.tw;       have = 16ull * c->n_reads; break;
         case FLORIA_FIELD_META:     src = c->dev.meta;     have = 32ull * c->n_reads; break;
+        case FLORIA_FIELD_SET_ORDER:
+            if (!c->dev.set_order) return fail(FLORIA_E_INVALID, "the contig carries no set_order");
+            src = c->dev.set_order; have = 4ull * c->n_cells; break;
         default: return fail(FLORIA_E_INVALID, "unknown field");
     }
     if (bytes > have) return fail(FLORIA_E_INVALID, "field is smaller than the requested size");
@@ -2687,10 +2694,12 @@ void floria_hip_record_summary_free(floria_record_summary* s) {
     g_big.put(s->cell_off); g_big.put(s->first_snp); g_big.put(s->last_snp); g_big.put(s->ref_end); free(s);
 }
 
-int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out) {
+// `ordered`: floria_hip_assemble_contigs_ordered — the contigs that hold a merged fragment get their set_order from the device (assemble_order_kernel.h)
+static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out, bool ordered) {
     if (!ctx || !Y || !plan || !out || !plan->frag_off) return fail(FLORIA_E_INVALID, "null argument");
     const uint32_t nc = plan->n_contigs;
     for (uint32_t c = 0; c < nc; ++c) out[c] = nullptr;
+    if (ordered && plan->set_order) return fail(FLORIA_E_INVALID, "assemble: the plan gives a set_order and the call is asked to derive it (give the order or ask for it, not both)");
     if (!ctx->res_token || Y != ctx->res_summary || Y->token != ctx->res_token)
         return fail(FLORIA_E_INVALID, "assemble: the record summary is not the context's live residency (a later floria_hip_pileup_records* call has replaced its cells)");
     if (nc != ctx->res_n_contigs) return fail(FLORIA_E_INVALID, "assemble: the plan has " + std::to_string(nc) + " contigs, the resident pileup's SNP table has " + std::to_string(ctx->res_n_contigs));
@@ -2707,6 +2716,8 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     if (NF && (!plan->part_off || !plan->part_rec)) return fail(FLORIA_E_INVALID, "null argument");
     if (NF && plan->part_off[0] != 0) return fail(FLORIA_E_INVALID, "assemble: part_off does not start at 0");
     std::vector<uint32_t> frag_ctg((size_t)NF);
+    std::vector<uint32_t> merged(ordered ? nc : 0, 0);      // ordered: != 0 for a contig with a fragment of two or more parts that have cells
+    std::vector<uint64_t> part_cells(ordered ? (size_t)NF : 0);      // ... and the cells of every fragment's parts together
     for (uint32_t c = 0; c < nc; ++c)
         for (uint64_t f = plan->frag_off[c]; f < plan->frag_off[c + 1]; ++f) {
             frag_ctg[f] = c;
@@ -2715,15 +2726,29 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
             if (p1 < p0) return fail(FLORIA_E_INVALID, "assemble: part_off decreases at " + where());
             if (p1 == p0) return fail(FLORIA_E_INVALID, "assemble: " + where() + " has no part");
             bool any = false;
+            uint64_t with = 0, sum = 0;
             for (uint64_t p = p0; p < p1; ++p) {
                 const uint32_t rec = plan->part_rec[p];
                 if (rec >= n_rec) return fail(FLORIA_E_INVALID, "assemble: " + where() + " names record " + std::to_string(rec) + " of " + std::to_string(n_rec));
                 if (ctx->res_contig[rec] != c) return fail(FLORIA_E_INVALID, "assemble: record " + std::to_string(rec) + " lies on contig " + std::to_string(ctx->res_contig[rec]) + ", " + where() + " does not");
                 any = any || Y->cell_off[rec + 1] > Y->cell_off[rec];
+                if (Y->cell_off[rec + 1] > Y->cell_off[rec]) { ++with; sum += Y->cell_off[rec + 1] - Y->cell_off[rec]; }
             }
+            if (ordered) { part_cells[f] = sum; if (with >= 2) merged[c] = 1; }
             if (!any) return fail(FLORIA_E_INVALID, "assemble: the parts of " + where() + " have no cell (every read has >= 1 cell)");
         }
     const uint64_t NP = NF ? plan->part_off[NF] : 0;
+    // ordered: what the general kernel may meet — the fragments beyond the wavefront kernel's tables and the largest of them (the scratch is sized before any launch)
+    bool any_merged = false;
+    uint64_t n_general = 0, cells_max = 0;
+    if (ordered)
+        for (uint32_t c = 0; c < nc; ++c) {
+            if (!merged[c]) continue;
+            any_merged = true;
+            for (uint64_t f = plan->frag_off[c]; f < plan->frag_off[c + 1]; ++f)
+                if (part_cells[f] > fl::AO_FAST_CELLS || ctx->knobs.asm_order_general) { ++n_general; cells_max = std::max(cells_max, part_cells[f]); }
+        }
+    if (cells_max >= (1ull << 31)) return fail(FLORIA_E_UNSUPPORTED, "assemble: a fragment whose parts have 2^31 and more cells");
     HIPCHK(hipSetDevice(ctx->device));
     const uint32_t n = nc, nf32 = (uint32_t)NF;
     const uint32_t n_tiles = (nf32 + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
@@ -2731,7 +2756,17 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     Carve C;
     const Seg s_po = C.seg(8 * (NF + 1)), s_pr = C.seg(4 * NP + 4), s_fc = C.seg(4 * NF + 4), s_fo = C.seg(8ull * (n + 1)), s_cnt = C.seg(8 * (NF + 1)), s_tile = C.seg(8ull * n_tiles + 8),
               s_tot = C.seg(8ull * (n + 1)), s_cdev = C.seg(sizeof(fl::ContigDev) * n);
+    const Seg s_mg = C.seg(any_merged ? 4ull * n : 0), s_todo = C.seg(any_merged ? 8 * (NF + 1) : 0);
     if (int rc = C.place(ctx->asm_plan)) return rc;
+    fl::AsmOrderArgs oa{};
+    if (n_general) {
+        oa.cells_max = (uint32_t)cells_max; oa.ctrl_bytes = fl::fx_ctrl_bytes(oa.cells_max + 1); oa.slot_bytes = fl::fx_slot_bytes(oa.cells_max + 1);
+        const uint64_t per = fl::AO_TABLES * (oa.ctrl_bytes + oa.slot_bytes);      // a thread's five tables; as many threads as 2 GiB hold, one at the least
+        oa.n_threads = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(n_general, 65536), (2ull << 30) / per));
+        oa.scratch_bytes = per * oa.n_threads;
+        if (int rc = ctx->asm_ord_scr.ensure(oa.scratch_bytes)) return rc;
+        oa.scratch = ctx->asm_ord_scr.as<uint8_t>();
+    }
     EventTimer T(ctx->stream);
     ctx->timing = floria_timing{};
     fl::AssembleArgs a{};
@@ -2771,7 +2806,8 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     for (uint32_t i = 0; i < n; ++i) P.rp[i + 1] = plan->frag_off[i + 1];
     const uint64_t R = P.R = NF, CC = P.C = cp[n];
     P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
-    const bool any_so = plan->set_order != nullptr && CC != 0;
+    const bool derive_so = any_merged && CC != 0;
+    const bool any_so = (plan->set_order != nullptr && CC != 0) || derive_so;
     const ArenaLayout AL = layout_arena(R, CC, n, any_so);
     const size_t o_ro = AL.o_ro, o_first = AL.o_first, o_last = AL.o_last, o_snp = AL.o_snp, o_so = AL.o_so;
     Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
@@ -2791,7 +2827,7 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
         arena_contig(AL, D, P.rp, cp, i, u);
         u.allele = (const uint8_t*)(TT + t_al + cp[i]); u.qual = (const uint8_t*)(TT + t_q + cp[i]);
         P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
-        if (any_so && u.n_reads) P.so_dev[i] = (const uint32_t*)(D + o_so + 4 * cp[i]);
+        if (any_so && u.n_reads && (!derive_so || merged[i])) P.so_dev[i] = (const uint32_t*)(D + o_so + 4 * cp[i]);
     }
     // ---- FILL writes the raw CSR arrays where an upload's DMA would have put them; then the upload's own validate + flatten launch ----
     a.read_off = (uint32_t*)(D + o_ro); a.first = (uint32_t*)(D + o_first); a.last = (uint32_t*)(D + o_last);
@@ -2800,13 +2836,31 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     int rc = 0;
     hipError_t e = hipSuccess;
     t = T.begin(K_H2D);
-    if (any_so) { std::vector<CopyRun> runs{{(const char*)plan->set_order, D + o_so, (size_t)(4 * CC)}}; rc = issue_copies(ctx, runs, &pinned_b, &staged_b); }
-    if (!rc) e = issue_tables(ctx, P, ctx->stream);
+    if (any_so && !derive_so) { std::vector<CopyRun> runs{{(const char*)plan->set_order, D + o_so, (size_t)(4 * CC)}}; rc = issue_copies(ctx, runs, &pinned_b, &staged_b); }
+    if (!rc && derive_so) e = C.up(s_mg, merged.data(), 4ull * n, ctx->stream);
+    if (!rc && e == hipSuccess) e = issue_tables(ctx, P, ctx->stream);
     T.end(t);
     if (!rc && e == hipSuccess && NF) {
         t = T.begin(K_PILEUP);
         hipLaunchKernelGGL(fl::assemble_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
         e = hipGetLastError();
+        if (e == hipSuccess && derive_so) {
+            // the set orders of the merged contigs' fragments, where an uploaded set_order would lie.  Preset to all ones: whatever the kernels leave unwritten
+            // is no permutation, and the cell orders below refuse it.
+            oa.cell_off = a.cell_off; oa.snp = a.snp; oa.part_off = a.part_off; oa.part_rec = a.part_rec; oa.frag_ctg = a.frag_ctg; oa.frag_cells = a.frag_cells;
+            oa.merged_snp = a.out_snp; oa.ctg_merged = C.at<const uint32_t>(s_mg); oa.set_order = (uint32_t*)(D + o_so); oa.todo = C.at<uint64_t>(s_todo);
+            oa.n_frags = NF; oa.n_parts = NP; oa.total_cells = CC; oa.n_records = n_rec; oa.n_contigs = n; oa.force_general = ctx->knobs.asm_order_general;
+            e = hipMemsetAsync(D + o_so, 0xff, 4 * CC, ctx->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(oa.todo, 0, 8, ctx->stream);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(fl::assemble_order_kernel, dim3(grid), dim3(256), 0, ctx->stream, oa);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess && n_general) {
+                hipLaunchKernelGGL(fl::assemble_order_general_kernel, dim3((oa.n_threads + 63) / 64), dim3(64), 0, ctx->stream, oa);
+                e = hipGetLastError();
+            }
+        }
         T.end(t);
     }
     if (!rc && e == hipSuccess) { const int tk = T.begin(K_SEL); e = launch_flatten(ctx, P, 0, ctx->stream); T.end(tk); }
@@ -2826,6 +2880,14 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
     ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.select_ms = T.sum(K_SEL); ctx->timing.total_ms = T.span();
     ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
     return 0;
+}
+
+int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out) {
+    return assemble_impl(ctx, Y, plan, out, false);
+}
+
+int floria_hip_assemble_contigs_ordered(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out) {
+    return assemble_impl(ctx, Y, plan, out, true);
 }
 
 // ---- remove_monomorphic_allele (utils_frags.rs:713-772) on resident contigs (mono_kernel.h) ----------------------------------------------------------------------

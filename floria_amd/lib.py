@@ -29,7 +29,7 @@ SYMBOLS = [
     "floria_hip_contig_upload_batch", "floria_hip_host_alloc", "floria_hip_host_free", "floria_hip_set_option",
     "floria_hip_contig_download", "floria_hip_phase_pileups_batch",
     "floria_hip_pileup_records", "floria_hip_record_cells_free", "floria_hip_pileup_records_realign",
-    "floria_hip_pileup_records_resident", "floria_hip_record_summary_free", "floria_hip_assemble_contigs", "floria_hip_haploset_alleles",
+    "floria_hip_pileup_records_resident", "floria_hip_record_summary_free", "floria_hip_assemble_contigs", "floria_hip_assemble_contigs_ordered", "floria_hip_haploset_alleles",
     "floria_hip_drop_monomorphic", "floria_hip_mono_result_free", "floria_hip_mono_timing",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
@@ -86,6 +86,7 @@ def load():
                                                          C.POINTER(C.POINTER(capi.CRecordSummary))]
         L.floria_hip_record_summary_free.argtypes = [C.POINTER(capi.CRecordSummary)]
         L.floria_hip_assemble_contigs.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(C.c_void_p)]
+        L.floria_hip_assemble_contigs_ordered.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(C.c_void_p)]
         L.floria_hip_drop_monomorphic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u64p, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(capi.CMonoResult))]
         L.floria_hip_mono_result_free.argtypes = [C.POINTER(capi.CMonoResult)]
         L.floria_hip_mono_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -222,7 +223,7 @@ class ResidentContig:
         self._h = h
 
     FIELDS = {"read_off": (0, np.uint32), "first": (1, np.uint32), "last": (2, np.uint32), "snp": (3, np.uint32),
-              "cell_aw": (4, np.uint32), "tw": (5, np.uint64), "meta": (6, np.uint32)}
+              "cell_aw": (4, np.uint32), "tw": (5, np.uint64), "meta": (6, np.uint32), "set_order": (7, np.uint32)}
 
     def download(self, field, count):
         """Diagnostic (floria_hip_contig_download): `count` elements of a resident array."""
@@ -500,7 +501,12 @@ class FloriaHip:
         return self._pileup_records(blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles,
                                     refs=None if ref_off is None else (ref_off, ref_seq), walk=walk, resident=True)
 
-    def assemble_contigs(self, summary, frag_off, part_off, part_rec, set_order=None):
+    def assemble_contigs_ordered(self, summary, frag_off, part_off, part_rec):
+        """floria_hip_assemble_contigs_ordered: assemble_contigs() whose merged contigs (a fragment with two or more parts that have cells) carry the set_order
+        the reference's containers give their reads, derived on the device (download field "set_order"); the other contigs carry none."""
+        return self.assemble_contigs(summary, frag_off, part_off, part_rec, _ordered=True)
+
+    def assemble_contigs(self, summary, frag_off, part_off, part_rec, set_order=None, _ordered=False):
         """floria_hip_assemble_contigs: the fragment plan (frag_off uint64 [n_contigs + 1], part_off uint64 [n_frags + 1], part_rec uint32 record indices in merge
         order, optional set_order uint32 over the merged cells of all contigs) -> one ResidentContig per contig, usable wherever uploaded ones are."""
         fo = np.ascontiguousarray(frag_off, np.uint64); po = np.ascontiguousarray(part_off, np.uint64); pr = np.ascontiguousarray(part_rec, np.uint32)
@@ -512,7 +518,7 @@ class FloriaHip:
         hs = (C.c_void_p * max(n, 1))()
         if summary._p is None:
             raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: the record summary has been freed")
-        _check(load().floria_hip_assemble_contigs(self._h, summary._p, C.byref(plan), hs))
+        _check((load().floria_hip_assemble_contigs_ordered if _ordered else load().floria_hip_assemble_contigs)(self._h, summary._p, C.byref(plan), hs))
         return [ResidentContig(self, handle=C.c_void_p(hs[i]), n_reads=int(fo[i + 1] - fo[i])) for i in range(n)]
 
     def drop_monomorphic(self, contigs, snp_counts, error, with_set_order=False):

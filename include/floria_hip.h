@@ -219,6 +219,7 @@ int  floria_hip_contig_upload_batch(floria_hip_ctx* ctx, const floria_pileup* pi
 #define FLORIA_FIELD_CELL_AW  4
 #define FLORIA_FIELD_TW       5
 #define FLORIA_FIELD_META     6
+#define FLORIA_FIELD_SET_ORDER 7   /* uint32 [n_cells], only of a contig that carries a set_order (FLORIA_E_INVALID "the contig carries no set_order" otherwise) */
 int  floria_hip_contig_download(const floria_hip_contig* c, int field, void* dst, size_t bytes);
 
 /* Pinned host memory for pileup arrays (NULL on failure). */
@@ -462,6 +463,23 @@ typedef struct {
  * residency stays.  floria_hip_last_timing then reports pileup_ms (merge passes + scan), select_ms (flatten), h2d_ms, d2h_ms, total_ms. */
 int  floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary* resident, const floria_fragment_plan* plan, floria_hip_contig** out /* [n_contigs] */);
 
+/* floria_hip_assemble_contigs whose set orders come from the device: the same validation, kernels, arena and handles, and in addition every contig that is MERGED —
+ * that holds at least one fragment with two or more parts that have cells, which a host can tell from the summary's cell_off — carries a set_order
+ * (floria_pileup::set_order) computed for every one of its reads as the reference's containers build Frag.positions (csrc/assemble_order_kernel.h):
+ *   - each part's own set: an empty map receives the part's SNPs ascending, growing as it goes; an empty set reserves room for all of them and receives the map's
+ *     keys in bucket order; a part without cells leaves the unallocated empty set;
+ *   - the accumulator starts as the first part's set; for every later part reserve(accumulator empty ? n : (n + 1) / 2), then insert of the part's keys in the
+ *     iteration order of the part's own set — insert reserves room for one key before it looks the key up, so a key both parts have can still grow a full table;
+ *   - set_order[read_off[r] + j] = the index within the merged read of the j-th key in the accumulator's bucket order.
+ * Contigs that are not merged carry no set_order and every download field of theirs has the bytes the plain call gives; if no contig is merged the call IS the
+ * plain call.  The derived orders lie where an uploaded set_order lies, the cell orders are computed at once as for a host-given order (their permutation check
+ * covers the derived orders too), and "arith" = 1 and floria_hip_drop_monomorphic(.., with_set_order = 1) use them as they use a host-given one.
+ * plan->set_order != NULL is FLORIA_E_INVALID before anything is launched (give the order or ask for it, not both).  Fragments whose parts have more than 223
+ * cells together take a one-thread-per-fragment kernel whose tables are sized from the summary before any launch: FLORIA_E_NOMEM if they cannot be had,
+ * FLORIA_E_UNSUPPORTED for 2^31 and more cells in the parts of one fragment.  On error no handle is returned and the residency stays.  floria_hip_last_timing
+ * counts the additional launches into pileup_ms.  (Test option "asm_order_general" = 1: every fragment takes the one-thread kernel; results do not change.) */
+int  floria_hip_assemble_contigs_ordered(floria_hip_ctx* ctx, const floria_record_summary* resident, const floria_fragment_plan* plan, floria_hip_contig** out /* [n_contigs] */);
+
 /* ---- remove_monomorphic_allele (utils_frags.rs:713-772, --ignore-monomorphic; called at floria.rs:315-317) on resident contigs: no cell crosses the link ------------
  * contigs[0..n_contigs) are resident contigs of this context from any source (single uploads, an upload batch, floria_hip_assemble_contigs; they need not share an
  * arena); snp_off is the prefix sum of their SNP counts (contig c has SNPs 1 .. snp_off[c+1] - snp_off[c]).  Literal to the reference:
@@ -552,7 +570,8 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * default 2), "beam_path" (0 auto, 1 generic, 2 slab, 3 wide), "no_specialized", "no_p1_shortcut", "opt_threads"
  * (0|128|512|1024), "opt_global", "opt_block_order" (tests / A/B: the optimise kernel's passes visit a block's reads in block order instead of longest first), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
- * insert path with its duplicate test), "hw_queues" (tests: override the number of
+ * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
+ * kernel; results do not change), "hw_queues" (tests: override the number of
  * concurrently running streams floria_hip_create measured — 6 on an MI355X whose host set GPU_MAX_HW_QUEUES=12 before HIP initialised, 4 or fewer
  * with the runtime's default; below 5 the launch plans stay within two job groups and do not speculate). */
 int  floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value);
