@@ -9,6 +9,10 @@ FLORIA_E_DEVICE = -2
 FLORIA_E_NOMEM = -3
 FLORIA_E_UNSUPPORTED = -4
 FLORIA_FIELD_SET_ORDER = 7      # floria_hip_contig_download: uint32 [n_cells] of a contig that carries a set_order
+FLORIA_FIELD_SEQ_POS = 8        # ... uint32 [n_cells], the SEQ_POS words (mate << 31 | seq_pos) of a contig that carries positions
+FLORIA_ASM_DERIVE_SET_ORDER = 1
+FLORIA_ASM_KEEP_SEQ_POS = 2
+FLORIA_SPAN_NONE = 0xFFFFFFFF
 FLORIA_MAX_ALLELES = 4
 FLORIA_MAX_PLOIDY = 16
 
@@ -101,6 +105,10 @@ class CRecordSummary(C.Structure):
 
 class CFragmentPlan(C.Structure):
     _fields_ = [("n_contigs", C.c_uint32), ("frag_off", u64p), ("part_off", u64p), ("part_rec", u32p), ("set_order", u32p)]
+
+
+class CAssembleOptions(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("part_mate", u8p)]
 
 
 class CMonoResult(C.Structure):

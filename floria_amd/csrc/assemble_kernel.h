@@ -17,6 +17,9 @@
 // of pileup_kernel.h turns the counts into exclusive offsets over ALL fragments of the batch (the arena's cell regions are the contigs' back to back, so a global
 // offset IS the cell's place), FILL writes snp / allele / qual there and the fragment's first, last and read_off entries.
 // Every index is bounded by lengths the host validated before the launch: part_rec < n_records, offsets ascending, cell_off the device's own scan.
+// With positions (the SP instance of FILL) the merged cell's SEQ_POS word goes next to its SNP: the sequence position of the cell
+// that gave the SNP its call — `snp_pos_to_seq_pos.extend` follows the rule of `seq_dict.extend`, so it is the src[] slot the merge resolves anyway — and in
+// bit 31 the mate flag of the part that cell belongs to, which rides in bit 63 of the slot (a cell index never reaches it).
 #pragma once
 #include "common.h"
 #include "wave_util.h"
@@ -43,6 +46,11 @@ struct AssembleArgs {
     uint8_t*  out_allele;
     uint8_t*  out_qual;
     uint64_t  n_frags;
+    // floria_hip_assemble_contigs_opt with KEEP_SEQ_POS (FILL only; all four null / unused otherwise): the word `mate << 31 | seq_pos` of every merged cell
+    const uint32_t* seq_pos;      // [cell_off[n_records]] pileup_walk_kernel<FILL>'s seq_pos, next to snp
+    const uint8_t*  part_mate;    // [part_off[n_frags]] 0 / 1 per part, null = all 0
+    uint32_t* out_sp;             // [frag_cells[n_frags]] the arena's seq_pos region (the SP instance only)
+    uint32_t* sp_overflow;        // one word, set to 1 when a walked seq_pos >= 2^31 was met (it cannot be encoded: the host refuses the call)
 };
 
 constexpr uint64_t ASM_NONE = ~0ull;
@@ -73,8 +81,12 @@ __device__ __forceinline__ uint64_t asm_lower_bound(const uint32_t* snp, uint64_
     return lo + (uint32_t)__popcll(__ballot(lt));
 }
 
-template <bool FILL>
+// SP: the FILL instance that also writes the SEQ_POS words.  A template parameter, not a test of out_sp at run time: with the run-time branch the plain FILL pass
+// (one-part fragments, the straight copy) measured 0.10 ms slower on the 200-contig long-read set than the kernel without the feature (profiles/read_spans.md), so
+// the plain call launches an instance whose code has no trace of it; part_mate stays a nullable pointer behind a wave-uniform branch of the SP instance.
+template <bool FILL, bool SP = false>
 __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs g) {
+    static_assert(FILL || !SP, "positions are written by the FILL pass");
     __shared__ uint64_t s_src[4][64];
     const uint32_t lane = threadIdx.x & 63, wv = uni(threadIdx.x >> 6);
     uint64_t* const src = s_src[wv];                       // slot l: 1 + the cell that gives SNP w + l its call, 0 = no part has the SNP
@@ -91,6 +103,14 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs g) {
                 for (uint64_t c = b + lane; c < e; c += 64) {
                     const uint64_t slot = out0 + (c - b);
                     g.out_snp[slot] = g.snp[c]; g.out_allele[slot] = g.allele[c]; g.out_qual[slot] = g.qual[c];
+                }
+                if (SP) {
+                    const uint32_t mate = g.part_mate ? (uint32_t)(g.part_mate[p0] & 1u) << 31 : 0u;
+                    for (uint64_t c = b + lane; c < e; c += 64) {
+                        const uint32_t sp = g.seq_pos[c];
+                        if (sp >> 31) atomicOr(g.sp_overflow, 1u);
+                        g.out_sp[out0 + (c - b)] = (sp & 0x7fffffffu) | mate;
+                    }
                 }
                 if (e > b) { lo_snp = g.snp[b]; hi_snp = g.snp[e - 1]; }
             }
@@ -114,11 +134,12 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs g) {
                     const uint32_t rec = g.part_rec[p];
                     const uint64_t b = g.cell_off[rec], e = g.cell_off[rec + 1];
                     if (e == b) continue;
+                    const uint64_t mbit = SP && g.part_mate ? (uint64_t)(g.part_mate[p] & 1u) << 63 : 0ull;      // (wave-uniform)
                     const uint64_t i0 = asm_lower_bound(g.snp, b, e, w, lane);
                     const uint64_t idx = i0 + lane;
                     const uint64_t s = idx < e ? (uint64_t)g.snp[idx] : ASM_NONE;
                     const bool in = s != ASM_NONE && s - w < 64;      // (s >= w: idx is at or behind the lower bound)
-                    if (in) src[s - w] = idx + 1;          // LDS writes of one wave land in program order: the later part wins
+                    if (in) src[s - w] = (idx + 1) | mbit; // LDS writes of one wave land in program order: the later part wins
                     else if (s < cand) cand = s;
                     if (__popcll(__ballot(in)) == 64 && i0 + 64 < e) {      // the window is full of this part: its next cell lies behind the 64 loaded ones
                         const uint64_t s2 = g.snp[i0 + 64];
@@ -128,13 +149,18 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs g) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const uint64_t sc = src[lane];
+                const uint64_t sv = src[lane], sc = SP ? sv & ~(1ull << 63) : sv;
                 const bool have = sc != 0;
                 const uint64_t m = __ballot(have);         // (bit 0 is set: w is a SNP some part has)
                 if (FILL) {
                     if (have) {
                         const uint64_t slot = out + mbcnt64(m);
                         g.out_snp[slot] = (uint32_t)(w + lane); g.out_allele[slot] = g.allele[sc - 1]; g.out_qual[slot] = g.qual[sc - 1];
+                        if (SP) {
+                            const uint32_t sp = g.seq_pos[sc - 1];
+                            if (sp >> 31) atomicOr(g.sp_overflow, 1u);
+                            g.out_sp[slot] = (sp & 0x7fffffffu) | ((uint32_t)(sv >> 63) << 31);
+                        }
                     }
                     if (first_window) lo_snp = (uint32_t)w;
                     hi_snp = (uint32_t)(w + 63 - (uint32_t)__clzll((long long)m));

@@ -47,6 +47,7 @@
 #include "assemble_kernel.h"
 #include "assemble_order_kernel.h"
 #include "mono_kernel.h"
+#include "span_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -257,10 +258,12 @@ struct floria_hip_ctx {
     uint32_t res_n_contigs = 0;
     std::vector<uint32_t> res_contig;         // contig of every record (header-sized; the plan is validated against it)
     const uint64_t* res_cell_off = nullptr; const uint32_t* res_snp = nullptr; const uint8_t *res_allele = nullptr, *res_qual = nullptr;
+    const uint32_t* res_seq_pos = nullptr;    // ... and the walked sequence positions next to them (floria_hip_assemble_contigs_opt, KEEP_SEQ_POS)
     DevBuf asm_plan;                          // floria_hip_assemble_contigs: the fragment plan and the per-fragment cell counts / offsets
     DevBuf asm_ord_scr;                       // floria_hip_assemble_contigs_ordered: the general kernel's tables
     double mono_ms[6] = {};                   // the last floria_hip_drop_monomorphic call's device time by kind (floria_hip_mono_timing)
     DevBuf mono_buf;                          // floria_hip_drop_monomorphic: the per-SNP tables, the per-read survivor words and the call's small tables
+    DevBuf span_buf;                          // floria_hip_read_spans: the groups, the contig table and the two result arrays (a buffer of its own: no residency ends)
     uint32_t stage_threads = 8;
 };
 
@@ -290,6 +293,7 @@ struct floria_hip_contig {
     bool has_q0 = false;        // some cell has qual 0 (weight 0): presence != (weight sum > 0)
     const uint32_t *h_first = nullptr, *h_last = nullptr;   // valid after host_meta(c)
     fl::ContigDev dev{};
+    const uint32_t* seq_pos = nullptr;      // [n_cells] the SEQ_POS words (include/floria_hip.h) of a contig that carries positions, else null
 };
 
 namespace {
@@ -986,7 +990,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -1163,19 +1167,22 @@ struct UploadPlan {
     std::vector<uint32_t> chunk_first;                  // [n_chunks+1] contig boundaries
     std::vector<uint32_t> contig_chunk;                 // [n]
     std::vector<const uint32_t*> so_dev;                // [n] device copy of the contig's set_order (include/floria_hip.h), null where the host gave none
+    std::vector<const uint32_t*> sp_dev;                // [n] the contig's part of the seq_pos region, null where it carries no positions (empty: none does)
     bool all_pinned = false;
 };
 
 // Where the regions of a batch arena lie, for R reads and C cells in n contigs: the ONE definition every producer of resident contigs uses (plan_upload,
 // floria_hip_assemble_contigs, floria_hip_drop_monomorphic), so that their handles cannot differ in layout.  16-B tails: the beam kernel's LDS-DMA moves cells in
-// 16-B pieces.  The set-order region exists only when some contig carries one.
-struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, bytes = 0; };
-ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so) {
+// 16-B pieces.  The set-order region exists only when some contig carries one, the seq_pos region only when some contig carries positions; it lies behind
+// every other region, so no other offset depends on it.
+struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, o_sp = 0, bytes = 0; };
+ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so, bool any_sp) {
     ArenaLayout Y;
     size_t cursor = 0;
     auto seg = [&](size_t bytes) { const size_t o = cursor; cursor += (bytes + 255) & ~(size_t)255; return o; };
     Y.o_ro = seg(4 * (R + n)); Y.o_first = seg(4 * R); Y.o_last = seg(4 * R); Y.o_snp = seg(4 * C + 16); Y.o_aw = seg(4 * C + 16); Y.o_tw = seg(16 * R); Y.o_meta = seg(32 * R);
     Y.o_so = any_so ? seg(4 * C + 16) : 0;
+    Y.o_sp = any_sp ? seg(4 * C + 16) : 0;
     Y.bytes = cursor;
     return Y;
 }
@@ -1234,7 +1241,7 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
     // ---- arena layout -------------------------------------------------------------------------------------------------------
     bool any_so = false;                                                                                // host-given set orders (optional, the reference-arithmetic mode reads them)
     for (uint32_t i = 0; i < n; ++i) any_so = any_so || (pileups[i].n_reads && pileups[i].set_order);
-    const ArenaLayout Y = layout_arena(R, C, n, any_so);
+    const ArenaLayout Y = layout_arena(R, C, n, any_so, false);      // (uploads carry no positions)
     const size_t o_ro = Y.o_ro, o_first = Y.o_first, o_last = Y.o_last, o_snp = Y.o_snp, o_so = Y.o_so;
     Arena* A = P.A = arena_get(ctx, Y.bytes + 256);
     if (!A) return FLORIA_E_NOMEM;
@@ -1362,6 +1369,7 @@ int finish_upload(floria_hip_ctx* ctx, UploadPlan& P, floria_hip_contig** out) {
         c->dev.read_off = P.ucd[i].read_off; c->dev.first = P.ucd[i].first; c->dev.last = P.ucd[i].last; c->dev.cell_snp = P.ucd[i].snp;
         c->dev.cell_aw = P.ucd[i].cell_aw; c->dev.tw = P.ucd[i].tw; c->dev.meta = P.ucd[i].meta; c->dev.n_reads = P.ucd[i].n_reads;
         c->dev.set_order = P.so_dev[i];
+        c->seq_pos = P.sp_dev.empty() ? nullptr : P.sp_dev[i];
         out[i] = c;
     }
     P.A->refs = n;
@@ -1515,6 +1523,10 @@ int floria_hip_contig_download(const floria_hip_contig* c, int field, void* dst,
         case FLORIA_FIELD_SET_ORDER:
             if (!c->dev.set_order) return fail(FLORIA_E_INVALID, "the contig carries no set_order");
             src = c->dev.set_order; have = 4ull * c->n_cells; break;
+        case FLORIA_FIELD_SEQ_POS:
+            // (to a contig without positions the field stays what it was before positions existed, an unknown field, and the message keeps saying so)
+            if (!c->seq_pos) return fail(FLORIA_E_INVALID, "the contig carries no seq_pos (field 8 is an unknown field of a contig without positions)");
+            src = c->seq_pos; have = 4ull * c->n_cells; break;
         default: return fail(FLORIA_E_INVALID, "unknown field");
     }
     if (bytes > have) return fail(FLORIA_E_INVALID, "field is smaller than the requested size");
@@ -2651,10 +2663,10 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
         if (counts) counts->cells = total;
         if (resident) {
             ctx->res_contig.assign(A->contig, A->contig + n); ctx->res_n_contigs = nc;
-            ctx->res_cell_off = a.cell_off; ctx->res_snp = a.snp; ctx->res_allele = a.allele; ctx->res_qual = a.qual;
+            ctx->res_cell_off = a.cell_off; ctx->res_snp = a.snp; ctx->res_allele = a.allele; ctx->res_qual = a.qual; ctx->res_seq_pos = a.seq_pos;
         }
     }
-    if (resident && n == 0) { ctx->res_contig.clear(); ctx->res_n_contigs = nc; ctx->res_cell_off = nullptr; ctx->res_snp = nullptr; ctx->res_allele = nullptr; ctx->res_qual = nullptr; }
+    if (resident && n == 0) { ctx->res_contig.clear(); ctx->res_n_contigs = nc; ctx->res_cell_off = nullptr; ctx->res_snp = nullptr; ctx->res_allele = nullptr; ctx->res_qual = nullptr; ctx->res_seq_pos = nullptr; }
     guard.r = nullptr;
     *out = R;
     return 0;
@@ -2695,7 +2707,9 @@ void floria_hip_record_summary_free(floria_record_summary* s) {
 }
 
 // `ordered`: floria_hip_assemble_contigs_ordered — the contigs that hold a merged fragment get their set_order from the device (assemble_order_kernel.h)
-static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out, bool ordered) {
+// `keep_sp`: floria_hip_assemble_contigs_opt with FLORIA_ASM_KEEP_SEQ_POS — every contig carries the SEQ_POS words of its cells; part_mate [n_parts] or null
+static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out, bool ordered, bool keep_sp = false,
+                         const uint8_t* part_mate = nullptr) {
     if (!ctx || !Y || !plan || !out || !plan->frag_off) return fail(FLORIA_E_INVALID, "null argument");
     const uint32_t nc = plan->n_contigs;
     for (uint32_t c = 0; c < nc; ++c) out[c] = nullptr;
@@ -2738,6 +2752,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
             if (!any) return fail(FLORIA_E_INVALID, "assemble: the parts of " + where() + " have no cell (every read has >= 1 cell)");
         }
     const uint64_t NP = NF ? plan->part_off[NF] : 0;
+    if (part_mate) for (uint64_t p = 0; p < NP; ++p) if (part_mate[p] > 1) return fail(FLORIA_E_INVALID, "assemble: part_mate of part " + std::to_string((unsigned long long)p) + " is " + std::to_string((unsigned)part_mate[p]) + " (0 or 1)");
     // ordered: what the general kernel may meet — the fragments beyond the wavefront kernel's tables and the largest of them (the scratch is sized before any launch)
     bool any_merged = false;
     uint64_t n_general = 0, cells_max = 0;
@@ -2757,6 +2772,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     const Seg s_po = C.seg(8 * (NF + 1)), s_pr = C.seg(4 * NP + 4), s_fc = C.seg(4 * NF + 4), s_fo = C.seg(8ull * (n + 1)), s_cnt = C.seg(8 * (NF + 1)), s_tile = C.seg(8ull * n_tiles + 8),
               s_tot = C.seg(8ull * (n + 1)), s_cdev = C.seg(sizeof(fl::ContigDev) * n);
     const Seg s_mg = C.seg(any_merged ? 4ull * n : 0), s_todo = C.seg(any_merged ? 8 * (NF + 1) : 0);
+    const Seg s_pm = C.seg(keep_sp && part_mate ? NP + 16 : 0), s_spf = C.seg(keep_sp ? 16 : 0);
     if (int rc = C.place(ctx->asm_plan)) return rc;
     fl::AsmOrderArgs oa{};
     if (n_general) {
@@ -2781,7 +2797,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     T.end(t);
     if (NF) {
         t = T.begin(K_PILEUP);
-        hipLaunchKernelGGL(fl::assemble_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((fl::assemble_kernel<false, false>), dim3(grid), dim3(256), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(fl::pileup_scan_tiles_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, a.frag_cells, C.at<uint64_t>(s_tile), nf32);
         hipLaunchKernelGGL(fl::pileup_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, C.at<uint64_t>(s_tile), n_tiles, a.frag_cells + NF);
@@ -2808,12 +2824,13 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
     const bool derive_so = any_merged && CC != 0;
     const bool any_so = (plan->set_order != nullptr && CC != 0) || derive_so;
-    const ArenaLayout AL = layout_arena(R, CC, n, any_so);
+    const ArenaLayout AL = layout_arena(R, CC, n, any_so, keep_sp);
     const size_t o_ro = AL.o_ro, o_first = AL.o_first, o_last = AL.o_last, o_snp = AL.o_snp, o_so = AL.o_so;
     Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
     if (!AR) return FLORIA_E_NOMEM;
     arena_describe(AR, AL, n, R, CC, P.rp);
     char* D = P.D = AR->buf.as<char>();
+    if (keep_sp) { P.sp_dev.assign(n, nullptr); for (uint32_t i = 0; i < n; ++i) P.sp_dev[i] = (const uint32_t*)(D + AL.o_sp + 4 * cp[i]); }
     size_t c2 = 0;
     auto seg2 = [&](size_t bytes) { const size_t o = c2; c2 += (bytes + 255) & ~(size_t)255; return o; };
     const size_t t_al = seg2(CC + 16), t_q = seg2(CC + 16);
@@ -2832,6 +2849,8 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     // ---- FILL writes the raw CSR arrays where an upload's DMA would have put them; then the upload's own validate + flatten launch ----
     a.read_off = (uint32_t*)(D + o_ro); a.first = (uint32_t*)(D + o_first); a.last = (uint32_t*)(D + o_last);
     a.out_snp = (uint32_t*)(D + o_snp); a.out_allele = (uint8_t*)(TT + t_al); a.out_qual = (uint8_t*)(TT + t_q);
+    if (keep_sp) { a.seq_pos = ctx->res_seq_pos; a.part_mate = part_mate ? C.at<const uint8_t>(s_pm) : nullptr; a.out_sp = (uint32_t*)(D + AL.o_sp); a.sp_overflow = C.at<uint32_t>(s_spf); }
+    uint32_t sp_overflow = 0;
     uint64_t pinned_b = 0, staged_b = 0;
     int rc = 0;
     hipError_t e = hipSuccess;
@@ -2839,10 +2858,12 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     if (any_so && !derive_so) { std::vector<CopyRun> runs{{(const char*)plan->set_order, D + o_so, (size_t)(4 * CC)}}; rc = issue_copies(ctx, runs, &pinned_b, &staged_b); }
     if (!rc && derive_so) e = C.up(s_mg, merged.data(), 4ull * n, ctx->stream);
     if (!rc && e == hipSuccess) e = issue_tables(ctx, P, ctx->stream);
+    if (!rc && e == hipSuccess && keep_sp) { e = hipMemsetAsync(C.at(s_spf), 0, 16, ctx->stream); if (e == hipSuccess && part_mate) e = C.up(s_pm, part_mate, NP, ctx->stream); }
     T.end(t);
     if (!rc && e == hipSuccess && NF) {
         t = T.begin(K_PILEUP);
-        hipLaunchKernelGGL(fl::assemble_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
+        if (keep_sp) hipLaunchKernelGGL((fl::assemble_kernel<true, true>), dim3(grid), dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((fl::assemble_kernel<true, false>), dim3(grid), dim3(256), 0, ctx->stream, a);
         e = hipGetLastError();
         if (e == hipSuccess && derive_so) {
             // the set orders of the merged contigs' fragments, where an uploaded set_order would lie.  Preset to all ones: whatever the kernels leave unwritten
@@ -2864,9 +2885,12 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
         T.end(t);
     }
     if (!rc && e == hipSuccess) { const int tk = T.begin(K_SEL); e = launch_flatten(ctx, P, 0, ctx->stream); T.end(tk); }
-    if (!rc && e == hipSuccess) { t = T.begin(K_D2H); e = hipMemcpyAsync(P.ust.data(), TT + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream); T.end(t); }
+    if (!rc && e == hipSuccess) { t = T.begin(K_D2H); e = hipMemcpyAsync(P.ust.data(), TT + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && keep_sp) e = hipMemcpyAsync(&sp_overflow, C.at(s_spf), 4, hipMemcpyDeviceToHost, ctx->stream);
+        T.end(t); }
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (!rc && e != hipSuccess) rc = fail(FLORIA_E_DEVICE, std::string("assemble: ") + hipGetErrorString(e));
+    if (!rc && sp_overflow) rc = fail(FLORIA_E_UNSUPPORTED, "assemble: a sequence position of 2^31 and more cannot be kept (the SEQ_POS word has 31 bits for it)");
     if (!rc) rc = finish_upload(ctx, P, out);
     if (rc) { for (uint32_t c = 0; c < nc; ++c) out[c] = nullptr; return drop(rc); }
     if (any_so) {                                          // the cell orders of the batch, now: a set_order that is no permutation is refused here, and "arith" = 1 reuses them
@@ -2888,6 +2912,15 @@ int floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summary
 
 int floria_hip_assemble_contigs_ordered(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, floria_hip_contig** out) {
     return assemble_impl(ctx, Y, plan, out, true);
+}
+
+int floria_hip_assemble_contigs_opt(floria_hip_ctx* ctx, const floria_record_summary* Y, const floria_fragment_plan* plan, const floria_assemble_options* opts, floria_hip_contig** out) {
+    if (out && plan) for (uint32_t c = 0; c < plan->n_contigs; ++c) out[c] = nullptr;
+    if (!opts) return fail(FLORIA_E_INVALID, "null argument");
+    if (opts->flags & ~(FLORIA_ASM_DERIVE_SET_ORDER | FLORIA_ASM_KEEP_SEQ_POS)) return fail(FLORIA_E_INVALID, "assemble: unknown flag bits " + std::to_string(opts->flags));
+    const bool keep = (opts->flags & FLORIA_ASM_KEEP_SEQ_POS) != 0;
+    if (opts->part_mate && !keep) return fail(FLORIA_E_INVALID, "assemble: part_mate is given without FLORIA_ASM_KEEP_SEQ_POS");
+    return assemble_impl(ctx, Y, plan, out, (opts->flags & FLORIA_ASM_DERIVE_SET_ORDER) != 0, keep, opts->part_mate);
 }
 
 // ---- remove_monomorphic_allele (utils_frags.rs:713-772) on resident contigs (mono_kernel.h) ----------------------------------------------------------------------
@@ -2947,7 +2980,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     Carve C;
     const Seg s_mc = C.seg(sizeof(fl::MonoContig) * n), s_rp = C.seg(8ull * (n + 1)), s_so = C.seg(8ull * (n + 1)), s_ws = C.seg(32 * S + 32), s_zk = C.seg(4 * S + 4), s_rm = C.seg(S + 16),
               s_nr = C.seg(8ull * n), s_k3 = C.seg(12 * Rin + 16), s_cdev = C.seg(sizeof(fl::ContigDev) * n), s_uc = C.seg(sizeof(fl::UploadContig) * n), s_op = C.seg(8ull * (n + 1)),
-              s_or = C.seg(4 * Rin + 16), s_st = C.seg(sizeof(fl::UploadStatus) * n), s_sop = C.seg(8ull * n);
+              s_or = C.seg(4 * Rin + 16), s_st = C.seg(sizeof(fl::UploadStatus) * n), s_sop = C.seg(8ull * n), s_spp = C.seg(8ull * n);
     if (int rc = C.place(ctx->mono_buf)) return give_up(rc);
     int t = 0;
     if (with_set_order && Rin) {
@@ -2967,7 +3000,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     for (uint32_t i = 0; i < n; ++i) {
         const floria_hip_contig* k = contigs[i];
         fl::MonoContig& m = mc[i];
-        m.read_off = k->dev.read_off; m.snp = k->dev.cell_snp; m.cell_aw = k->dev.cell_aw; m.snp_base = snp_off[i]; m.ord_base = cpi[i];
+        m.read_off = k->dev.read_off; m.snp = k->dev.cell_snp; m.cell_aw = k->dev.cell_aw; m.snp_base = snp_off[i]; m.ord_base = cpi[i]; m.seq_pos = k->seq_pos;
         m.n_reads = k->n_reads; m.n_cells = (uint32_t)k->n_cells; m.n_snps = (uint32_t)std::min<uint64_t>(snp_off[i + 1] - snp_off[i], 0xffffffffull); m.pad = 0;
     }
     fl::MonoArgs a{};
@@ -3024,17 +3057,21 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     ctx->upload_epoch++;
     P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
     const bool any_so = with_set_order != 0 && CC != 0;
-    const ArenaLayout AL = layout_arena(R, CC, n, any_so);
+    bool any_sp = false;                                       // an output contig carries positions iff its input does
+    for (uint32_t i = 0; i < n; ++i) any_sp = any_sp || contigs[i]->seq_pos != nullptr;
+    const ArenaLayout AL = layout_arena(R, CC, n, any_so, any_sp);
     Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
     if (!AR) return give_up(FLORIA_E_NOMEM);
     arena_describe(AR, AL, n, R, CC, P.rp);
     char* D = P.D = AR->buf.as<char>();
     const auto drop = [&](int rc) { sync_all(ctx); arena_put(AR); for (uint32_t c = 0; c < n; ++c) out[c] = nullptr; return give_up(rc); };
     P.ucd.resize(n); P.ust.resize(n); P.so_dev.assign(n, nullptr);
-    std::vector<uint32_t*> sop(n, nullptr);
+    std::vector<uint32_t*> sop(n, nullptr), spp(n, nullptr);
+    if (any_sp) P.sp_dev.assign(n, nullptr);
     for (uint32_t i = 0; i < n; ++i) {
         fl::UploadContig& u = P.ucd[i];
         arena_contig(AL, D, P.rp, P.cp, i, u);
+        if (contigs[i]->seq_pos) { spp[i] = (uint32_t*)(D + AL.o_sp + 4 * P.cp[i]); P.sp_dev[i] = spp[i]; }
         u.allele = nullptr; u.qual = nullptr;                   // (the raw bytes of an upload do not exist here: FILL writes the resident form)
         P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
         if (any_so && u.n_reads) { sop[i] = (uint32_t*)(D + AL.o_so + 4 * P.cp[i]); P.so_dev[i] = sop[i]; }
@@ -3042,6 +3079,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     a.out = C.at<const fl::UploadContig>(s_uc); a.out_prefix = C.at<const uint64_t>(s_op); a.old_read = C.at<const uint32_t>(s_or); a.status = C.at<fl::UploadStatus>(s_st);
     a.Rq1 = ctx->d_hash.as<uint64_t>(); a.Rq2 = ctx->d_hash.as<uint64_t>() + 2ull * ctx->hash_len;
     a.out_set_order = C.at<uint32_t* const>(s_sop); a.ord = ctx->cur_ord; a.n_reads_out = R;
+    a.out_seq_pos = any_sp ? C.at<uint32_t* const>(s_spp) : nullptr;
     hipError_t e = hipSuccess;
     t = T.begin(K_H2D);
     e = C.up(s_uc, P.ucd.data(), sizeof(fl::UploadContig) * n, ctx->stream);
@@ -3049,6 +3087,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     if (e == hipSuccess) e = C.up(s_or, old_read.data(), 4 * R, ctx->stream);
     if (e == hipSuccess) e = C.up(s_st, P.ust.data(), sizeof(fl::UploadStatus) * n, ctx->stream);
     if (e == hipSuccess) e = C.up(s_sop, sop.data(), 8ull * n, ctx->stream);
+    if (e == hipSuccess && any_sp) e = C.up(s_spp, spp.data(), 8ull * n, ctx->stream);
     if (e == hipSuccess && R) e = hipMemcpyAsync(D + AL.o_ro, ro_all.data(), 4 * ro_all.size(), hipMemcpyHostToDevice, ctx->stream);
     T.end(t);
     if (e == hipSuccess && R) {
@@ -3131,6 +3170,57 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(counts, C.at(s_h), 4ull * n_counts, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// ---- first / last sequence position of a read inside a haploset's SNP range (span_kernel.h) ----------------------------------------------------------------------
+int floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
+                          const uint32_t* grp_read, const uint32_t* grp_range, uint32_t n_groups, uint32_t* left, uint32_t* right) {
+    if (!ctx || (n_contigs && !contigs) || (n_groups && (!grp_contig || !grp_off || !grp_range))) return fail(FLORIA_E_INVALID, "null argument");
+    std::vector<fl::SpanContig> sc(n_contigs);
+    for (uint32_t i = 0; i < n_contigs; ++i) {
+        const floria_hip_contig* k = contigs[i];
+        if (!k) return fail(FLORIA_E_INVALID, "null argument");
+        if (k->ctx != ctx) return fail(FLORIA_E_INVALID, "read_spans: contig " + std::to_string(i) + " belongs to another context");
+        if (!k->seq_pos) return fail(FLORIA_E_INVALID, "the contig carries no seq_pos");
+        sc[i] = fl::SpanContig{k->dev.read_off, k->dev.cell_snp, k->seq_pos, k->n_reads, (uint32_t)k->n_cells};
+    }
+    if (n_groups == 0) return 0;
+    if (grp_off[0] != 0) return fail(FLORIA_E_INVALID, "read_spans: grp_off does not start at 0");
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        if (grp_contig[g] >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
+        if (grp_off[g + 1] < grp_off[g]) return fail(FLORIA_E_INVALID, "grp_off decreases");
+    }
+    const uint64_t N = grp_off[n_groups];
+    if (N == 0) return 0;
+    if (!grp_read || !left || !right) return fail(FLORIA_E_INVALID, "null argument");
+    if (N >= (1ull << 32) * 256) return fail(FLORIA_E_UNSUPPORTED, "read_spans: 2^40 and more entries in one call");
+    for (uint32_t g = 0; g < n_groups; ++g)
+        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) if (grp_read[i] >= contigs[grp_contig[g]]->n_reads) return fail(FLORIA_E_INVALID, "group read id out of range");
+    HIPCHK(hipSetDevice(ctx->device));
+    Carve C;
+    const Seg s_cd = C.seg(sizeof(fl::SpanContig) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4 * N), s_rg = C.seg(8ull * n_groups),
+              s_l = C.seg(4 * N), s_r = C.seg(4 * N);
+    if (int rc = C.place(ctx->span_buf)) return rc;
+    EventTimer T(ctx->stream);
+    ctx->timing = floria_timing{};
+    int t = T.begin(K_H2D);
+    HIPCHK(C.up(s_cd, sc.data(), sizeof(fl::SpanContig) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, grp_contig, 4ull * n_groups, ctx->stream));
+    HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4 * N, ctx->stream)); HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, ctx->stream));
+    T.end(t);
+    fl::SpanArgs a{};
+    a.contigs = C.at<const fl::SpanContig>(s_cd); a.grp_contig = C.at<const uint32_t>(s_gc); a.grp_off = C.at<const uint64_t>(s_go); a.grp_read = C.at<const uint32_t>(s_gr);
+    a.grp_range = C.at<const uint32_t>(s_rg); a.left = C.at<uint32_t>(s_l); a.right = C.at<uint32_t>(s_r); a.n_entries = N; a.n_groups = n_groups; a.n_contigs = n_contigs;
+    t = T.begin(K_PILEUP);
+    hipLaunchKernelGGL(fl::read_spans_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    T.end(t);
+    t = T.begin(K_D2H);
+    HIPCHK(hipMemcpyAsync(left, a.left, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(right, a.right, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+    T.end(t);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.total_ms = T.span();
     return 0;
 }
 

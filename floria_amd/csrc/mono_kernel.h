@@ -14,7 +14,8 @@
 //                              The host drops the empty reads, sorts the rest per contig (first ascending, last descending, old index ascending), takes the prefix
 //                              sums and sends read_off and old_read back.
 //   mono_filter_kernel<true>   FILL, one wavefront per OUTPUT read: ballot + mbcnt compaction of the surviving cells into the read's place, first / last, the tw
-//                              sums, the meta record, the contig's status words.
+//                              sums, the meta record, the contig's status words.  Where the input contig carries positions the surviving cells' SEQ_POS words move
+//                              with them (the reference removes the key from snp_pos_to_seq_pos with the cell, utils_frags.rs:749).
 //   mono_order_kernel          only when set orders are asked for, one wavefront per output read, after FILL (it reads the SNP list FILL wrote): the input read's
 //                              cells in set order (cell_orders' output) with the removed ones deleted, each renumbered to its index in the cut-down read.
 // Every index is bounded by lengths the host validated before the launch (cells per contig, SNPs per contig: no `last` exceeds its contig's SNP count) and, where a
@@ -33,6 +34,7 @@ struct MonoContig {                // one input contig and its place in the tabl
     uint64_t snp_base;             // snp_off[c]: the contig's first entry of wsum / 4, zero_key and removed
     uint64_t ord_base;             // cells of the contigs before it: where its part of the cell orders starts
     uint32_t n_reads, n_cells, n_snps, pad;
+    const uint32_t* seq_pos;       // [n_cells] the SEQ_POS words of a contig that carries positions, else null
 };
 
 struct MonoArgs {
@@ -56,6 +58,7 @@ struct MonoArgs {
     uint32_t* const* out_set_order;// [n_contigs] (ORDER) the contig's set_order region
     const uint2* ord;              // (ORDER) the input contigs' cells in set order
     uint64_t  n_reads_out;
+    uint32_t* const* out_seq_pos;  // [n_contigs] (FILL) the contig's seq_pos region, null where its input carries none; the table itself null when no input does
 };
 
 // is SNP s (1-based, as read from a cell) of contig cd removed?  An index outside the contig's table counts as removed: it addresses nothing.
@@ -169,6 +172,7 @@ template <> __global__ __launch_bounds__(256) void mono_filter_kernel<true>(Mono
         uint32_t e = G(cd.read_off)[ro + 1];
         e = e > cd.n_cells ? cd.n_cells : e;
         const uint32_t ob = G(od.read_off)[r];
+        uint32_t* const osp = g.out_seq_pos && cd.seq_pos ? g.out_seq_pos[ci] : nullptr;      // (wave-uniform)
         uint32_t n = 0, F = 0, L = 0, ma = 0, q0 = 0;          // n, F, L wave-uniform
         uint64_t t1 = 0, t2 = 0;
         for (uint32_t c0 = b; c0 < e; c0 += 64) {
@@ -183,6 +187,7 @@ template <> __global__ __launch_bounds__(256) void mono_filter_kernel<true>(Mono
                 const uint32_t a = (aw >> 28) & 3u, w = aw & 0x0fffffffu;
                 const uint32_t idx = hash_idx(s, a);
                 ((uint32_t*)od.snp)[slot] = s; od.cell_aw[slot] = aw;
+                if (osp) osp[slot] = G(cd.seq_pos)[c];
                 t1 += g.Rq1[idx] * (uint64_t)w; t2 += g.Rq2[idx] * (uint64_t)w;
                 ma = a > ma ? a : ma; q0 |= w == 0 ? 1u : 0u;
             }

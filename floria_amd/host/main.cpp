@@ -14,7 +14,7 @@
 // longest first; one context and one host thread per device; the files are those of a one-GPU run),
 // --batch-contigs N / --batch-cells N (size of a device batch), --debug (debug_graph.txt per contig), --lp-tie first|last (which optimal vertex of the
 // stitching LP is used where the optimum is not unique; the run reports how many contigs that concerns), and for tests --dump-frags FILE,
-// --ingest-only, --no-realign, --stitch-graph FILE.
+// --dump-seq-pos FILE, --ingest-only, --no-realign, --stitch-graph FILE.
 // --pileup host | device: where the CIGAR walk that turns alignment records into SNP calls runs.  host [default]: frag_from_record on -t threads, one contig per task;
 // device: one floria_hip_pileup_records call per ingest round for every record that passes the alignment filter, the Frags filled from its cells (same files).
 // fused: device, with the realignment of the calls done by the same call (floria_hip_pileup_records_realign) before the cells come back; without realignment (--no-realign)
@@ -126,7 +126,7 @@ int main(int argc, char** argv) {
     floria_hip_init_env();                      // GPU_MAX_HW_QUEUES=12 unless set: the job groups' streams and the copy streams must not share hardware queues (read when HIP initialises)
     Options o;
     bool have_e = false, have_l = false;
-    std::string dump_frags;
+    std::string dump_frags, dump_seq_pos;
     size_t batch_contigs = 4096;         // --batch-contigs
     uint64_t batch_cells = 256ull << 20; // --batch-cells (1.5 GB of pinned staging)
     bool ingest_only = false, no_realign = false, have_realign = false;
@@ -212,6 +212,7 @@ int main(int argc, char** argv) {
             else if (a == "--batch-contigs") batch_contigs = std::max<size_t>(1, std::stoul(val()));       // contigs per device batch
             else if (a == "--batch-cells") batch_cells = std::max<uint64_t>(1, std::stoull(val()));        // SNP calls per device batch
             else if (a == "--dump-frags") dump_frags = val();
+            else if (a == "--dump-seq-pos") dump_seq_pos = val();      // (tests) Frag::snp_pos_to_seq_pos of every fragment, in --dump-frags' order
             else if (a == "--no-realign") no_realign = true;                   // (tests) keep the alleles as called
             else if (a == "--realign") { parse_realign_spec(val(), o); have_realign = true; }
             else if (a == "--pileup") {
@@ -348,6 +349,8 @@ int main(int argc, char** argv) {
 
         std::ofstream dump;
         if (!dump_frags.empty()) dump.open(dump_frags, std::ios::trunc);
+        std::ofstream dump_sp;
+        if (!dump_seq_pos.empty()) dump_sp.open(dump_seq_pos, std::ios::trunc);
         // ---- which contigs (floria.rs:229-262) -------------------------------------------------------------------------------------
         bool warn_first_length = true;
         const size_t n_threads = std::max<size_t>(1, o.num_threads);
@@ -472,6 +475,15 @@ int main(int argc, char** argv) {
                     }
                     for (const Frag& f : w.frags_without_snps) dump << "#SNPLESS\t" << f.id << "\t" << f.first_pos_base << "\t" << f.last_pos_base << "\t" << (f.seq_len[0] + f.seq_len[1]) << "\n";
                 }
+            if (dump_sp.is_open())
+                for (const ContigWork& w : work) {
+                    dump_sp << "#CONTIG\t" << w.name << "\t" << w.all_frags.size() << "\n";
+                    for (const Frag& f : w.all_frags) {          // id, then snp:mate:seq_pos for every entry of snp_pos_to_seq_pos, ascending
+                        dump_sp << f.id;
+                        for (const auto& kv : f.snp_pos_to_seq_pos) dump_sp << "\t" << kv.first << ":" << (int)kv.second.first << ":" << kv.second.second;
+                        dump_sp << "\n";
+                    }
+                }
             t_ingest += now_s() - t0;
             if (ingest_only || work.empty()) continue;
             ++n_batches;
@@ -563,6 +575,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Total time taken is %.3fs\n", now_s() - t_all);
         // everything is written and closed: leave without tearing down the records, maps and sequences one by one (seconds for a large BAM)
         if (dump.is_open()) dump.close();
+        if (dump_sp.is_open()) dump_sp.close();
         sessions.clear();
         // every output stream of this run was scoped to the function that wrote it and is closed; stdio is flushed here.  What is left are the records,
         // maps and sequences of the inputs, whose node-by-node teardown takes seconds for a large run: the process leaves without it (the freer of the

@@ -30,6 +30,7 @@ SYMBOLS = [
     "floria_hip_contig_download", "floria_hip_phase_pileups_batch",
     "floria_hip_pileup_records", "floria_hip_record_cells_free", "floria_hip_pileup_records_realign",
     "floria_hip_pileup_records_resident", "floria_hip_record_summary_free", "floria_hip_assemble_contigs", "floria_hip_assemble_contigs_ordered", "floria_hip_haploset_alleles",
+    "floria_hip_assemble_contigs_opt", "floria_hip_read_spans",
     "floria_hip_drop_monomorphic", "floria_hip_mono_result_free", "floria_hip_mono_timing",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
@@ -87,6 +88,8 @@ def load():
         L.floria_hip_record_summary_free.argtypes = [C.POINTER(capi.CRecordSummary)]
         L.floria_hip_assemble_contigs.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(C.c_void_p)]
         L.floria_hip_assemble_contigs_ordered.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(C.c_void_p)]
+        L.floria_hip_assemble_contigs_opt.argtypes = [C.c_void_p, C.POINTER(capi.CRecordSummary), C.POINTER(capi.CFragmentPlan), C.POINTER(capi.CAssembleOptions), C.POINTER(C.c_void_p)]
+        L.floria_hip_read_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u32p, C.c_uint32, capi.u32p, capi.u32p]
         L.floria_hip_drop_monomorphic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u64p, C.c_double, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(capi.CMonoResult))]
         L.floria_hip_mono_result_free.argtypes = [C.POINTER(capi.CMonoResult)]
         L.floria_hip_mono_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -223,7 +226,7 @@ class ResidentContig:
         self._h = h
 
     FIELDS = {"read_off": (0, np.uint32), "first": (1, np.uint32), "last": (2, np.uint32), "snp": (3, np.uint32),
-              "cell_aw": (4, np.uint32), "tw": (5, np.uint64), "meta": (6, np.uint32), "set_order": (7, np.uint32)}
+              "cell_aw": (4, np.uint32), "tw": (5, np.uint64), "meta": (6, np.uint32), "set_order": (7, np.uint32), "seq_pos": (8, np.uint32)}
 
     def download(self, field, count):
         """Diagnostic (floria_hip_contig_download): `count` elements of a resident array."""
@@ -506,9 +509,11 @@ class FloriaHip:
         the reference's containers give their reads, derived on the device (download field "set_order"); the other contigs carry none."""
         return self.assemble_contigs(summary, frag_off, part_off, part_rec, _ordered=True)
 
-    def assemble_contigs(self, summary, frag_off, part_off, part_rec, set_order=None, _ordered=False):
+    def assemble_contigs(self, summary, frag_off, part_off, part_rec, set_order=None, _ordered=False, keep_seq_pos=False, part_mate=None, _flags=None):
         """floria_hip_assemble_contigs: the fragment plan (frag_off uint64 [n_contigs + 1], part_off uint64 [n_frags + 1], part_rec uint32 record indices in merge
-        order, optional set_order uint32 over the merged cells of all contigs) -> one ResidentContig per contig, usable wherever uploaded ones are."""
+        order, optional set_order uint32 over the merged cells of all contigs) -> one ResidentContig per contig, usable wherever uploaded ones are.
+        keep_seq_pos (floria_hip_assemble_contigs_opt, FLORIA_ASM_KEEP_SEQ_POS): every contig also carries one SEQ_POS word `mate << 31 | seq_pos` per cell
+        (download field "seq_pos", read_spans); part_mate uint8 [len(part_rec)] marks the parts of the second mate, None = all 0.  (_flags: the raw flags word.)"""
         fo = np.ascontiguousarray(frag_off, np.uint64); po = np.ascontiguousarray(part_off, np.uint64); pr = np.ascontiguousarray(part_rec, np.uint32)
         if len(fo) < 1 or len(po) != int(fo[-1]) + 1 or (len(po) and len(pr) < int(po.max())):
             raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: frag_off needs n_contigs + 1 entries, part_off n_frags + 1, part_rec part_off[-1]")
@@ -518,7 +523,15 @@ class FloriaHip:
         hs = (C.c_void_p * max(n, 1))()
         if summary._p is None:
             raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: the record summary has been freed")
-        _check((load().floria_hip_assemble_contigs_ordered if _ordered else load().floria_hip_assemble_contigs)(self._h, summary._p, C.byref(plan), hs))
+        if keep_seq_pos or part_mate is not None or _flags is not None:
+            pm = None if part_mate is None else np.ascontiguousarray(part_mate, np.uint8)
+            if pm is not None and len(pm) != len(pr):
+                raise FloriaHipError(capi.FLORIA_E_INVALID, "assemble_contigs: part_mate needs one byte per entry of part_rec")
+            flags = _flags if _flags is not None else (capi.FLORIA_ASM_KEEP_SEQ_POS if keep_seq_pos else 0) | (capi.FLORIA_ASM_DERIVE_SET_ORDER if _ordered else 0)
+            opts = capi.CAssembleOptions(int(flags), None if pm is None else capi.ptr(pm, C.c_uint8))
+            _check(load().floria_hip_assemble_contigs_opt(self._h, summary._p, C.byref(plan), C.byref(opts), hs))
+        else:
+            _check((load().floria_hip_assemble_contigs_ordered if _ordered else load().floria_hip_assemble_contigs)(self._h, summary._p, C.byref(plan), hs))
         return [ResidentContig(self, handle=C.c_void_p(hs[i]), n_reads=int(fo[i + 1] - fo[i])) for i in range(n)]
 
     def drop_monomorphic(self, contigs, snp_counts, error, with_set_order=False):
@@ -563,6 +576,28 @@ class FloriaHip:
         _check(load().floria_hip_haploset_alleles(self._h, arr, C.c_uint32(len(contigs)), capi.ptr(gc, C.c_uint32), capi.ptr(off, C.c_uint64), capi.ptr(reads, C.c_uint32),
                                                   capi.ptr(rng, C.c_uint32), C.c_uint32(len(groups)), capi.ptr(pos_off, C.c_uint64), capi.ptr(counts, C.c_uint32)))
         return pos_off, counts
+
+    def read_spans(self, contigs, grp_contig, groups, ranges):
+        """floria_hip_read_spans: per haploset (read-id list + inclusive SNP range, as haploset_alleles takes them; or groups = (grp_off, grp_read) arrays) and read the SEQ_POS word of the read's first
+        cell with snp >= lo and of its last cell with snp <= hi -> (left uint32 [sum of the group sizes], right uint32 [same]); capi.FLORIA_SPAN_NONE where the
+        read has no such cell.  Every contig must carry positions (assemble_contigs(keep_seq_pos=True), or drop_monomorphic of such contigs)."""
+        n = len(contigs)
+        arr = contigs._arr if isinstance(contigs, ContigBatch) else (C.c_void_p * max(n, 1))(*[c._h for c in contigs])
+        gc = np.ascontiguousarray(grp_contig, np.uint32)
+        if isinstance(groups, tuple) and len(groups) == 2 and isinstance(groups[0], np.ndarray):      # (grp_off uint64 [n_groups + 1], grp_read uint32) as the C entry takes them
+            off, reads = np.ascontiguousarray(groups[0], np.uint64), np.ascontiguousarray(groups[1], np.uint32)
+        else:
+            off = np.zeros(len(groups) + 1, np.uint64)
+            off[1:] = np.cumsum([len(g) for g in groups])
+            reads = np.ascontiguousarray(np.concatenate([np.asarray(g, np.uint32) for g in groups] + [np.zeros(0, np.uint32)]), np.uint32)
+        ng = len(off) - 1
+        rng = np.ascontiguousarray(np.asarray(ranges, np.uint32).reshape(-1))
+        if ng < 0 or len(gc) != ng or len(rng) != 2 * ng or (ng and len(reads) < int(off.max())):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "read_spans: one contig index and one (lo, hi) per group, grp_off[-1] read ids")
+        left = np.zeros(int(off[-1]), np.uint32); right = np.zeros(int(off[-1]), np.uint32)
+        _check(load().floria_hip_read_spans(self._h, arr, C.c_uint32(n), capi.ptr(gc, C.c_uint32), capi.ptr(off, C.c_uint64), capi.ptr(reads, C.c_uint32),
+                                            capi.ptr(rng, C.c_uint32), C.c_uint32(ng), capi.ptr(left, C.c_uint32), capi.ptr(right, C.c_uint32)))
+        return left, right
 
     def _pileup_records(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=None, walk=None, resident=False):
         def arr(a, dt):

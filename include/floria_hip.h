@@ -220,6 +220,7 @@ int  floria_hip_contig_upload_batch(floria_hip_ctx* ctx, const floria_pileup* pi
 #define FLORIA_FIELD_TW       5
 #define FLORIA_FIELD_META     6
 #define FLORIA_FIELD_SET_ORDER 7   /* uint32 [n_cells], only of a contig that carries a set_order (FLORIA_E_INVALID "the contig carries no set_order" otherwise) */
+#define FLORIA_FIELD_SEQ_POS   8   /* uint32 [n_cells], the SEQ_POS words (floria_hip_assemble_contigs_opt), only of a contig that carries positions (FLORIA_E_INVALID "the contig carries no seq_pos (field 8 is an unknown field of a contig without positions)" otherwise) */
 int  floria_hip_contig_download(const floria_hip_contig* c, int field, void* dst, size_t bytes);
 
 /* Pinned host memory for pileup arrays (NULL on failure). */
@@ -448,7 +449,7 @@ typedef struct {
  *   - a fragment's cells: one cell per SNP that occurs in any of its parts, in ascending SNP order; allele and qual of a SNP come from the LAST part in list order
  *     that has it (`seq_dict.extend`: the later record's call overwrites the earlier one);
  *   - first / last: the smallest / largest merged SNP (= the min of the parts' firsts / max of their lasts; a part without cells changes neither);
- *   - seq_pos and ref_end are not part of a contig; records the plan does not name are unused; a record may appear anywhere, any number of times; parts need not
+ *   - seq_pos and ref_end are not part of a contig (floria_hip_assemble_contigs_opt keeps seq_pos); records the plan does not name are unused; a record may appear anywhere, any number of times; parts need not
  *     be in genome order.
  * The handles are indistinguishable from those floria_hip_contig_upload_batch returns for the equivalent floria_pileup array: every floria_hip_contig_download
  * field has the same bytes, the derived properties (biallelic / q = 0 routing, set_order in "arith" = 1, one arena for the batch) are the same, each is freed with
@@ -480,6 +481,27 @@ int  floria_hip_assemble_contigs(floria_hip_ctx* ctx, const floria_record_summar
  * counts the additional launches into pileup_ms.  (Test option "asm_order_general" = 1: every fragment takes the one-thread kernel; results do not change.) */
 int  floria_hip_assemble_contigs_ordered(floria_hip_ctx* ctx, const floria_record_summary* resident, const floria_fragment_plan* plan, floria_hip_contig** out /* [n_contigs] */);
 
+/* floria_hip_assemble_contigs with options.  flags == 0 IS floria_hip_assemble_contigs, flags == FLORIA_ASM_DERIVE_SET_ORDER IS floria_hip_assemble_contigs_ordered: the
+ * same bytes in every handle, the same refusals with the same messages.
+ * FLORIA_ASM_KEEP_SEQ_POS: every contig of the batch (an empty one too) CARRIES POSITIONS — Frag::snp_pos_to_seq_pos, one SEQ_POS word per resident cell:
+ *     word = mate << 31 | seq_pos
+ *   - seq_pos is what floria_record_cells::seq_pos holds for the cell that gave the merged SNP its call (hard-clip shift of a supplementary alignment included);
+ *   - mate is part_mate[p] of the part p that cell belongs to — the second element of the reference's (u8, GnPosition): 1 for the parts the host marks as the
+ *     second mate (file_reader.rs:556-562), 0 otherwise and for supplementary parts (:649-651); part_mate == NULL: every mate is 0;
+ *   - a SNP several parts have takes the word of the LAST part in list order that has it (`snp_pos_to_seq_pos.extend` follows the rule of `seq_dict.extend`).
+ * The words lie in a region of their own behind every other region of the arena; every other download field, the derived properties and the results of every
+ * entry point on such a handle are those of the handle without positions.  floria_hip_contig_download(FLORIA_FIELD_SEQ_POS) returns the words,
+ * floria_hip_drop_monomorphic carries them through, floria_hip_read_spans answers write_reads' two lookups from them.  Both flags together work: the set-order
+ * kernels do not read positions.  A walked seq_pos >= 2^31 cannot be encoded (no BAM record with l_seq < 2^31 - 2^28 produces one): the FILL pass raises a status
+ * word and the call fails with FLORIA_E_UNSUPPORTED, returns no handle and leaves the residency intact.
+ * Refused before any launch, FLORIA_E_INVALID each: opts == NULL; flag bits other than the two; part_mate without FLORIA_ASM_KEEP_SEQ_POS; a part_mate byte other
+ * than 0 or 1; everything the plain and the ordered call refuse. */
+#define FLORIA_ASM_DERIVE_SET_ORDER 1u   /* what floria_hip_assemble_contigs_ordered does */
+#define FLORIA_ASM_KEEP_SEQ_POS     2u
+typedef struct { uint32_t flags; const uint8_t* part_mate; /* [n_parts] 0/1 in the order of part_rec, NULL = all 0; only with KEEP_SEQ_POS */ } floria_assemble_options;
+int  floria_hip_assemble_contigs_opt(floria_hip_ctx* ctx, const floria_record_summary* resident, const floria_fragment_plan* plan, const floria_assemble_options* opts,
+                                     floria_hip_contig** out /* [n_contigs] */);
+
 /* ---- remove_monomorphic_allele (utils_frags.rs:713-772, --ignore-monomorphic; called at floria.rs:315-317) on resident contigs: no cell crosses the link ------------
  * contigs[0..n_contigs) are resident contigs of this context from any source (single uploads, an upload batch, floria_hip_assemble_contigs; they need not share an
  * arena); snp_off is the prefix sum of their SNP counts (contig c has SNPs 1 .. snp_off[c+1] - snp_off[c]).  Literal to the reference:
@@ -500,6 +522,8 @@ int  floria_hip_assemble_contigs_ordered(floria_hip_ctx* ctx, const floria_recor
  * indices renumbered, which is what the reference's set holds (`remove` moves no other key, utils_frags.rs:745-755).  A host-given input order that is no
  * permutation is FLORIA_E_INVALID with S1's message.  with_set_order == 0: the outputs carry none, and "arith" = 1 on them then emulates a one-walk set of the
  * CUT-DOWN cells, which is NOT the reference's function for a read that lost cells (its set keeps the layout it had with the removed keys in it).
+ * POSITIONS.  An output contig carries positions (floria_hip_assemble_contigs_opt) iff its input contig does: the surviving cells' SEQ_POS words move with them (the
+ * reference removes the key from snp_pos_to_seq_pos with the cell, utils_frags.rs:749); the outputs of inputs without positions refuse FLORIA_FIELD_SEQ_POS as before.
  * res (may be NULL) receives the library-owned map back to the inputs (floria_hip_mono_result_free).
  * Refused before any launch, FLORIA_E_INVALID each: a null argument; a contig of another context; snp_off not starting at 0 or descending; a non-finite error; a
  * contig with a read whose `last` exceeds its SNP count (the message names the contig).  On error no handle is returned.
@@ -529,6 +553,22 @@ int  floria_hip_mono_timing(const floria_hip_ctx* ctx, double* ms6);
 int  floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
                                  const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
                                  const uint32_t* grp_range, uint32_t n_groups, const uint64_t* pos_off, uint32_t* counts);
+
+/* The two lookups write_reads (file_writer.rs:460-530) makes in Frag::snp_pos_to_seq_pos per (haploset, read), for a host that holds no cells: the groups are given
+ * as for floria_hip_haploset_alleles (reads of a contig plus an inclusive 1-based SNP range [lo, hi]); every contig must carry positions
+ * (floria_hip_assemble_contigs_opt with FLORIA_ASM_KEEP_SEQ_POS, or floria_hip_drop_monomorphic of such contigs).  For entry j of group g (read grp_read[j] of contig
+ * grp_contig[g]): left[j] = the SEQ_POS word (mate << 31 | seq_pos) of the read's first cell with snp >= lo, right[j] = that of its last cell with snp <= hi, each
+ * FLORIA_SPAN_NONE where the read has no such cell.  The two are answered independently: a group with hi < lo gets no special case.  (The word of mate 1 at
+ * seq_pos 2^31 - 1 equals FLORIA_SPAN_NONE; no BAM record reaches it.)  The +-25-base extension, extend_read_clipping and the sequence-length clamps stay on the host.
+ * 8 B per entry come back, one transfer per array (csrc/span_kernel.h: one thread per entry, no scratch).
+ * Refused before any launch, FLORIA_E_INVALID each: a null argument; a contig of another context; a contig without positions ("the contig carries no seq_pos");
+ * grp_contig >= n_contigs; grp_off not starting at 0 or descending; a grp_read >= its contig's n_reads.
+ * The call works in a buffer of its own: unlike floria_hip_haploset_alleles it ends no residency (the last phase_blocks* batch stays valid for floria_hip_hap_graph,
+ * a record residency for floria_hip_assemble_contigs*).  floria_hip_last_timing then reports pileup_ms (the kernel), h2d_ms, d2h_ms, total_ms. */
+#define FLORIA_SPAN_NONE 0xFFFFFFFFu
+int  floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                           const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
+                           const uint32_t* grp_range, uint32_t n_groups, uint32_t* left /* [grp_off[n_groups]] */, uint32_t* right /* same */);
 
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
