@@ -189,6 +189,8 @@ struct Knobs {
     uint32_t fx_tags = 0;         // (A/B) reference arithmetic: cap on the words of a position map's claim table (0 = as many as cost no workgroup per CU)
     uint32_t arith_ow6 = 0;       // (A/B) ... the optimise kernel compiled for six waves per SIMD at every ploidy
     uint32_t asm_order_general = 0;      // (tests) floria_hip_assemble_contigs_ordered: every fragment's set order through the general kernel (assemble_order_kernel.h)
+    uint32_t chain_wgs = 0;       // (tests) the grid-stride launches of the resident chain (walk, realign gather / scatter, assemble, assemble order, mono FILL / ORDER) use at most this
+                                  // many workgroups, and the general order kernel this many threads: a wavefront's second trip at small shapes (0 = the grids as they are)
     uint32_t arith_replay = 0;    // (tests) reference arithmetic: replay every position map insertion by insertion (the home-bucket rule of optimize_kernel.h off)
     uint32_t arith_hbm = 0;       // (tests) reference arithmetic: position-map tables and first-insertion keys in HBM scratch even where they fit into LDS
     uint32_t opt_block_order = 0; // (A/B, tests) optimise: the build / distance passes visit the reads in block order instead of longest first
@@ -1013,6 +1015,12 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     delete c;
 }
 
+// the grid of a grid-stride launch of the resident chain: as computed, unless the test option "chain_wgs" caps it
+static inline uint32_t chain_grid(const floria_hip_ctx* ctx, uint32_t grid) {
+    const uint32_t cap = ctx->knobs.chain_wgs;
+    return cap && grid > cap ? cap : grid;
+}
+
 int floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots) {
     if (!ctx) return fail(FLORIA_E_INVALID, "null ctx");
     ctx->user_slots = beam_slots;
@@ -1038,6 +1046,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "arith_hbm") K.arith_hbm = value != 0;
     else if (k == "arith_replay") { K.arith_replay = value != 0; ctx->ord_epoch = ~0ull; }      // (the cell orders are computed again, the long way or the short one)
     else if (k == "asm_order_general") K.asm_order_general = value != 0;
+    else if (k == "chain_wgs") { if (value < 0 || value > (int64_t)0x7fffffff) return fail(FLORIA_E_INVALID, "chain_wgs: 0 off | the largest grid of the resident chain's grid-stride launches"); K.chain_wgs = (uint32_t)value; }
     else if (k == "fx_tags") { if (value != 0 && (value < (int64_t)fl::FX_TAGS_MIN || value > (int64_t)fl::FX_TAGS_MAX || (value & (value - 1)))) return fail(FLORIA_E_INVALID, "fx_tags: 0 | a power of two in 128..1024"); K.fx_tags = (uint32_t)value; }
     else if (k == "arith_ow6") K.arith_ow6 = value != 0;
     else if (k == "s2_assign_only") K.s2_assign_only = value != 0;
@@ -2574,7 +2583,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
         // (the table travels from its first used entry: the kernels index it with the caller's offsets)
         a.snp_pos = C.at<const int64_t>(s_sp) - snp_b; a.alleles = C.at<const uint8_t>(s_al) - 4 * snp_b; a.n_alleles = C.at<const uint8_t>(s_na) - snp_b;
         a.cell_off = C.at<uint64_t>(s_off); a.ref_end = C.at<int64_t>(s_re); a.n_records = n;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, (uint64_t)ctx->n_cu * 8);      // one wavefront per record, grid-stride beyond 8 workgroups per CU
+        const uint32_t grid = chain_grid(ctx, (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, (uint64_t)ctx->n_cu * 8));      // one wavefront per record, grid-stride beyond 8 workgroups per CU
         int t = T.begin(K_PILEUP);
         hipLaunchKernelGGL(fl::pileup_walk_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
@@ -2603,7 +2612,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
             r.alleles = a.alleles; r.n_alleles = a.n_alleles; r.ref_off = C.at<const uint64_t>(s_roff); r.ref_seq = C.at<const uint8_t>(s_ref) - ref_b;
             r.snp = a.snp; r.seq_pos = a.seq_pos; r.allele = a.allele; r.undecided = O.at<uint8_t>(o_und); r.counts = C.at<uint64_t>(s_cnt);
             r.n_cells = total; r.n_records = n;
-            const uint32_t ggrid = (uint32_t)std::min<uint64_t>((total + 7) / 8, (uint64_t)ctx->n_cu * 8);      // 8 cells per workgroup and trip
+            const uint32_t ggrid = chain_grid(ctx, (uint32_t)std::min<uint64_t>((total + 7) / 8, (uint64_t)ctx->n_cu * 8));      // 8 cells per workgroup and trip
             t = T.begin(K_PILEUP);
             HIPCHK(hipMemsetAsync(r.counts, 0, 8ull * fl::RG_N_COUNTS, ctx->stream));
             hipLaunchKernelGGL(fl::realign_decide_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, r);
@@ -2628,7 +2637,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
                 hipLaunchKernelGGL(fl::realign_fill_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, r);
                 HIPCHK(hipGetLastError());
                 HIPCHK(walk ? launch_realign_walk(ctx, *walk, ra) : launch_realign(ctx, ra));
-                const uint32_t sgrid = (uint32_t)std::min<uint64_t>((n_work + 255) / 256, (uint64_t)ctx->n_cu * 8);
+                const uint32_t sgrid = chain_grid(ctx, (uint32_t)std::min<uint64_t>((n_work + 255) / 256, (uint64_t)ctx->n_cu * 8));
                 hipLaunchKernelGGL(fl::realign_scatter_kernel, dim3(sgrid), dim3(256), 0, ctx->stream, (const uint8_t*)ra.best, (const uint64_t*)r.wcell, n_work, r.allele, r.counts);
                 HIPCHK(hipGetLastError());
                 T.end(t);
@@ -2778,7 +2787,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     if (n_general) {
         oa.cells_max = (uint32_t)cells_max; oa.ctrl_bytes = fl::fx_ctrl_bytes(oa.cells_max + 1); oa.slot_bytes = fl::fx_slot_bytes(oa.cells_max + 1);
         const uint64_t per = fl::AO_TABLES * (oa.ctrl_bytes + oa.slot_bytes);      // a thread's five tables; as many threads as 2 GiB hold, one at the least
-        oa.n_threads = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(n_general, 65536), (2ull << 30) / per));
+        oa.n_threads = chain_grid(ctx, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(n_general, 65536), (2ull << 30) / per)));
         oa.scratch_bytes = per * oa.n_threads;
         if (int rc = ctx->asm_ord_scr.ensure(oa.scratch_bytes)) return rc;
         oa.scratch = ctx->asm_ord_scr.as<uint8_t>();
@@ -2790,7 +2799,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     a.part_off = C.at<const uint64_t>(s_po); a.part_rec = C.at<const uint32_t>(s_pr); a.frag_ctg = C.at<const uint32_t>(s_fc); a.frag_off = C.at<const uint64_t>(s_fo);
     a.frag_cells = C.at<uint64_t>(s_cnt); a.n_frags = NF;
     std::vector<uint64_t> cp(n + 1, 0);
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((NF + 3) / 4, (uint64_t)ctx->n_cu * 8));      // one wavefront per fragment, grid-stride beyond 8 workgroups per CU
+    const uint32_t grid = chain_grid(ctx, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((NF + 3) / 4, (uint64_t)ctx->n_cu * 8)));      // one wavefront per fragment, grid-stride beyond 8 workgroups per CU
     int t = T.begin(K_H2D);
     if (NF) { HIPCHK(C.up(s_po, plan->part_off, 8 * (NF + 1), ctx->stream)); HIPCHK(C.up(s_pr, plan->part_rec, 4 * NP, ctx->stream)); HIPCHK(C.up(s_fc, frag_ctg.data(), 4 * NF, ctx->stream)); }
     HIPCHK(C.up(s_fo, plan->frag_off, 8ull * (n + 1), ctx->stream));
@@ -3091,7 +3100,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     if (e == hipSuccess && R) e = hipMemcpyAsync(D + AL.o_ro, ro_all.data(), 4 * ro_all.size(), hipMemcpyHostToDevice, ctx->stream);
     T.end(t);
     if (e == hipSuccess && R) {
-        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((R + 3) / 4, (uint64_t)ctx->n_cu * 8));      // one wavefront per output read, grid-stride beyond 8 workgroups per CU
+        const uint32_t grid = chain_grid(ctx, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((R + 3) / 4, (uint64_t)ctx->n_cu * 8)));      // one wavefront per output read, grid-stride beyond 8 workgroups per CU
         t = T.begin(K_FILL);
         hipLaunchKernelGGL(fl::mono_filter_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
         T.end(t);

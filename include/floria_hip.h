@@ -611,7 +611,9 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * (0|128|512|1024), "opt_global", "opt_block_order" (tests / A/B: the optimise kernel's passes visit a block's reads in block order instead of longest first), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
- * kernel; results do not change), "hw_queues" (tests: override the number of
+ * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
+ * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic — uses at most N workgroups, and the one-thread order kernel at most N threads,
+ * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "hw_queues" (tests: override the number of
  * concurrently running streams floria_hip_create measured — 6 on an MI355X whose host set GPU_MAX_HW_QUEUES=12 before HIP initialised, 4 or fewer
  * with the runtime's default; below 5 the launch plans stay within two job groups and do not speculate). */
 int  floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value);

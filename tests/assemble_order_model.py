@@ -2,8 +2,8 @@
 pileups and the CPU oracle's restatement of the reference's containers (oracle.set_order_of -> positions_order, oracle/floria_oracle.cpp).  A contig is merged
 when one of its fragments has two or more parts with cells; the other contigs carry no order (None).
 
-Also here: the named hand cases both test files use (parts as lists of SNP indices, merge order), the two cases beyond the wavefront kernel's tables, and the
-seeded random pairs."""
+Also here: the named hand cases both test files use (parts as lists of SNP indices, merge order), the two cases beyond the wavefront kernel's tables, the
+case whose parts are long enough for a second round of assemble_kernel's search, and the seeded random pairs."""
 import dataclasses
 
 import numpy as np
@@ -67,6 +67,36 @@ BEYOND = {
     "k1792_plus_5": ([R(1, 1793), [5]], True, True),
     "two_thousand_keys": ([R(1, 2400, 3), R(5000, 7400, 2)], True, True),
 }
+# one fragment of two parts of more than 4 160 cells each: assemble_kernel's 64-ary search of a part's SNP list (asm_lower_bound) narrows a range to step - 1
+# cells per round, so only such a part sends it through a second round.  On a table of 9 000 SNPs no part has a SNP that is a multiple of 4; of every 12 SNPs
+# the first part has those congruent to 2 3 5 6 7 9 10 11, the second those congruent to 1 2 5 6 9 10: both have cells in every 64-SNP window, and they share
+# five SNPs of every 12.  SNPs 5 000 .. 5 199 belong to the first part alone, ALL of them: one whole window [w, w + 64) of the merge at least lies inside the
+# stretch, full of that part, at an i0 that two rounds found.  The set order differs from the one-walk order: 6 100 + 2 200 reserved keys outgrow the first part's
+# 8 192 buckets, which hold the 6 800 merged keys of a one-walk set.
+ROUNDS_SNPS = 9000
+ROUNDS_STRETCH = (5000, 5200)
+_in_stretch = lambda s: ROUNDS_STRETCH[0] <= s < ROUNDS_STRETCH[1]
+ROUNDS = {
+    "two_search_rounds": ([[s for s in range(1, ROUNDS_SNPS + 1) if _in_stretch(s) or s % 12 in (2, 3, 5, 6, 7, 9, 10, 11)],
+                           [s for s in range(1, ROUNDS_SNPS + 1) if not _in_stretch(s) and s % 12 in (1, 2, 5, 6, 9, 10)]], True, True),
+}
+# world name -> (cases, SNPs of contig 0's table): what both test files build with world()
+WORLDS = {"hand": (HAND, 2000), "beyond": (BEYOND, 7400), "rounds": (ROUNDS, ROUNDS_SNPS)}
+
+
+def merge_windows(parts):
+    """the 64-SNP windows assemble_kernel's merge visits for parts given as ascending SNP arrays: the first starts at the smallest SNP of any part, the next at
+    the smallest SNP at or behind w + 64 that any part has -> (window starts, per part: its cells inside every window)"""
+    parts = [np.asarray(p, np.int64) for p in parts]
+    u = np.unique(np.concatenate(parts))
+    w = [int(u[0])]
+    while True:
+        k = int(np.searchsorted(u, w[-1] + 64))
+        if k >= len(u):
+            break
+        w.append(int(u[k]))
+    w = np.asarray(w, np.int64)
+    return w, [np.searchsorted(p, w + 64) - np.searchsorted(p, w) for p in parts]
 
 
 def world(cases, names, table, singles=((5, 9), (1, 40), (60, 61)), second_contig=None):

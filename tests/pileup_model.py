@@ -260,6 +260,17 @@ def random_case(seed=1577, n_records=20000):
     return recs, tables
 
 
+_sweep = []
+
+
+def random_sweep():
+    """random_case() and its walk -> (records, tables, walked): computed once per process and shared by the tests, never changed"""
+    if not _sweep:
+        recs, tables = random_case()
+        _sweep.append((recs, tables, walk_records(recs, tables)))
+    return _sweep[0]
+
+
 def coverage(records, tables, result):
     """what the random sweep asserts about its own input: ops seen, cells, SNPs under D / N, records with more than 64 ops"""
     ops = set(op for r in records for op, _ in r["cigar"])

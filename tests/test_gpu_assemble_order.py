@@ -22,7 +22,7 @@ def world_of(oracle, which):
     if which == "pairs":
         recs, tables, walked, frags = om.random_pairs()
     else:
-        cases, n_snps = (om.HAND, 2000) if which == "hand" else (om.BEYOND, 7400)
+        cases, n_snps = om.WORLDS[which]
         recs, tables, walked, frags, _ = om.world(cases, sorted(cases), am.grid_table(n_snps), second_contig=am.grid_table(40, start=40, step=9))
     plan = am.build_plan(walked, frags)
     orders, differs = om.expected_orders(oracle, walked, plan)

@@ -59,8 +59,7 @@ def test_record_counts_that_fill_no_workgroup_wavefront_or_scan_tile(gpu_ctx, n)
 
 
 def test_random_sweep_equals_the_model(gpu_ctx):
-    recs, tables = pm.random_case()
-    want = pm.walk_records(recs, tables)
+    recs, tables, want = pm.random_sweep()
     cov = pm.coverage(recs, tables, want)
     assert len(recs) >= 20000 and len(tables) == 3 and cov["ops"] == set(pm.OPS), cov
     assert cov["cells"] >= 10000 and cov["under_dn"] >= 100 and cov["long_records"] >= 100, cov

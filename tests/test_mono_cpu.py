@@ -83,6 +83,20 @@ def test_hand_case_has_one_site_of_every_rule():
     assert mm.filter_set_order([1, 2, 3, 5, 8], [4, 0, 2, 1, 3], mm.HAND_MASK).tolist() == [2, 0, 1]
 
 
+def test_filter_set_order_on_a_long_read_equals_a_list_with_the_removed_keys_deleted():
+    """the model tests/test_gpu_chain_trips.py holds mono_order_kernel against, on a read of 290 cells with a random order: a `remove` moves no other key, so the
+    filtered order is the old one without the removed cells, each renamed to its rank among the survivors — stated here with plain lists"""
+    rng = np.random.default_rng(12)
+    snps = np.sort(rng.choice(np.arange(1, 301), size=290, replace=False))
+    order = rng.permutation(290)
+    removed = (rng.random(300) < 0.3).astype(np.uint8)
+    alive = [int(s) for s in snps if not removed[s - 1]]
+    want = [alive.index(int(snps[i])) for i in order if not removed[int(snps[i]) - 1]]
+    assert len(want) > 128 and len(want) < 290
+    got = mm.filter_set_order(snps, order, removed)
+    assert got.dtype == np.uint32 and got.tolist() == want and sorted(want) == list(range(len(alive)))
+
+
 def test_library_exports_the_entry_points(hip_lib):
     import ctypes
     L = ctypes.CDLL(os.path.join(ROOT, "floria_amd", "csrc", "libfloria_hip.so"))
