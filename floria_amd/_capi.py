@@ -113,7 +113,8 @@ class CAssembleOptions(C.Structure):
 
 class CMonoResult(C.Structure):
     _fields_ = [("n_contigs", C.c_uint32), ("read_off", u64p), ("old_read", u32p), ("removed", u8p),
-                ("n_removed_snps", C.c_uint64), ("n_removed_cells", C.c_uint64), ("n_dropped_reads", C.c_uint64)]
+                ("n_removed_snps", C.c_uint64), ("n_removed_cells", C.c_uint64), ("n_dropped_reads", C.c_uint64),
+                ("new_first", u32p), ("new_last", u32p)]
 
 
 def ptr(a, ctype):

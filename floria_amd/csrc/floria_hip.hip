@@ -2941,7 +2941,7 @@ int floria_hip_mono_timing(const floria_hip_ctx* ctx, double* ms6) {
 
 void floria_hip_mono_result_free(floria_mono_result* r) {
     if (!r) return;
-    free(r->read_off); free(r->old_read); free(r->removed); free(r);
+    free(r->read_off); free(r->old_read); free(r->removed); free(r->new_first); free(r->new_last); free(r);
 }
 
 int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n, const uint64_t* snp_off, double error, int with_set_order,
@@ -2976,7 +2976,8 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
         if (!M) return false;
         M->n_contigs = n;
         M->read_off = (uint64_t*)calloc(n + 1, 8); M->old_read = (uint32_t*)calloc(n_out + 1, 4); M->removed = (uint8_t*)calloc(n_mask + 1, 1);
-        return M->read_off && M->old_read && M->removed;
+        M->new_first = (uint32_t*)calloc(n_out + 1, 4); M->new_last = (uint32_t*)calloc(n_out + 1, 4);
+        return M->read_off && M->old_read && M->removed && M->new_first && M->new_last;
     };
     if (n == 0) {
         if (res) { if (!new_result(0, 0)) return give_up(fail(FLORIA_E_NOMEM, "calloc")); *res = M; }
@@ -3121,6 +3122,10 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     if (M) {
         memcpy(M->read_off, P.rp.data(), 8ull * (n + 1));
         if (R) memcpy(M->old_read, old_read.data(), 4 * R);
+        for (uint32_t c = 0; c < n; ++c) {                      // the survivors' new ends: the COUNT pass brought them back with the cell counts
+            const uint32_t* k = k3.data() + 3 * rp[c];
+            for (uint64_t i = P.rp[c]; i < P.rp[c + 1]; ++i) { M->new_first[i] = k[3 * (size_t)old_read[i] + 1]; M->new_last[i] = k[3 * (size_t)old_read[i] + 2]; }
+        }
         for (uint32_t c = 0; c < n; ++c) M->n_removed_snps += n_rm[c];
         M->n_removed_cells = cpi[n] - kept_cells; M->n_dropped_reads = Rin - R;
     }

@@ -272,16 +272,18 @@ Batch::Batch(Session& s, std::vector<ContigWork>& work, bool with_set_orders) : 
     // The Frags of all contigs go straight into the COMPACT wire form (floria_pileup_packed: a presence bit per SNP of a read's span, a 2-bit allele and a
     // quality byte per call — a fifth of the CSR bytes on the PCIe link), in ONE pinned buffer laid out field by field at the offsets
     // floria_hip_pack_pileups_batch uses, so that every field of a chunk of contigs is one DMA.  Alleles beyond the 2-bit envelope are refused here.
-    const size_t n = work.size();
+    // A contig that already has a handle (--pileup resident: assembled on the device) is not marshalled: only the others (host_ix_) are packed here.
+    for (size_t i = 0; i < work.size(); ++i) if (!work[i].handle) host_ix_.push_back(i);
+    const size_t n = host_ix_.size();
     std::vector<uint64_t> rp(n + 1, 0), cp(n + 1, 0), pb(n + 1, 0);
     for (size_t i = 0; i < n; ++i) {
         uint64_t C = 0, bits = 0;
-        for (const Frag& f : work[i].all_frags) {
+        for (const Frag& f : work[host_ix_[i]].all_frags) {
             if (f.last_position < f.first_position) throw Error(FLORIA_E_INVALID, "Frag with last_position < first_position");
             C += f.seq_dict.size(); bits += (uint64_t)f.last_position - f.first_position + 1;
         }
         if (bits >= (1ull << 32) || C >= (1ull << 32)) throw Error(FLORIA_E_UNSUPPORTED, "contig too large for one pileup (2^32 cells / span bits)");
-        rp[i + 1] = rp[i] + work[i].all_frags.size(); cp[i + 1] = cp[i] + C; pb[i + 1] = pb[i] + (bits + 7) / 8 + 1;
+        rp[i + 1] = rp[i] + work[host_ix_[i]].all_frags.size(); cp[i + 1] = cp[i] + C; pb[i + 1] = pb[i] + (bits + 7) / 8 + 1;
     }
     const uint64_t R = rp[n], C = cp[n];
     // set orders: only for the contigs that hold a fragment whose position set is not that of one CIGAR walk (every other contig's are emulated on the device)
@@ -289,7 +291,7 @@ Batch::Batch(Session& s, std::vector<ContigWork>& work, bool with_set_orders) : 
     uint64_t order_cells = 0;
     if (with_set_orders)
         for (size_t i = 0; i < n; ++i) {
-            for (const Frag& f : work[i].all_frags) if (f.other_set_order()) { needs_order[i] = 1; break; }
+            for (const Frag& f : work[host_ix_[i]].all_frags) if (f.other_set_order()) { needs_order[i] = 1; break; }
             if (needs_order[i]) order_cells += cp[i + 1] - cp[i];
         }
     size_t cur = 0;
@@ -303,7 +305,7 @@ Batch::Batch(Session& s, std::vector<ContigWork>& work, bool with_set_orders) : 
     memset(B + o_pr, 0, pb[n] + 16); memset(B + o_a2, 0, C / 4 + n + 16);
     piles_.resize(n);
     for (size_t i = 0; i < n; ++i) {
-        const std::vector<Frag>& fr = work[i].all_frags;
+        const std::vector<Frag>& fr = work[host_ix_[i]].all_frags;
         uint32_t* ro = (uint32_t*)(B + o_ro + 4 * (rp[i] + i)); uint32_t* bo = (uint32_t*)(B + o_bo + 4 * (rp[i] + i));
         uint32_t* fi = (uint32_t*)(B + o_fi + 4 * rp[i]);       uint32_t* la = (uint32_t*)(B + o_la + 4 * rp[i]);
         uint8_t* pr = (uint8_t*)(B + o_pr + pb[i]); uint8_t* a2 = (uint8_t*)(B + o_a2 + cp[i] / 4 + i); uint8_t* qu = (uint8_t*)(B + o_qu + cp[i]);
@@ -341,10 +343,11 @@ Batch::Batch(Session& s, std::vector<ContigWork>& work, bool with_set_orders) : 
         }
         piles_[i] = floria_pileup_packed{ro, fi, la, bo, pr, a2, qu, (uint32_t)fr.size(), so};
     }
-    handles_.assign(n, nullptr);
+    handles_.assign(work.size(), nullptr); owned_.assign(work.size(), 0);
+    for (size_t i = 0; i < work.size(); ++i) handles_[i] = work[i].handle.get();
 }
 Batch::~Batch() {
-    for (floria_hip_contig* h : handles_) if (h) floria_hip_contig_free(h);
+    for (size_t i = 0; i < handles_.size(); ++i) if (handles_[i] && owned_[i]) floria_hip_contig_free(handles_[i]);
     if (pinned_) floria_hip_host_free(pinned_);
 }
 
@@ -359,7 +362,18 @@ void Batch::generate_hap_graphs(const Options& o) {
     b0.push_back((uint32_t)bs.size());
     floria_params prm{o.epsilon, (uint32_t)o.max_ploidy, (uint32_t)o.max_number_solns, o.ploidy_sensitivity, o.stopping_heuristic ? 1 : 0};
     floria_block_result* res = nullptr;
-    check(floria_hip_phase_pileups_batch_packed(s_.ctx(), piles_.data(), (uint32_t)piles_.size(), bc.data(), bs.data(), be.data(), (uint32_t)bs.size(), &prm, &res, handles_.data()));
+    if (host_ix_.size() == work_.size()) {                                     // no contig came with a handle: upload + S1 as one pipelined call
+        check(floria_hip_phase_pileups_batch_packed(s_.ctx(), piles_.data(), (uint32_t)piles_.size(), bc.data(), bs.data(), be.data(), (uint32_t)bs.size(), &prm, &res, handles_.data()));
+        owned_.assign(work_.size(), 1);
+    } else {
+        // contigs of the batch that kept the host walk are uploaded first: every contig then has a handle, and S1 runs on the handles
+        if (!host_ix_.empty()) {
+            std::vector<floria_hip_contig*> up(host_ix_.size(), nullptr);
+            check(floria_hip_contig_upload_batch_packed(s_.ctx(), piles_.data(), (uint32_t)piles_.size(), up.data()));
+            for (size_t j = 0; j < host_ix_.size(); ++j) { handles_[host_ix_[j]] = up[j]; owned_[host_ix_[j]] = 1; }
+        }
+        check(floria_hip_phase_blocks_batch(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), bc.data(), bs.data(), be.data(), (uint32_t)bs.size(), &prm, &res));
+    }
     floria_hap_graph* hg = nullptr;
     int rc = floria_hip_hap_graph(s_.ctx(), res, &hg);
     if (rc) { floria_hip_block_result_free(res); check(rc); }
@@ -423,6 +437,78 @@ void Batch::stats_and_hapq(const Options& o) {
         w.hq.hapqs.assign(hq.begin() + k, hq.begin() + k + m); w.hq.rel_err.assign(rel.begin() + k, rel.begin() + k + m); w.hq.avg_err = avg[i];
         k += m;
     }
+    // ---- contigs whose Frags hold no cells (they came with a handle): what the writers read in seq_dict and snp_pos_to_seq_pos, one call each for the batch
+    std::vector<const floria_hip_contig*> rh;
+    std::vector<size_t> rix;
+    for (size_t i = 0; i < work_.size(); ++i) if (work_[i].handle) { rix.push_back(i); rh.push_back(handles_[i]); }
+    if (rh.empty()) return;
+    GroupCsr r;
+    std::vector<uint64_t> pos_off{0};
+    for (size_t c = 0; c < rix.size(); ++c) {
+        ContigWork& w = work_[rix[c]];
+        w.allele_off.assign(1, 0);
+        for (size_t q = 0; q < w.final_parts.size(); ++q) {
+            const SnpPosition lo = w.final_ranges[q].first, hi = w.final_ranges[q].second;
+            for (const Frag* f : w.final_parts[q]) r.reads.push_back((uint32_t)f->counter_id);
+            r.off.push_back(r.reads.size()); r.gc.push_back((uint32_t)c);
+            r.rng.push_back(lo); r.rng.push_back(hi);
+            const uint64_t len = hi < lo ? 0 : (uint64_t)hi - lo + 1;
+            pos_off.push_back(pos_off.back() + len);
+            w.allele_off.push_back(w.allele_off.back() + len);
+        }
+    }
+    const uint32_t nr = (uint32_t)r.gc.size();
+    if (!nr) return;
+    std::vector<uint32_t> counts(4 * pos_off.back() + 4, 0);
+    check(floria_hip_haploset_alleles(s_.ctx(), rh.data(), (uint32_t)rh.size(), r.gc.data(), r.off.data(), r.reads.data(), r.rng.data(), nr, pos_off.data(), counts.data()));
+    bytes_back += 16 * pos_off.back();
+    std::vector<uint32_t> left, right;
+    if (o.output_reads) {                                                      // write_reads' two lookups per (haploset, read)
+        left.assign(r.reads.size() + 1, FLORIA_SPAN_NONE); right.assign(r.reads.size() + 1, FLORIA_SPAN_NONE);
+        check(floria_hip_read_spans(s_.ctx(), rh.data(), (uint32_t)rh.size(), r.gc.data(), r.off.data(), r.reads.data(), r.rng.data(), nr, left.data(), right.data()));
+        bytes_back += 8 * r.reads.size();
+    }
+    size_t gi = 0;
+    for (size_t c = 0; c < rix.size(); ++c) {
+        ContigWork& w = work_[rix[c]];
+        const size_t m = w.final_parts.size();
+        w.allele_counts.assign(counts.begin() + 4 * pos_off[gi], counts.begin() + 4 * pos_off[gi + m]);
+        if (o.output_reads) {
+            w.span_left.assign(m, {}); w.span_right.assign(m, {});
+            for (size_t q = 0; q < m; ++q) {
+                w.span_left[q].assign(left.begin() + r.off[gi + q], left.begin() + r.off[gi + q + 1]);
+                w.span_right[q].assign(right.begin() + r.off[gi + q], right.begin() + r.off[gi + q + 1]);
+            }
+        }
+        gi += m;
+    }
+}
+
+std::string Batch::dump_handles() const {
+    std::string t;
+    for (size_t i = 0; i < work_.size(); ++i) {
+        const ContigWork& w = work_[i];
+        const floria_hip_contig* h = handles_[i];
+        if (!h) throw Error(FLORIA_E_INVALID, "dump_handles: contig " + w.name + " has no handle yet");
+        const size_t R = w.all_frags.size();
+        t += "#CONTIG\t" + w.name + "\t" + std::to_string(R) + "\n#IDS";
+        for (const Frag& f : w.all_frags) t += "\t" + f.id;
+        t += "\n";
+        std::vector<uint32_t> ro(R ? R + 1 : 0);
+        check(floria_hip_contig_download(h, FLORIA_FIELD_READ_OFF, ro.data(), 4 * ro.size()));
+        const size_t C = R ? ro[R] : 0;
+        const size_t words[8] = {ro.size(), R, R, C, C, 4 * R, 8 * R, C};
+        for (int field = 0; field <= FLORIA_FIELD_SET_ORDER; ++field) {
+            std::vector<uint32_t> v(words[field]);
+            const int rc = floria_hip_contig_download(h, field, v.data(), 4 * v.size());
+            if (field == FLORIA_FIELD_SET_ORDER && rc == FLORIA_E_INVALID) continue;       // the contig carries no set order
+            check(rc);
+            t += "#FIELD\t" + std::to_string(field);
+            for (uint32_t x : v) { t += '\t'; t += std::to_string(x); }
+            t += "\n";
+        }
+    }
+    return t;
 }
 
 std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPosition, SnpPosition>>> process_reads_for_final_parts(

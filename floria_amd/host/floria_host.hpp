@@ -69,6 +69,8 @@ struct Options {
     floria_realign_walk walk = {8, 8, 0, 0};
     bool pileup_device = false;         // --pileup host | device: frag_from_record's CIGAR walk on the host (default) or by floria_hip_pileup_records, one call per ingest round
     bool pileup_fused = false;          // --pileup fused: pileup_device, and the calls are realigned by the same device call (floria_hip_pileup_records_realign) instead of by realign()
+    bool pileup_resident = false;       // --pileup resident: the walk (and the realignment) by floria_hip_pileup_records_resident, the fragments assembled on the device from a plan made of
+                                        // headers (floria_hip_assemble_contigs_opt): the host holds header-only Frags and a handle per contig, no cell comes back
 };
 // "exact" | "block:STEP,RULE,TIE" (STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down) -> options.realign_walk / options.walk; anything else throws with the grammar
 void parse_realign_spec(const std::string& spec, Options& options);
@@ -327,6 +329,7 @@ private:
     floria_record_cells* cells_ = nullptr;
     std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
 };
+struct ContigPlan;
 class ContigIngest {
 public:
     // records of `contig` -> one Frag per passing alignment (file_reader.rs:343-430); with a queue the undecided realignments are deferred; with a RecordPileup the
@@ -337,9 +340,95 @@ public:
     ContigIngest(ContigIngest&&) noexcept;
     ContigIngest& operator=(ContigIngest&&) noexcept;
     std::pair<std::vector<Frag>, std::vector<Frag>> finish();              // combine_frags (:491-659) -> (frags with SNPs, frags without)
+    ContigPlan plan() const;                                      // the fragment plan of the records held (before finish()): --dump-plan under the routes that walk into Frags
 private:
     struct Impl;
     std::unique_ptr<Impl> p_;
+};
+
+// ---- --pileup resident: fragments planned from headers ------------------------------------------------------------------------------------
+// What combine_frags (file_reader.rs:491-659) reads of one passing alignment when it decides who is merged onto whom: its flags, its place among the contig's records
+// (Frag::counter_id before the sort) and the first / last SNP of its walk.  The host walk has them in its Frags, floria_hip_pileup_records_resident returns them in
+// its summary; no cell is needed.
+struct PlanRecord {
+    uint32_t rec = 0;                                    // index into BamFile::records of the segment
+    uint16_t flags = 0;
+    size_t counter_id = 0;
+    SnpPosition first = UINT32_MAX, last = 0;            // Frag::first_position / last_position of the walk; UINT32_MAX / 0: the record has no cell
+    bool has_cells() const { return first != UINT32_MAX; }
+};
+struct PlannedFrag {
+    std::vector<PlanRecord> parts;                       // merge order: the first is the base, each later one is `extend`ed onto it
+    std::vector<uint8_t> mate;                           // per part: 1 for the second mate's part (file_reader.rs:556-562)
+    SnpPosition first = UINT32_MAX, last = 0;            // of the merged fragment
+    size_t counter_id = 0;                               // the base's
+};
+struct ContigPlan {
+    std::vector<PlannedFrag> frags;                      // sorted by Frag::cmp: the pileup's read order
+    std::vector<PlannedFrag> snpless;                    // fragments whose parts hold no cell, in the order combine_frags yields them
+};
+// combine_frags on headers: `groups` = the passing records of every read name, in record order, names in the order of their first record; snp_to_gn as
+// VcfProfile::vcf_snp_pos_to_gn_pos_map of the contig.  A two-record paired group: sorted by (flags, Frag::cmp), flag 64 first -> (first, second), flag 128 first ->
+// (second, first), the extension marked as mate 1.  A lone primary record passes.  Anything else: no primary -> dropped; a gap of more than supp_aln_dist_cutoff bases
+// between consecutive sorted (first, last) intervals of the parts with cells -> the LAST primary alone; otherwise that primary, then every other part in record order.
+ContigPlan plan_contig(std::vector<std::vector<PlanRecord>>& groups, const std::map<SnpPosition, GnPosition>& snp_to_gn, int64_t supp_aln_dist_cutoff);
+// --dump-plan: "#CONTIG name n_frags n_snpless", then per fragment "F id first last part .." and per snpless fragment "S id part ..", a part as name:flag:pos:mate
+std::string plan_text(const std::string& contig, const ContigPlan& plan, const BamFile& bam);
+
+struct ContigHandle {                                    // an owned floria_hip_contig (freed on the thread that lets go of it: one host thread at a time per context)
+    floria_hip_contig* h = nullptr;
+    ContigHandle() = default;
+    explicit ContigHandle(floria_hip_contig* p) : h(p) {}
+    ContigHandle(ContigHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    ContigHandle& operator=(ContigHandle&& o) noexcept { if (this != &o) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ContigHandle(const ContigHandle&) = delete;
+    ContigHandle& operator=(const ContigHandle&) = delete;
+    ~ContigHandle() { reset(); }
+    void reset(floria_hip_contig* p = nullptr) { if (h) floria_hip_contig_free(h); h = p; }
+    floria_hip_contig* get() const { return h; }
+    explicit operator bool() const { return h != nullptr; }
+};
+// One contig of a resident round: header-only Frags (id, first / last position, first / last base, is_paired, sequences with --output-reads; NO seq_dict, qual_dict,
+// positions or snp_pos_to_seq_pos), the plan they came from, and after ResidentPileup::assemble the handle of the contig on the device.
+struct HeaderContig {
+    ContigPlan plan;
+    std::vector<Frag> all_frags, frags_without_snps;     // all_frags in plan order with counter_id == index
+    uint64_t part_cells = 0;                             // cells of all parts of all_frags (from cell_off): an upper bound of the merged count
+    size_t merged_frags = 0;                             // fragments with two or more parts that have cells
+    ContigHandle handle;
+};
+// The walks of one ingest round in ONE floria_hip_pileup_records_resident call (RecordPileup's record selection and host_contigs rule; with ref_seqs the calls are
+// realigned there, options.realign_walk / walk honoured), then per contig a plan from the summary, one floria_hip_assemble_contigs_opt call for the round and, with
+// --ignore-monomorphic, one floria_hip_drop_monomorphic call.  assemble() must run before the context's next floria_hip_pileup_records* call (include/floria_hip.h, RESIDENCY).
+class ResidentPileup {
+public:
+    ResidentPileup(Session& s, const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string* contigs, size_t n_contigs,
+                   const std::map<std::string, std::string>* ref_seqs = nullptr);
+    ~ResidentPileup();
+    ResidentPileup(const ResidentPileup&) = delete;
+    ResidentPileup& operator=(const ResidentPileup&) = delete;
+    bool on_table(size_t contig_index) const { return table_of_[contig_index] >= 0; }      // false: the contig keeps the host walk (or is unknown to the BAM / VCF)
+    HeaderContig plan(size_t contig_index) const;                                          // thread-safe: reads the summary
+    // planned[i] (may be null where !on_table(i)) for every contig of the constructor's list; fills planned[i]->handle and re-maps the Frags through the filter
+    void assemble(std::vector<HeaderContig*>& planned, bool derive_set_order, bool keep_seq_pos, bool ignore_monomorphic, double epsilon);
+    size_t records_sent = 0, blob_bytes = 0;
+    double kernel_ms = 0., h2d_ms = 0., d2h_ms = 0.;         // floria_hip_last_timing of the pileup call
+    double assemble_s = 0., filter_s = 0.;                   // wall seconds of the assemble and the filter call
+    double assemble_ms = 0., filter_ms = 0.;                 // their device-event totals
+    uint64_t bytes_back = 0;                                 // what the host received: the summary's arrays, the filter's three words per read, its mask and map
+    uint64_t removed_snps = 0, dropped_reads = 0;            // --ignore-monomorphic
+    std::vector<std::string> host_contigs;
+    floria_realign_counts counts = {};
+private:
+    Session& s_;
+    const BamFile& bam_;
+    const VcfProfile& vp_;
+    const Options& o_;
+    const std::string* contigs_;
+    floria_record_summary* summary_ = nullptr;
+    std::vector<int32_t> table_of_;                          // contig of the list -> contig of the SNP table, -1
+    std::vector<uint64_t> snp_count_;                        // per table contig
+    std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
 };
 std::pair<size_t, double> l_epsilon_auto_detect(const BamFile& bam);                   // :749-826
 // The same fed segment by segment (complete targets in header order, as BamStream::next yields them): done() once 1000 columns have been sampled,
@@ -379,6 +468,14 @@ struct ContigWork {
     std::vector<const Frag*> snpless;                                  // get_frags_in_snpless_gaps
     std::vector<double> stats;                                         // 4 per final haploset: cov, err, total_err, total_cov
     HapqResult hq;
+    // --pileup resident: the contig as assembled on the device (all_frags then are header-only, ResidentPileup).  Owned here; whoever hands the ContigWork to another
+    // thread resets it first (a context takes one host thread at a time).
+    ContigHandle handle;
+    uint64_t resident_cells = 0;                                       // cells of the parts of its fragments (floria_record_summary::cell_off): what --batch-cells counts for it
+    // ... and what the writers would have read in the cells, filled by Batch::stats_and_hapq for a contig with a handle:
+    std::vector<uint64_t> allele_off;                                  // [final haplosets + 1] positions before haploset k (its range length; 0 for an empty haploset)
+    std::vector<uint32_t> allele_counts;                               // [4 * allele_off.back()] floria_hip_haploset_alleles: set_to_seq_dict(.., false) over the range
+    std::vector<std::vector<uint32_t>> span_left, span_right;          // --output-reads: floria_hip_read_spans per final haploset, per read in final_parts[k] order
 };
 class Batch {
 public:
@@ -390,20 +487,29 @@ public:
     Batch& operator=(const Batch&) = delete;
     void generate_hap_graphs(const Options& options);                  // upload + S1 + hap graph for every contig (graph_processing.rs:325-372)
     void process_reads_for_final_parts(const Options& options);        // S2 for every contig, from path_parts / path_ranges
-    void stats_and_hapq(const Options& options);                       // get_errors_cov_from_frags + get_hapq for every final haploset
+    void stats_and_hapq(const Options& options);                       // get_errors_cov_from_frags + get_hapq for every final haploset; for contigs with a handle also the
+                                                                       // writers' allele tables and, with --output-reads, their trim lookups
+    // --dump-handles (tests): per contig "#CONTIG name n_reads", "#IDS id ..", then "#FIELD k v .." for floria_hip_contig_download fields 0-6 as uint32 words and
+    // field 7 where the contig carries a set order; valid once generate_hap_graphs has run (every contig then has a handle, whichever route made it)
+    std::string dump_handles() const;
+    uint64_t bytes_back = 0;                                           // bytes of the allele tables and trim lookups received
 private:
     Session& s_;
     std::vector<ContigWork>& work_;
     void* pinned_ = nullptr;
+    std::vector<size_t> host_ix_;                                      // the contigs without a handle of their own: marshalled here, piles_[j] is contig host_ix_[j]
     std::vector<floria_pileup_packed> piles_;
-    std::vector<floria_hip_contig*> handles_;
+    std::vector<floria_hip_contig*> handles_;                          // per contig: the ContigWork's own handle, or the one uploaded here (owned_)
+    std::vector<char> owned_;
 };
 // utils_frags::remove_monomorphic_allele (utils_frags.rs:713-772, --ignore-monomorphic): SNPs where one allele carries (almost) all of the
 // phred weight are dropped from every read; reads left without SNPs are dropped; the rest is sorted and renumbered
 std::vector<Frag> remove_monomorphic_allele(std::vector<Frag> frags, double error);
 // write_reads + write_nosnp_reads (file_writer.rs:86-150, 370-560, --output-reads): long_reads/{i}_part.fastq, short_reads/{i}_part_paired{1,2}.fastq, snpless*.fastq
+// span_left / span_right (both or neither): floria_hip_read_spans' words per haploset and per read in part[i] order, for Frags that hold no snp_pos_to_seq_pos
 void write_reads(const std::vector<std::vector<const Frag*>>& part, const std::vector<std::pair<SnpPosition, SnpPosition>>& snp_range_parts_vec, const std::string& out_bam_part_dir,
-                 bool extend_read_clipping, const std::vector<uint8_t>& hapqs, bool gzip);
+                 bool extend_read_clipping, const std::vector<uint8_t>& hapqs, bool gzip, const std::vector<std::vector<uint32_t>>* span_left = nullptr,
+                 const std::vector<std::vector<uint32_t>>* span_right = nullptr);
 void write_nosnp_reads(const std::string& out_bam_part_dir, const std::vector<const Frag*>& snpless_frags, bool gzip);
 // scores the queued realignment windows on the device (floria_hip_realign; with a walk floria_hip_realign_walk) and stores the winning alleles where they belong
 void realign_queue_on_device(Session& s, RealignQueue& queue, const floria_realign_walk* walk = nullptr);

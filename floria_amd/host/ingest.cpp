@@ -274,7 +274,7 @@ void frag_sequences(Frag& frag, const BamRecord& rec, bool keep_sequences) {
     }
 }
 
-struct Tagged { uint16_t flags; Frag frag; };
+struct Tagged { uint16_t flags; Frag frag; uint32_t rec_ix = 0; };
 
 // global alignment score of two byte strings, affine gaps: a gap of length n costs open + (n - 1) * extend
 int nw_affine_score(const unsigned char* q, int nq, const unsigned char* r, int nr) {
@@ -925,7 +925,7 @@ ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Optio
         const bool on_device = device_cells && device_cells->cells(rec_ix, dc);
         Frag fr = on_device ? frag_from_cells(rec, dc, this_count, o.output_reads) : frag_from_record(rec, snp_positions, pos_allele_map, this_count, o.output_reads);
         if (ref_seq && !(on_device && device_cells->realigned)) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue, o.realign_walk ? &o.walk : nullptr);             // :416-423
-        buckets[ins.first->second].push_back({rec.flags, std::move(fr)});
+        buckets[ins.first->second].push_back({rec.flags, std::move(fr), rec_ix});
     }
 }
 
@@ -938,78 +938,102 @@ bool RecordPileup::cells(uint32_t rec_ix, Cells& out) const {
     out = {cells_->snp + b, cells_->allele + b, cells_->qual + b, cells_->seq_pos + b, (size_t)(e - b), cells_->ref_end[s - 1]};
     return true;
 }
-RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
-                           const std::map<std::string, std::string>* ref_seqs) {
-    const bool filter_supplementary = true, use_supplementary = !o.dont_use_supp_aln;
-    // the SNP table of the round's contigs: positions in order, REF + ALT bytes; a contig the device's numbering (rank + 1) would not match stays on the host
+namespace {
+// The records of a round that go to the device, as floria_hip_pileup_records* takes them (shared by --pileup device / fused / resident): every record of the given
+// contigs that passes alignment_passed_check, as offsets into the stretch of the segment's inflated buffer that holds them; the SNP table of those contigs; with
+// ref_seqs their reference sequences back to back.  A contig the device's numbering (rank + 1) would not match, or with a site of more than FLORIA_MAX_ALLELES
+// alleles, is not sent (host_contigs).
+struct RecordSelection {
     std::vector<uint64_t> snp_off{0};
     std::vector<int64_t> snp_pos;
     std::vector<uint8_t> alleles, n_alleles;
     std::vector<int32_t> pos;
     std::vector<uint16_t> flags;
     std::vector<uint32_t> contig, n_cigar, l_seq, rec_of;
-    std::vector<const unsigned char*> cig_p, seq_p, qual_p;
+    std::vector<uint64_t> cigar_off, seq_off, qual_off;
     std::vector<uint64_t> ref_off{0};                                          // ref_seqs: the table's contigs' sequences back to back
     std::vector<uint8_t> ref_bytes;
-    for (size_t ci = 0; ci < n_contigs; ++ci) {
-        const auto tid_it = std::find(bam.target_names.begin(), bam.target_names.end(), contigs[ci]);
-        const auto counters = vp.vcf_pos_to_snp_counter_map.find(contigs[ci]);
-        const auto pam = vp.vcf_pos_allele_map.find(contigs[ci]);
-        if (tid_it == bam.target_names.end() || counters == vp.vcf_pos_to_snp_counter_map.end() || pam == vp.vcf_pos_allele_map.end()) continue;
-        // both maps in lockstep: the same positions, the counters 1, 2, .. in position order, 1 to FLORIA_MAX_ALLELES alleles at every site
-        bool ok = counters->second.size() == pam->second.size();
-        SnpPosition rank = 0;
-        auto al = pam->second.begin();
-        for (auto ct = counters->second.begin(); ok && ct != counters->second.end(); ++ct, ++al)
-            ok = ct->first == al->first && ct->second == ++rank && !al->second.empty() && al->second.size() <= FLORIA_MAX_ALLELES;
-        if (!ok) { host_contigs.push_back(contigs[ci]); continue; }
-        const uint32_t table_ix = (uint32_t)snp_off.size() - 1;
-        for (const auto& kv : pam->second) {
-            snp_pos.push_back((int64_t)kv.first);
-            for (size_t a = 0; a < FLORIA_MAX_ALLELES; ++a) alleles.push_back(a < kv.second.size() ? kv.second[a] : 0);
-            n_alleles.push_back((uint8_t)kv.second.size());
+    std::vector<std::string> host_contigs;
+    std::vector<int32_t> table_of;                                             // contig of the list -> contig of the table, -1: not sent
+    size_t blob_bytes = 0;
+    floria_alignments A{};
+    floria_snp_table S{};
+    floria_ref_seqs F{};
+    size_t n() const { return pos.size(); }
+    RecordSelection(const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs, const std::map<std::string, std::string>* ref_seqs) {
+        const bool filter_supplementary = true, use_supplementary = !o.dont_use_supp_aln;
+        std::vector<const unsigned char*> cig_p, seq_p, qual_p;
+        table_of.assign(n_contigs, -1);
+        for (size_t ci = 0; ci < n_contigs; ++ci) {
+            const auto tid_it = std::find(bam.target_names.begin(), bam.target_names.end(), contigs[ci]);
+            const auto counters = vp.vcf_pos_to_snp_counter_map.find(contigs[ci]);
+            const auto pam = vp.vcf_pos_allele_map.find(contigs[ci]);
+            if (tid_it == bam.target_names.end() || counters == vp.vcf_pos_to_snp_counter_map.end() || pam == vp.vcf_pos_allele_map.end()) continue;
+            // both maps in lockstep: the same positions, the counters 1, 2, .. in position order, 1 to FLORIA_MAX_ALLELES alleles at every site
+            bool ok = counters->second.size() == pam->second.size();
+            SnpPosition rank = 0;
+            auto al = pam->second.begin();
+            for (auto ct = counters->second.begin(); ok && ct != counters->second.end(); ++ct, ++al)
+                ok = ct->first == al->first && ct->second == ++rank && !al->second.empty() && al->second.size() <= FLORIA_MAX_ALLELES;
+            if (!ok) { host_contigs.push_back(contigs[ci]); continue; }
+            const uint32_t table_ix = (uint32_t)snp_off.size() - 1;
+            table_of[ci] = (int32_t)table_ix;
+            for (const auto& kv : pam->second) {
+                snp_pos.push_back((int64_t)kv.first);
+                for (size_t a = 0; a < FLORIA_MAX_ALLELES; ++a) alleles.push_back(a < kv.second.size() ? kv.second[a] : 0);
+                n_alleles.push_back((uint8_t)kv.second.size());
+            }
+            snp_off.push_back(snp_pos.size());
+            if (ref_seqs) {
+                const auto fa = ref_seqs->find(contigs[ci]);
+                if (fa != ref_seqs->end()) ref_bytes.insert(ref_bytes.end(), fa->second.begin(), fa->second.end());
+                ref_off.push_back(ref_bytes.size());
+            }
+            for (const uint32_t rec_ix : bam.by_tid[(size_t)(tid_it - bam.target_names.begin())]) {
+                const BamRecord& rec = bam.records[rec_ix];
+                if (!alignment_passed_check(rec.flags, rec.mapq, use_supplementary, filter_supplementary, o.mapq_cutoff).first) continue;
+                pos.push_back(rec.pos); flags.push_back(rec.flags); contig.push_back(table_ix); n_cigar.push_back((uint32_t)rec.cigar.n); l_seq.push_back((uint32_t)rec.seq.n);
+                cig_p.push_back(rec.cigar.p); seq_p.push_back(rec.seq.packed); qual_p.push_back(rec.qual.p); rec_of.push_back(rec_ix);
+            }
         }
-        snp_off.push_back(snp_pos.size());
-        if (ref_seqs) {
-            const auto fa = ref_seqs->find(contigs[ci]);
-            if (fa != ref_seqs->end()) ref_bytes.insert(ref_bytes.end(), fa->second.begin(), fa->second.end());
-            ref_off.push_back(ref_bytes.size());
+        const size_t n = pos.size();
+        if (n == 0) return;
+        // the stretch of the inflated buffer that holds these records' CIGARs, bases and qualities (a round's contigs are neighbours in a sorted BAM)
+        const unsigned char *lo = cig_p[0], *hi = cig_p[0];
+        for (size_t i = 0; i < n; ++i) {
+            lo = std::min({lo, cig_p[i], seq_p[i], qual_p[i]});
+            hi = std::max({hi, cig_p[i] + 4 * (size_t)n_cigar[i], seq_p[i] + ((size_t)l_seq[i] + 1) / 2, qual_p[i] + l_seq[i]});
         }
-        for (const uint32_t rec_ix : bam.by_tid[(size_t)(tid_it - bam.target_names.begin())]) {
-            const BamRecord& rec = bam.records[rec_ix];
-            if (!alignment_passed_check(rec.flags, rec.mapq, use_supplementary, filter_supplementary, o.mapq_cutoff).first) continue;
-            pos.push_back(rec.pos); flags.push_back(rec.flags); contig.push_back(table_ix); n_cigar.push_back((uint32_t)rec.cigar.n); l_seq.push_back((uint32_t)rec.seq.n);
-            cig_p.push_back(rec.cigar.p); seq_p.push_back(rec.seq.packed); qual_p.push_back(rec.qual.p); rec_of.push_back(rec_ix);
-        }
+        cigar_off.resize(n); seq_off.resize(n); qual_off.resize(n);
+        for (size_t i = 0; i < n; ++i) { cigar_off[i] = (uint64_t)(cig_p[i] - lo); seq_off[i] = (uint64_t)(seq_p[i] - lo); qual_off[i] = (uint64_t)(qual_p[i] - lo); }
+        blob_bytes = (size_t)(hi - lo);
+        A.blob = lo; A.blob_bytes = blob_bytes; A.n_records = (uint32_t)n; A.pos = pos.data(); A.flags = flags.data(); A.contig = contig.data();
+        A.cigar_off = cigar_off.data(); A.n_cigar = n_cigar.data(); A.seq_off = seq_off.data(); A.l_seq = l_seq.data(); A.qual_off = qual_off.data();
+        S.n_contigs = (uint32_t)snp_off.size() - 1; S.snp_off = snp_off.data(); S.snp_pos = snp_pos.data(); S.alleles = alleles.data(); S.n_alleles = n_alleles.data();
+        F.n_contigs = S.n_contigs; F.seq_off = ref_off.data(); F.seq = ref_bytes.data();
     }
-    const size_t n = pos.size();
+    RecordSelection(const RecordSelection&) = delete;
+    RecordSelection& operator=(const RecordSelection&) = delete;
+};
+}  // namespace
+
+RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
+                           const std::map<std::string, std::string>* ref_seqs) {
+    RecordSelection sel(bam, vp, o, contigs, n_contigs, ref_seqs);
+    host_contigs = sel.host_contigs;
+    const size_t n = sel.n();
     records_sent = n;
     if (n == 0) return;
-    // the stretch of the inflated buffer that holds these records' CIGARs, bases and qualities (a round's contigs are neighbours in a sorted BAM)
-    const unsigned char *lo = cig_p[0], *hi = cig_p[0];
-    for (size_t i = 0; i < n; ++i) {
-        lo = std::min({lo, cig_p[i], seq_p[i], qual_p[i]});
-        hi = std::max({hi, cig_p[i] + 4 * (size_t)n_cigar[i], seq_p[i] + ((size_t)l_seq[i] + 1) / 2, qual_p[i] + l_seq[i]});
-    }
-    std::vector<uint64_t> cigar_off(n), seq_off(n), qual_off(n);
-    for (size_t i = 0; i < n; ++i) { cigar_off[i] = (uint64_t)(cig_p[i] - lo); seq_off[i] = (uint64_t)(seq_p[i] - lo); qual_off[i] = (uint64_t)(qual_p[i] - lo); }
-    blob_bytes = (size_t)(hi - lo);
-    floria_alignments A{};
-    A.blob = lo; A.blob_bytes = blob_bytes; A.n_records = (uint32_t)n; A.pos = pos.data(); A.flags = flags.data(); A.contig = contig.data();
-    A.cigar_off = cigar_off.data(); A.n_cigar = n_cigar.data(); A.seq_off = seq_off.data(); A.l_seq = l_seq.data(); A.qual_off = qual_off.data();
-    floria_snp_table S{};
-    S.n_contigs = (uint32_t)snp_off.size() - 1; S.snp_off = snp_off.data(); S.snp_pos = snp_pos.data(); S.alleles = alleles.data(); S.n_alleles = n_alleles.data();
+    blob_bytes = sel.blob_bytes;
     if (ref_seqs) {
-        floria_ref_seqs F{};
-        F.n_contigs = S.n_contigs; F.seq_off = ref_off.data(); F.seq = ref_bytes.data();
-        if (const int rc = floria_hip_pileup_records_realign(session.ctx(), &A, &S, &F, o.realign_walk ? &o.walk : nullptr, &cells_, &counts))
+        if (const int rc = floria_hip_pileup_records_realign(session.ctx(), &sel.A, &sel.S, &sel.F, o.realign_walk ? &o.walk : nullptr, &cells_, &counts))
             throw Error(rc, std::string("floria_hip_pileup_records_realign: ") + floria_hip_last_error());
         realigned = true;
-    } else if (const int rc = floria_hip_pileup_records(session.ctx(), &A, &S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
+    } else if (const int rc = floria_hip_pileup_records(session.ctx(), &sel.A, &sel.S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
     floria_timing tm;
     if (floria_hip_last_timing(session.ctx(), &tm) == 0) { kernel_ms = tm.pileup_ms; h2d_ms = tm.h2d_ms; d2h_ms = tm.d2h_ms; }
     slot_.assign(bam.records.size(), 0);
-    for (size_t i = 0; i < n; ++i) slot_[rec_of[i]] = (uint32_t)i + 1;
+    for (size_t i = 0; i < n; ++i) slot_[sel.rec_of[i]] = (uint32_t)i + 1;
 }
 
 std::pair<std::vector<Frag>, std::vector<Frag>> ContigIngest::finish() {
@@ -1081,6 +1105,224 @@ std::pair<std::vector<Frag>, std::vector<Frag>> ContigIngest::finish() {
     for (Frag& f : ref_frags) (f.seq_dict.empty() ? out.second : out.first).push_back(std::move(f));
     buckets.clear();
     return out;
+}
+
+// ---- --pileup resident: combine_frags on headers -----------------------------------------------------------------------------------------------
+// The decisions of finish() above restated on (flags, counter_id, first, last) alone.  A record without cells has first = UINT32_MAX and last = 0, what its Frag
+// has in the host route, so the sort of a pair, the intervals of a supplementary group and the merged ends come out as they do there.
+ContigPlan plan_contig(std::vector<std::vector<PlanRecord>>& groups, const std::map<SnpPosition, GnPosition>& snp_to_gn, int64_t supp_aln_dist_cutoff) {
+    const auto frag_less = [](SnpPosition af, SnpPosition al, size_t ac, SnpPosition bf, SnpPosition bl, size_t bc) {      // Frag::cmp
+        if (af != bf) return af < bf;
+        if (al != bl) return al > bl;
+        return ac < bc;
+    };
+    const auto paired = [](const PlanRecord& r) { return (r.flags & F_PAIRED1) || (r.flags & F_PAIRED2); };
+    ContigPlan out;
+    for (auto& g : groups) {
+        PlannedFrag pf;
+        if (g.size() == 2 && paired(g[0]) && paired(g[1])) {
+            std::sort(g.begin(), g.end(), [&](const PlanRecord& a, const PlanRecord& b) {
+                return a.flags != b.flags ? a.flags < b.flags : frag_less(a.first, a.last, a.counter_id, b.first, b.last, b.counter_id);
+            });
+            size_t ff, sf;
+            if ((g[0].flags & F_PAIRED1) == F_PAIRED1) { ff = 0; sf = 1; }
+            else if ((g[0].flags & F_PAIRED2) == F_PAIRED2) { ff = 1; sf = 0; }
+            else continue;
+            pf.parts = {g[ff], g[sf]}; pf.mate = {0, 1};
+        } else if (g.size() == 1 && (g[0].flags & F_SUPP) == 0) {
+            pf.parts = {g[0]}; pf.mate = {0};
+        } else {
+            std::vector<std::pair<SnpPosition, SnpPosition>> supp_intervals;
+            for (const PlanRecord& r : g) if (r.has_cells()) supp_intervals.push_back({r.first, r.last});
+            std::sort(supp_intervals.begin(), supp_intervals.end());
+            bool take_primary_only = false;
+            for (size_t i = 0; i + 1 < supp_intervals.size(); ++i)
+                if ((int64_t)snp_to_gn.at(supp_intervals[i + 1].first) - (int64_t)snp_to_gn.at(supp_intervals[i].second) > supp_aln_dist_cutoff) { take_primary_only = true; break; }
+            int primary = -1;
+            for (size_t i = 0; i < g.size(); ++i) if ((g[i].flags & F_SUPP) != F_SUPP) primary = (int)i;             // the LAST primary wins (:606-614)
+            if (primary < 0) continue;                                                                              // supplementary records only
+            pf.parts.push_back(g[(size_t)primary]);
+            if (!take_primary_only) for (size_t i = 0; i < g.size(); ++i) if ((int)i != primary) pf.parts.push_back(g[i]);
+            pf.mate.assign(pf.parts.size(), 0);
+        }
+        for (const PlanRecord& r : pf.parts) { pf.first = std::min(pf.first, r.first); pf.last = std::max(pf.last, r.last); }
+        pf.counter_id = pf.parts[0].counter_id;
+        (pf.first == UINT32_MAX ? out.snpless : out.frags).push_back(std::move(pf));
+    }
+    std::sort(out.frags.begin(), out.frags.end(), [&](const PlannedFrag& a, const PlannedFrag& b) { return frag_less(a.first, a.last, a.counter_id, b.first, b.last, b.counter_id); });
+    return out;
+}
+
+std::string plan_text(const std::string& contig, const ContigPlan& plan, const BamFile& bam) {
+    std::string t = "#CONTIG\t" + contig + "\t" + std::to_string(plan.frags.size()) + "\t" + std::to_string(plan.snpless.size()) + "\n";
+    const auto parts = [&](const PlannedFrag& f) {
+        for (size_t k = 0; k < f.parts.size(); ++k) {
+            const BamRecord& r = bam.records[f.parts[k].rec];
+            t += "\t" + std::string(r.qname) + ":" + std::to_string(r.flags) + ":" + std::to_string(r.pos) + ":" + std::to_string((int)f.mate[k]);
+        }
+        t += "\n";
+    };
+    for (const PlannedFrag& f : plan.frags) {
+        t += "F\t" + std::string(bam.records[f.parts[0].rec].qname) + "\t" + std::to_string(f.first) + "\t" + std::to_string(f.last);
+        parts(f);
+    }
+    for (const PlannedFrag& f : plan.snpless) { t += "S\t" + std::string(bam.records[f.parts[0].rec].qname); parts(f); }
+    return t;
+}
+
+ContigPlan ContigIngest::plan() const {
+    if (p_->buckets.empty()) return {};
+    std::vector<std::vector<PlanRecord>> groups(p_->buckets.size());
+    for (size_t b = 0; b < groups.size(); ++b)
+        for (const Tagged& t : p_->buckets[b]) {
+            PlanRecord r;
+            r.rec = t.rec_ix; r.flags = t.flags; r.counter_id = t.frag.counter_id; r.first = t.frag.first_position; r.last = t.frag.last_position;
+            groups[b].push_back(r);
+        }
+    return plan_contig(groups, *p_->snp_to_gn, p_->supp_aln_dist_cutoff);
+}
+
+ResidentPileup::~ResidentPileup() { floria_hip_record_summary_free(summary_); }
+ResidentPileup::ResidentPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
+                               const std::map<std::string, std::string>* ref_seqs)
+    : s_(session), bam_(bam), vp_(vp), o_(o), contigs_(contigs) {
+    RecordSelection sel(bam, vp, o, contigs, n_contigs, ref_seqs);
+    host_contigs = sel.host_contigs;
+    table_of_ = sel.table_of;
+    for (size_t c = 0; c + 1 < sel.snp_off.size(); ++c) snp_count_.push_back(sel.snp_off[c + 1] - sel.snp_off[c]);
+    const size_t n = sel.n();
+    records_sent = n;
+    if (n == 0) return;
+    blob_bytes = sel.blob_bytes;
+    if (const int rc = floria_hip_pileup_records_resident(session.ctx(), &sel.A, &sel.S, ref_seqs ? &sel.F : nullptr, o.realign_walk ? &o.walk : nullptr, &summary_))
+        throw Error(rc, std::string("floria_hip_pileup_records_resident: ") + floria_hip_last_error());
+    counts = summary_->counts;
+    floria_timing tm;
+    if (floria_hip_last_timing(session.ctx(), &tm) == 0) { kernel_ms = tm.pileup_ms; h2d_ms = tm.h2d_ms; d2h_ms = tm.d2h_ms; }
+    bytes_back += (uint64_t)n * 24 + 8;                                        // cell_off, first_snp, last_snp, ref_end
+    slot_.assign(bam.records.size(), 0);
+    for (size_t i = 0; i < n; ++i) slot_[sel.rec_of[i]] = (uint32_t)i + 1;
+}
+
+HeaderContig ResidentPileup::plan(size_t ci) const {
+    HeaderContig hc;
+    if (!summary_ || table_of_[ci] < 0) return hc;
+    const std::string& contig = contigs_[ci];
+    const auto tid_it = std::find(bam_.target_names.begin(), bam_.target_names.end(), contig);
+    if (tid_it == bam_.target_names.end()) return hc;
+    const bool filter_supplementary = true, use_supplementary = !o_.dont_use_supp_aln;
+    // read name -> its passing alignments in record order, as ContigIngest buckets them
+    std::unordered_map<std::string_view, size_t> name_ix;
+    std::vector<std::vector<PlanRecord>> groups;
+    size_t count = 0;
+    for (const uint32_t rec_ix : bam_.by_tid[(size_t)(tid_it - bam_.target_names.begin())]) {
+        const BamRecord& rec = bam_.records[rec_ix];
+        const size_t this_count = count++;
+        if (!alignment_passed_check(rec.flags, rec.mapq, use_supplementary, filter_supplementary, o_.mapq_cutoff).first) continue;
+        const uint32_t s = slot_[rec_ix];
+        if (!s) throw Error(FLORIA_E_INVALID, "resident pileup: a passing record of contig " + contig + " was not sent");
+        auto ins = name_ix.emplace(rec.qname, groups.size());
+        if (ins.second) groups.emplace_back();
+        PlanRecord r;
+        r.rec = rec_ix; r.flags = rec.flags; r.counter_id = this_count;
+        if (summary_->cell_off[s] > summary_->cell_off[s - 1]) { r.first = summary_->first_snp[s - 1]; r.last = summary_->last_snp[s - 1]; }
+        groups[ins.first->second].push_back(r);
+    }
+    hc.plan = plan_contig(groups, vp_.vcf_snp_pos_to_gn_pos_map.at(contig), o_.supp_aln_dist_cutoff);
+    // the header Frag of a planned fragment: the base's identity, the ends combine_frags gives the merged one, the second mate's bases where there is one
+    const auto header = [&](const PlanRecord& r, bool keep_sequences) {
+        const BamRecord& rec = bam_.records[r.rec];
+        Frag f = frag_without_calls(rec, r.counter_id);
+        f.last_pos_base = (GnPosition)summary_->ref_end[slot_[r.rec] - 1];
+        frag_sequences(f, rec, keep_sequences);
+        return f;
+    };
+    const auto merged = [&](const PlannedFrag& pf, bool with_cells) {
+        Frag f = header(pf.parts[0], o_.output_reads);
+        size_t parts_with_cells = pf.parts[0].has_cells() ? 1 : 0;
+        for (size_t k = 1; k < pf.parts.size(); ++k) {
+            Frag g = header(pf.parts[k], o_.output_reads && pf.mate[k]);
+            f.first_pos_base = std::min(f.first_pos_base, g.first_pos_base);
+            f.last_pos_base = std::min(f.last_pos_base, g.last_pos_base);                  // (min, as in the reference, :547)
+            if (pf.mate[k]) { f.seq_len[1] = g.seq_len[0]; f.seq_string[1] = std::move(g.seq_string[0]); f.qual_string[1] = std::move(g.qual_string[0]); }
+            if (pf.parts[k].has_cells()) { f.merged_positions = true; ++parts_with_cells; }
+        }
+        f.first_position = pf.first; f.last_position = pf.last;
+        if (with_cells) {
+            if (parts_with_cells >= 2) ++hc.merged_frags;
+            for (const PlanRecord& r : pf.parts) { const uint32_t s = slot_[r.rec]; hc.part_cells += summary_->cell_off[s] - summary_->cell_off[s - 1]; }
+        }
+        return f;
+    };
+    hc.all_frags.reserve(hc.plan.frags.size());
+    for (const PlannedFrag& pf : hc.plan.frags) { hc.all_frags.push_back(merged(pf, true)); hc.all_frags.back().counter_id = hc.all_frags.size() - 1; }
+    for (const PlannedFrag& pf : hc.plan.snpless) hc.frags_without_snps.push_back(merged(pf, false));
+    return hc;
+}
+
+void ResidentPileup::assemble(std::vector<HeaderContig*>& planned, bool derive_set_order, bool keep_seq_pos, bool ignore_monomorphic, double epsilon) {
+    if (!summary_) return;                                                                 // nothing was sent: no contig of the round has a fragment
+    const size_t nt = snp_count_.size();
+    std::vector<HeaderContig*> by_table(nt, nullptr);
+    for (size_t ci = 0; ci < planned.size(); ++ci) if (table_of_[ci] >= 0) by_table[(size_t)table_of_[ci]] = planned[ci];
+    std::vector<uint64_t> frag_off{0}, part_off{0};
+    std::vector<uint32_t> part_rec;
+    std::vector<uint8_t> part_mate;
+    for (size_t t = 0; t < nt; ++t) {
+        if (by_table[t])
+            for (const PlannedFrag& pf : by_table[t]->plan.frags) {
+                for (size_t k = 0; k < pf.parts.size(); ++k) { part_rec.push_back(slot_[pf.parts[k].rec] - 1); part_mate.push_back(pf.mate[k]); }
+                part_off.push_back(part_rec.size());
+            }
+        frag_off.push_back(part_off.size() - 1);
+    }
+    if (part_rec.empty()) return;                                                          // no fragment with a cell in the whole round
+    floria_fragment_plan plan{};
+    plan.n_contigs = (uint32_t)nt; plan.frag_off = frag_off.data(); plan.part_off = part_off.data(); plan.part_rec = part_rec.data(); plan.set_order = nullptr;
+    floria_assemble_options opts{};
+    opts.flags = (derive_set_order ? FLORIA_ASM_DERIVE_SET_ORDER : 0u) | (keep_seq_pos ? FLORIA_ASM_KEEP_SEQ_POS : 0u);
+    opts.part_mate = keep_seq_pos ? part_mate.data() : nullptr;
+    const auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    std::vector<floria_hip_contig*> raw(nt, nullptr);
+    double t0 = now();
+    if (const int rc = floria_hip_assemble_contigs_opt(s_.ctx(), summary_, &plan, &opts, raw.data()))
+        throw Error(rc, std::string("floria_hip_assemble_contigs_opt: ") + floria_hip_last_error());
+    std::vector<ContigHandle> handles(nt);
+    for (size_t t = 0; t < nt; ++t) handles[t].reset(raw[t]);
+    assemble_s += now() - t0;
+    floria_timing tm;
+    if (floria_hip_last_timing(s_.ctx(), &tm) == 0) assemble_ms += tm.total_ms;
+    if (ignore_monomorphic) {                                                              // remove_monomorphic_allele (floria.rs:315-317) on the handles
+        t0 = now();
+        std::vector<uint64_t> snp_off{0};
+        for (size_t t = 0; t < nt; ++t) snp_off.push_back(snp_off.back() + snp_count_[t]);
+        std::vector<floria_hip_contig*> out(nt, nullptr);
+        floria_mono_result* res = nullptr;
+        if (const int rc = floria_hip_drop_monomorphic(s_.ctx(), raw.data(), (uint32_t)nt, snp_off.data(), epsilon, derive_set_order ? 1 : 0, out.data(), &res))
+            throw Error(rc, std::string("floria_hip_drop_monomorphic: ") + floria_hip_last_error());
+        for (size_t t = 0; t < nt; ++t) handles[t].reset(out[t]);                          // (frees the inputs)
+        uint64_t reads_in = 0;
+        for (size_t t = 0; t < nt; ++t) {
+            HeaderContig* hc = by_table[t];
+            const uint64_t off = res->read_off[t], n_new = res->read_off[t + 1] - off;
+            if (!hc) continue;
+            reads_in += hc->all_frags.size();
+            std::vector<Frag> kept;
+            kept.reserve(n_new);
+            for (uint64_t r = 0; r < n_new; ++r) {                                         // drop, reorder, renumber; the survivors' ends come back with the map
+                Frag& f = hc->all_frags[res->old_read[off + r]];
+                f.first_position = res->new_first[off + r]; f.last_position = res->new_last[off + r]; f.counter_id = (size_t)r;
+                kept.push_back(std::move(f));
+            }
+            hc->all_frags = std::move(kept);
+        }
+        removed_snps += res->n_removed_snps; dropped_reads += res->n_dropped_reads;
+        bytes_back += 12 * reads_in + snp_off.back();
+        floria_hip_mono_result_free(res);
+        filter_s += now() - t0;
+        if (floria_hip_last_timing(s_.ctx(), &tm) == 0) filter_ms += tm.total_ms;
+    }
+    for (size_t t = 0; t < nt; ++t) if (by_table[t]) by_table[t]->handle = std::move(handles[t]);
 }
 
 std::pair<std::vector<Frag>, std::vector<Frag>> get_frags_from_bamvcf_rewrite(const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string& contig,

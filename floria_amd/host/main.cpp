@@ -19,6 +19,12 @@
 // device: one floria_hip_pileup_records call per ingest round for every record that passes the alignment filter, the Frags filled from its cells (same files).
 // fused: device, with the realignment of the calls done by the same call (floria_hip_pileup_records_realign) before the cells come back; without realignment (--no-realign)
 // it is device.  Same files.
+// resident: one floria_hip_pileup_records_resident call per ingest round (re-aligned there unless --no-realign); the cells stay on the device.  Per contig a fragment plan
+// is made from names, flags and the per-record spans of the call's summary (combine_frags on headers, ingest.cpp: plan_contig), one floria_hip_assemble_contigs_opt call turns
+// the round's plans into resident contigs, --ignore-monomorphic is one floria_hip_drop_monomorphic call on them; the batch phases on the handles, the writers take their
+// allele tables from floria_hip_haploset_alleles and --output-reads' trims from floria_hip_read_spans.  A contig the device cannot number (see --pileup device) keeps the host
+// walk and is uploaded beside the others.  One device only, no --dump-frags (the qualities are folded into weights on the device).  Same files.
+// For tests: --dump-plan FILE (with --ingest-only, any route: the fragment plan per contig), --dump-handles FILE (any route: the resident arrays of every contig of every batch).
 // --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
 // RULE max | sum, TIE right | down): one member of the family of fixed-block walks (block 8) that scripts/probes/block_walk.c defines.  The reference's block-aligner is
 // some heuristic of this kind; which member, if any, is not known, so there is no bare `block`.  The run's log and cmd.log name the scoring used.
@@ -65,8 +71,10 @@ void usage() {
           "  --epsilon-round   round an ESTIMATED -e to a multiple of 2^-10 (there both arithmetics are the same function)\n"
           "  --lp-tie first|last, --lp-report   which optimal vertex of the stitching LP is used where the optimum is not unique, and how often that is\n"
           "  --no-realign      skip the re-alignment of the reads' bases around SNPs\n"
-          "  --pileup host|device|fused   where alignment records become SNP calls (the CIGAR walk): on the host threads [default] or in one device call per ingest round;\n"
-          "                    fused: that device call also re-aligns the calls (instead of the host loop that queues windows for the device); same files\n"
+          "  --pileup host|device|fused|resident   where alignment records become SNP calls (the CIGAR walk): on the host threads [default] or in one device call per ingest\n"
+          "                    round; fused: that device call also re-aligns the calls (instead of the host loop that queues windows for the device); resident: the calls\n"
+          "                    never come back - fragments are planned from the records' headers and assembled, filtered (--ignore-monomorphic) and phased on the device,\n"
+          "                    the writers ask it for allele tables and read trims (one device only; no --dump-frags).  Same files\n"
           "  --realign exact | block:STEP,RULE,TIE   how that re-alignment scores a window: exact [default] = the exact affine-gap alignment; block:... = a walk of a fixed\n"
           "                 8 x 8 block over the alignment matrix, shifted by STEP = 1 | 2 | 4 | 8 cells towards the larger border by RULE = max | sum, ties going\n"
           "                 TIE = right | down (e.g. block:8,max,right).  floria's block-aligner is a heuristic of this kind; which member is unknown, so one must be named\n"
@@ -126,7 +134,7 @@ int main(int argc, char** argv) {
     floria_hip_init_env();                      // GPU_MAX_HW_QUEUES=12 unless set: the job groups' streams and the copy streams must not share hardware queues (read when HIP initialises)
     Options o;
     bool have_e = false, have_l = false;
-    std::string dump_frags, dump_seq_pos;
+    std::string dump_frags, dump_seq_pos, dump_plan, dump_handles;
     size_t batch_contigs = 4096;         // --batch-contigs
     uint64_t batch_cells = 256ull << 20; // --batch-cells (1.5 GB of pinned staging)
     bool ingest_only = false, no_realign = false, have_realign = false;
@@ -217,9 +225,12 @@ int main(int argc, char** argv) {
             else if (a == "--realign") { parse_realign_spec(val(), o); have_realign = true; }
             else if (a == "--pileup") {
                 const std::string v = val();
-                if (v != "host" && v != "device" && v != "fused") throw Error(FLORIA_E_INVALID, "--pileup takes host or device (or fused: device, and the calls re-aligned there), not '" + v + "'");
-                o.pileup_device = v != "host"; o.pileup_fused = v == "fused";
+                if (v != "host" && v != "device" && v != "fused" && v != "resident")
+                    throw Error(FLORIA_E_INVALID, "--pileup takes host or device (or fused: device, and the calls re-aligned there; or resident: the calls stay on the device), not '" + v + "'");
+                o.pileup_device = v == "device" || v == "fused"; o.pileup_fused = v == "fused"; o.pileup_resident = v == "resident";
             }
+            else if (a == "--dump-plan") dump_plan = val();            // (tests, with --ingest-only) the fragment plan of every contig: needs no GPU under --pileup host
+            else if (a == "--dump-handles") dump_handles = val();      // (tests) the resident arrays of every contig of every batch, whichever route made the handle
             else if (a == "--ingest-only") ingest_only = true;          // (tests) stop after ingest: needs no GPU
             else if (a == "--stitch-graph") stitch_graph = val();       // (tests) N / E lines of a hap graph -> F / P lines on stdout: needs no GPU
             else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -274,6 +285,13 @@ int main(int argc, char** argv) {
             return 0;
         }
         if (no_realign && have_realign && o.realign_walk) throw Error(FLORIA_E_INVALID, "--no-realign and --realign " + realign_spec(o) + " exclude each other");
+        if (o.pileup_resident && devices.size() > 1)
+            throw Error(FLORIA_E_UNSUPPORTED, "--pileup resident runs on one device: the handles live on the context that walked the records, and dealing the contigs of a batch to "
+                                              "devices (--devices) would have to precede the walk");
+        if (o.pileup_resident && !dump_frags.empty())
+            throw Error(FLORIA_E_UNSUPPORTED, "--dump-frags is not available under --pileup resident: the quality bytes are folded into weights on the device and cannot be printed "
+                                              "(--dump-handles and --dump-seq-pos work)");
+        if (!dump_plan.empty() && !ingest_only) throw Error(FLORIA_E_INVALID, "--dump-plan needs --ingest-only");
         if (o.bam_file.empty()) throw Error(FLORIA_E_INVALID, "Must input a BAM file.");
         if (o.vcf_file.empty() || o.reference_fasta.empty()) throw Error(FLORIA_E_INVALID, "-v and -r are required");
         if (!(o.ploidy_sensitivity >= 1 && o.ploidy_sensitivity <= 3)) throw Error(FLORIA_E_INVALID, "Ploidy sensitivty option must be between 1 and 3");
@@ -337,7 +355,7 @@ int main(int argc, char** argv) {
         // one context per device of --devices (default: the one --device); every one throws without a usable MI355X: no CPU fallback
         if (devices.empty()) devices.push_back(o.device);
         std::vector<std::unique_ptr<Session>> sessions;
-        if (!ingest_only || o.pileup_device) for (int d : devices) sessions.emplace_back(new Session(d));     // (--ingest-only --pileup device needs a device for the walk)
+        if (!ingest_only || o.pileup_device || o.pileup_resident) for (int d : devices) sessions.emplace_back(new Session(d));     // (--ingest-only --pileup device | resident needs a device for the walk)
         for (auto& s : sessions) if (floria_hip_set_option(s->ctx(), "arith", reference_arith ? 1 : 0) != 0) throw Error(FLORIA_E_INVALID, floria_hip_last_error());
         // The reference-arithmetic mode adds a read's terms in the iteration order of its position set.  For a fragment built from ONE alignment the library emulates that
         // set on the device (arith_kernel.h); fragments whose set was EXTENDED by a mate or a supplementary piece (file_reader.rs:541, 639) or cut down by
@@ -351,6 +369,15 @@ int main(int argc, char** argv) {
         if (!dump_frags.empty()) dump.open(dump_frags, std::ios::trunc);
         std::ofstream dump_sp;
         if (!dump_seq_pos.empty()) dump_sp.open(dump_seq_pos, std::ios::trunc);
+        std::ofstream dump_pl, dump_hd;
+        if (!dump_plan.empty()) dump_pl.open(dump_plan, std::ios::trunc);
+        if (!dump_handles.empty()) dump_hd.open(dump_handles, std::ios::trunc);
+        std::mutex dump_hd_mu;
+        // --pileup resident: the handles keep positions (Frag::snp_pos_to_seq_pos) only where something reads them
+        const bool resident_keep_seq_pos = o.pileup_resident && (o.output_reads || !dump_seq_pos.empty());
+        size_t n_resident_merged = 0, n_resident_contigs = 0;
+        double t_resident_assemble = 0., t_resident_filter = 0., t_resident_assemble_ev = 0., t_resident_filter_ev = 0.;
+        uint64_t resident_bytes_back = 0, resident_removed_snps = 0, resident_dropped_reads = 0;
         // ---- which contigs (floria.rs:229-262) -------------------------------------------------------------------------------------
         bool warn_first_length = true;
         const size_t n_threads = std::max<size_t>(1, o.num_threads);
@@ -419,12 +446,47 @@ int main(int argc, char** argv) {
                                         "this is said once\n", o.pileup_fused ? "fused" : "device", device_cells->host_contigs[0].c_str(), FLORIA_MAX_ALLELES);
                     }
                 }
+                // --pileup resident: the round's walks (and realignment) in one device call whose cells stay there; the contigs it took are planned from headers, the
+                // others (host_contigs) go the host route below
+                std::unique_ptr<ResidentPileup> resident;
+                std::vector<HeaderContig> planned(take);
+                if (o.pileup_resident) {
+                    const double tw = now_s();
+                    resident.reset(new ResidentPileup(*session_holder, bam, vp, o, &todo[done], take, no_realign ? nullptr : &fasta));
+                    t_pileup += now_s() - tw;
+                    fused_counts.cells += resident->counts.cells; fused_counts.in_bounds += resident->counts.in_bounds; fused_counts.shortcut += resident->counts.shortcut;
+                    fused_counts.scored += resident->counts.scored; fused_counts.changed += resident->counts.changed;
+                    ++n_pileup_calls; n_pileup_records += resident->records_sent; n_pileup_bytes += resident->blob_bytes;
+                    t_pileup_kernels += resident->kernel_ms * 1e-3; t_pileup_h2d += resident->h2d_ms * 1e-3; t_pileup_d2h += resident->d2h_ms * 1e-3;
+                    if (!resident->host_contigs.empty() && !said_host_walk) {
+                        said_host_walk = true;
+                        fprintf(stderr, "floria-hip: --pileup resident: contig %s keeps the host walk (its SNP numbers are not their rank in position order, or a site has more than %d alleles) "
+                                        "and is uploaded beside the resident contigs of its batch; this is said once\n", resident->host_contigs[0].c_str(), FLORIA_MAX_ALLELES);
+                    }
+                }
+                const auto is_resident = [&](size_t i) { return resident && resident->on_table(i); };
                 parallel_for(take, n_threads, [&](size_t i) {
                     const std::string& contig = todo[done + i];
+                    if (is_resident(i)) { planned[i] = resident->plan(i); return; }
                     const auto fa = fasta.find(contig);
                     ing[i].reset(new ContigIngest(bam, vp, o, contig, (fa != fasta.end() && !no_realign) ? &fa->second : nullptr, on_device ? &queues[i] : nullptr, device_cells.get()));
                 });
                 device_cells.reset();
+                std::vector<std::string> plan_texts(dump_pl.is_open() ? take : 0);
+                if (dump_pl.is_open())
+                    parallel_for(take, n_threads, [&](size_t i) { plan_texts[i] = plan_text(todo[done + i], is_resident(i) ? planned[i].plan : ing[i]->plan(), bam); });
+                for (const std::string& t : plan_texts) dump_pl << t;
+                if (resident) {
+                    // combine_frags on the device: one assemble call for the round (and one filter call under --ignore-monomorphic), before the next round's walk
+                    // rewrites the pileup buffers
+                    std::vector<HeaderContig*> hp(take, nullptr);
+                    for (size_t i = 0; i < take; ++i) if (is_resident(i)) hp[i] = &planned[i];
+                    resident->assemble(hp, reference_arith, resident_keep_seq_pos, o.ignore_monomorphic, o.epsilon);
+                    t_resident_assemble += resident->assemble_s; t_resident_filter += resident->filter_s;
+                    t_resident_assemble_ev += resident->assemble_ms * 1e-3; t_resident_filter_ev += resident->filter_ms * 1e-3;
+                    resident_bytes_back += resident->bytes_back; resident_removed_snps += resident->removed_snps; resident_dropped_reads += resident->dropped_reads;
+                    for (size_t i = 0; i < take; ++i) if (is_resident(i)) { ++n_resident_contigs; n_resident_merged += planned[i].merged_frags; }
+                }
                 if (on_device) {
                     const double tr = now_s();
                     RealignQueue all;
@@ -438,6 +500,17 @@ int main(int argc, char** argv) {
                     ContigWork& w = got[i];
                     w.name = contig; w.out_dir = o.out_dir + "/" + contig;
                     const auto fa = fasta.find(contig);
+                    if (is_resident(i)) {
+                        // planned, assembled and filtered: the Frags are headers in the pileup's read order, the cells are behind the handle
+                        w.all_frags = std::move(planned[i].all_frags); w.frags_without_snps = std::move(planned[i].frags_without_snps);
+                        w.handle = std::move(planned[i].handle);
+                        w.resident_cells = planned[i].part_cells;
+                        const auto sgp = vp.snp_to_genome_pos.find(contig);
+                        w.snp_to_genome_pos = sgp == vp.snp_to_genome_pos.end() ? nullptr : &sgp->second;
+                        if (!ingest_only && !planned[i].plan.frags.empty() && w.snp_to_genome_pos) prepare_contig_dir(w.out_dir, o);     // (as below: before the filter)
+                        w.contig_len = fa == fasta.end() ? 0 : fa->second.size();
+                        return;
+                    }
                     auto fr = ing[i]->finish();
                     ing[i].reset();
                     w.all_frags = std::move(fr.first); w.frags_without_snps = std::move(fr.second);
@@ -457,6 +530,7 @@ int main(int argc, char** argv) {
                     if (w.all_frags.empty() || !w.snp_to_genome_pos) continue;
                     if (!ingest_only && w.contig_len == 0) throw Error(FLORIA_E_INVALID, "contig " + w.name + " is not in the reference fasta");
                     for (const Frag& f : w.all_frags) cells += f.seq_dict.size();
+                    cells += w.resident_cells;                                         // (header Frags: the parts' cells, an upper bound of the merged count)
                     work.push_back(std::move(w));
                 }
             }
@@ -478,6 +552,22 @@ int main(int argc, char** argv) {
             if (dump_sp.is_open())
                 for (const ContigWork& w : work) {
                     dump_sp << "#CONTIG\t" << w.name << "\t" << w.all_frags.size() << "\n";
+                    if (w.handle) {                              // header Frags: the same lines from the handle's SNP and SEQ_POS words (mate << 31 | seq_pos)
+                        const size_t R = w.all_frags.size();
+                        std::vector<uint32_t> ro(R + 1);
+                        auto get = [&](int field, std::vector<uint32_t>& v) {
+                            if (floria_hip_contig_download(w.handle.get(), field, v.data(), 4 * v.size()) != 0) throw Error(FLORIA_E_INVALID, std::string("--dump-seq-pos: ") + floria_hip_last_error());
+                        };
+                        get(FLORIA_FIELD_READ_OFF, ro);
+                        std::vector<uint32_t> snp(ro[R]), sp(ro[R]);
+                        get(FLORIA_FIELD_SNP, snp); get(FLORIA_FIELD_SEQ_POS, sp);
+                        for (size_t k = 0; k < R; ++k) {
+                            dump_sp << w.all_frags[k].id;
+                            for (uint32_t c = ro[k]; c < ro[k + 1]; ++c) dump_sp << "\t" << snp[c] << ":" << (sp[c] >> 31) << ":" << (sp[c] & 0x7fffffffu);
+                            dump_sp << "\n";
+                        }
+                        continue;
+                    }
                     for (const Frag& f : w.all_frags) {          // id, then snp:mate:seq_pos for every entry of snp_pos_to_seq_pos, ascending
                         dump_sp << f.id;
                         for (const auto& kv : f.snp_pos_to_seq_pos) dump_sp << "\t" << kv.first << ":" << (int)kv.second.first << ":" << kv.second.second;
@@ -489,7 +579,7 @@ int main(int argc, char** argv) {
             ++n_batches;
             if (reference_arith) {
                 size_t merged = 0, cut = 0;
-                for (const ContigWork& w : work) for (const Frag& f : w.all_frags) { merged += f.merged_positions ? 1 : 0; cut += f.removed_positions.empty() ? 0 : 1; }
+                for (const ContigWork& w : work) if (!w.handle) for (const Frag& f : w.all_frags) { merged += f.merged_positions ? 1 : 0; cut += f.removed_positions.empty() ? 0 : 1; }
                 n_frags_merged += merged; n_frags_cut += cut;
                 if (merged || cut) ++n_batches_orders;
             }
@@ -499,6 +589,7 @@ int main(int argc, char** argv) {
                 double t1 = now_s();
                 Batch batch(session, part, reference_arith);
                 batch.generate_hap_graphs(o);
+                if (dump_hd.is_open()) { const std::string t = batch.dump_handles(); std::lock_guard<std::mutex> g(dump_hd_mu); dump_hd << t; }
                 tm[0] += now_s() - t1; t1 = now_s();
                 parallel_for(part.size(), threads, [&](size_t i) {
                     ContigWork& w = part[i];
@@ -516,6 +607,7 @@ int main(int argc, char** argv) {
                 tm[2] += now_s() - t1; t1 = now_s();
                 batch.stats_and_hapq(o);
                 tm[3] += now_s() - t1;
+                if (batch.bytes_back) resident_bytes_back += batch.bytes_back;    // (resident contigs exist with one device only: no other thread is here then)
             };
             double tm[4] = {0., 0., 0., 0.};
             if (sessions.size() == 1) device_stages(*sessions[0], work, n_threads, tm);
@@ -548,21 +640,31 @@ int main(int argc, char** argv) {
             for (const std::string& r : rows) append_contig_ploidy_row(o, r);
             t_write += now_s() - t0;
             // the Frags of a batch are millions of small objects: freeing them goes to a thread of its own, the next batch's ingest does not wait for it
+            for (ContigWork& w : work) w.handle.reset();                           // (device memory goes back on this thread: a context takes one host thread at a time)
             if (freer.joinable()) freer.join();
             freer = std::thread([w = std::make_shared<std::vector<ContigWork>>(std::move(work))]() mutable { w.reset(); });
         }
         }       // (next segment of the BAM)
         fprintf(stderr, "BAM: %zu records in %zu segments, %.3fs of inflate + decode, largest inflated buffer %zu MiB\n", n_records, n_segments, t_stream, stream.peak_buffer_bytes() >> 20);
-        if (!fused || n_realign_device)                                           // (fused: only the contigs that kept the host walk queue windows)
+        const bool resident_realign = o.pileup_resident && !no_realign;
+        if (!(fused || resident_realign) || n_realign_device)                     // (fused, resident: only the contigs that kept the host walk queue windows)
         fprintf(stderr, "Realignment: %zu calls scored on the device in %.3fs (inside the ingest time), scoring %s\n", n_realign_device, t_realign,
                 o.realign_walk ? ("fixed-block walk " + realign_spec(o)).c_str() : "exact affine-gap DP");
-        if (fused)
+        if (fused || resident_realign)
             fprintf(stderr, "Realignment: %llu calls scored on the device behind the walk (%llu by the exact shortcut, %llu outside the window bounds), scoring %s\n",
                     (unsigned long long)fused_counts.scored, (unsigned long long)fused_counts.shortcut, (unsigned long long)(fused_counts.cells - fused_counts.in_bounds),
                     o.realign_walk ? ("fixed-block walk " + realign_spec(o)).c_str() : "exact affine-gap DP");
-        if (o.pileup_device)
+        if (o.pileup_device || o.pileup_resident)
             fprintf(stderr, "Pileup on the device: %zu records, %zu blob bytes in %zu calls, %.3fs (inside the ingest time; device events: upload %.3fs, kernels %.3fs, download %.3fs)\n",
                     n_pileup_records, n_pileup_bytes, n_pileup_calls, t_pileup, t_pileup_h2d, t_pileup_kernels, t_pileup_d2h);
+        if (o.pileup_resident) {
+            fprintf(stderr, "Resident contigs: %zu assembled on the device in %.3fs (device events %.3fs), --ignore-monomorphic filter %.3fs (device events %.3fs; %llu SNPs removed, %llu reads dropped); "
+                            "%llu bytes came back (record summaries, filter maps, allele tables, read trims), no cell\n", n_resident_contigs, t_resident_assemble, t_resident_assemble_ev,
+                    t_resident_filter, t_resident_filter_ev, (unsigned long long)resident_removed_snps, (unsigned long long)resident_dropped_reads, (unsigned long long)resident_bytes_back);
+            if (reference_arith)
+                fprintf(stderr, "Arithmetic: the set orders of %zu fragments merged from several alignments were derived on the device (floria_hip_assemble_contigs_opt), every resident contig "
+                                "phased in the reference's running sums\n", n_resident_merged);
+        }
         fprintf(stderr, "Batches %zu; ingest %.3fs, phasing (upload + S1 + graph) %.3fs, LP + paths %.3fs, S2 %.3fs, COV/ERR/HAPQ %.3fs, writers %.3fs\n", n_batches, t_ingest, t_s1,
                 t_stitch, t_s2, t_stats, t_write);
         if (reference_arith && n_batches_orders)
@@ -576,6 +678,8 @@ int main(int argc, char** argv) {
         // everything is written and closed: leave without tearing down the records, maps and sequences one by one (seconds for a large BAM)
         if (dump.is_open()) dump.close();
         if (dump_sp.is_open()) dump_sp.close();
+        if (dump_pl.is_open()) dump_pl.close();
+        if (dump_hd.is_open()) dump_hd.close();
         sessions.clear();
         // every output stream of this run was scoped to the function that wrote it and is closed; stdio is flushed here.  What is left are the records,
         // maps and sequences of the inputs, whose node-by-node teardown takes seconds for a large run: the process leaves without it (the freer of the

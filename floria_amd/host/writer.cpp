@@ -77,7 +77,8 @@ namespace {
 // contigs of a batch are written by several threads)
 std::string write_contig_files(const std::vector<std::vector<const Frag*>>& part, const std::vector<std::pair<SnpPosition, SnpPosition>>& ranges,
                                const std::string& dir, const std::string& prefix, const std::string& contig, const std::vector<GnPosition>& snp_to_gn,
-                               const std::vector<const Frag*>& snpless_frags, size_t contig_len, const HapqResult& hq, const std::vector<double>& st) {
+                               const std::vector<const Frag*>& snpless_frags, size_t contig_len, const HapqResult& hq, const std::vector<double>& st,
+                               const std::vector<uint64_t>* allele_off = nullptr, const std::vector<uint32_t>* allele_counts = nullptr) {
     mkdir_p(dir);
     const size_t n = part.size();
     // ---- write_haplotypes (:699-917) -----------------------------------------------------------------------------------------------
@@ -108,6 +109,10 @@ std::string write_contig_files(const std::vector<std::vector<const Frag*>>& part
         fputs(head.c_str(), vt);
         // write_fragset_haplotypes (:308-369): per SNP of the range the unit-count allele histogram of the haploset's reads
         std::vector<uint32_t> hist((size_t)(right - left + 1) * 4, 0);
+        if (allele_off) {                                                    // Frags without cells: the histogram was counted on the device (floria_hip_haploset_alleles)
+            if ((*allele_off)[i + 1] - (*allele_off)[i] != (uint64_t)(right - left + 1)) { fclose(vt); fclose(vi); fclose(hs); throw Error(FLORIA_E_INVALID, "allele table of another SNP range than the haploset's"); }
+            std::copy(allele_counts->begin() + 4 * (*allele_off)[i], allele_counts->begin() + 4 * (*allele_off)[i + 1], hist.begin());
+        } else
         for (const Frag* f : part[i])
             for (auto it = f->seq_dict.lower_bound(left); it != f->seq_dict.end() && it->first <= right; ++it) hist[(size_t)(it->first - left) * 4 + (it->second & 3)]++;
         fprintf(vi, ">HAP%zu.%s\tSNPRANGE:%u-%u\n", i, dir.c_str(), left, right);
@@ -231,27 +236,33 @@ void write_nosnp_reads(const std::string& dir, const std::vector<const Frag*>& s
 }
 
 void write_reads(const std::vector<std::vector<const Frag*>>& part, const std::vector<std::pair<SnpPosition, SnpPosition>>& ranges, const std::string& dir,
-                 bool extend_read_clipping, const std::vector<uint8_t>& hapqs, bool gzip) {
+                 bool extend_read_clipping, const std::vector<uint8_t>& hapqs, bool gzip, const std::vector<std::vector<uint32_t>>* span_left,
+                 const std::vector<std::vector<uint32_t>>* span_right) {
     constexpr size_t EXTENSION_BASES = 25;                                       // constants.rs:22
     mkdir_p(dir + "/short_reads"); mkdir_p(dir + "/long_reads");
     for (size_t i = 0; i < part.size(); ++i) {
         if (part[i].empty() || ranges.empty()) continue;                         // (hapqs[i] < HAPQ_CUTOFF = 0 never holds)
         (void)hapqs;
         const SnpPosition left_snp_pos = ranges[i].first, right_snp_pos = ranges[i].second;
-        std::vector<const Frag*> vec_part(part[i]);
-        std::sort(vec_part.begin(), vec_part.end(), [](const Frag* a, const Frag* b) { return *a < *b; });
+        std::vector<size_t> vec_part(part[i].size());                            // places in part[i] (where the device's lookups stand), sorted by Frag::cmp
+        for (size_t k = 0; k < vec_part.size(); ++k) vec_part[k] = k;
+        std::sort(vec_part.begin(), vec_part.end(), [&](size_t a, size_t b) { return *part[i][a] < *part[i][b]; });
         const std::string gz = gzip ? ".gz" : "";
         const std::string p0 = dir + "/long_reads/" + std::to_string(i) + "_part.fastq" + gz, p1 = dir + "/short_reads/" + std::to_string(i) + "_part_paired1.fastq" + gz,
                           p2 = dir + "/short_reads/" + std::to_string(i) + "_part_paired2.fastq" + gz;
         bool paired_written = false, single_end_written = false;
         {
             FastqOut w(p0, gzip), w1(p1, gzip), w2(p2, gzip);
-            for (const Frag* fp : vec_part) {
-                const Frag& frag = *fp;
+            for (const size_t at : vec_part) {
+                const Frag& frag = *part[i][at];
                 if (frag.seq_string[0].empty() && frag.seq_string[1].empty()) continue;            // no primary sequence
                 if (frag.first_position > right_snp_pos || frag.last_position < left_snp_pos) continue;   // fell off a merged haplogroup's range
                 size_t left_seq_pos = 0;
-                if (!(frag.first_position > left_snp_pos && extend_read_clipping)) {
+                if (!(frag.first_position > left_snp_pos && extend_read_clipping) && span_left) {  // a Frag without the map: floria_hip_read_spans looked it up
+                    const uint32_t word = (*span_left)[i][at];
+                    if (word == FLORIA_SPAN_NONE) throw Error(FLORIA_E_INVALID, "left snp position of partition for the read was not found.");
+                    left_seq_pos = word & 0x7fffffffu;
+                } else if (!(frag.first_position > left_snp_pos && extend_read_clipping)) {
                     auto it = frag.snp_pos_to_seq_pos.lower_bound(left_snp_pos);                  // first SNP of the read at or after the left end
                     if (it == frag.snp_pos_to_seq_pos.end()) throw Error(FLORIA_E_INVALID, "left snp position of partition for the read was not found.");
                     left_seq_pos = it->second.second;
@@ -261,6 +272,10 @@ void write_reads(const std::vector<std::vector<const Frag*>>& part, const std::v
                 if (frag.last_position < right_snp_pos && extend_read_clipping) {
                     right_read_pair = frag.is_paired ? 1 : 0;
                     right_seq_pos = frag.seq_string[right_read_pair].empty() ? 0 : frag.seq_string[right_read_pair].size() - 1;
+                } else if (span_right) {
+                    const uint32_t word = (*span_right)[i][at];
+                    if (word == FLORIA_SPAN_NONE) throw Error(FLORIA_E_INVALID, "right snp position of partition for the read was not found.");
+                    right_seq_pos = word & 0x7fffffffu; right_read_pair = (uint8_t)(word >> 31);
                 } else {
                     auto it = frag.snp_pos_to_seq_pos.upper_bound(right_snp_pos);                 // last SNP of the read at or before the right end
                     if (it == frag.snp_pos_to_seq_pos.begin()) throw Error(FLORIA_E_INVALID, "right snp position of partition for the read was not found.");
@@ -295,9 +310,12 @@ void prepare_contig_dir(const std::string& dir, const Options& o) {
         nftw(dir.c_str(), [](const char* p, const struct stat*, int, struct FTW*) -> int { return remove(p); }, 32, FTW_DEPTH | FTW_PHYS);
 }
 std::string write_contig_files(const ContigWork& w, const Options& o) {
-    std::string row = write_contig_files(w.final_parts, w.final_ranges, w.out_dir, w.name, w.name, *w.snp_to_genome_pos, w.snpless, w.contig_len, w.hq, w.stats);
+    // a contig that was assembled on the device (all_frags are headers) brings the allele tables and the trim lookups Batch::stats_and_hapq fetched for it
+    const bool headers = !w.allele_off.empty();
+    std::string row = write_contig_files(w.final_parts, w.final_ranges, w.out_dir, w.name, w.name, *w.snp_to_genome_pos, w.snpless, w.contig_len, w.hq, w.stats,
+                                         headers ? &w.allele_off : nullptr, headers ? &w.allele_counts : nullptr);
     if (o.output_reads) {                                                                   // file_writer.rs:68-84
-        write_reads(w.final_parts, w.final_ranges, w.out_dir, !o.trim_reads, w.hq.hapqs, o.gzip);
+        write_reads(w.final_parts, w.final_ranges, w.out_dir, !o.trim_reads, w.hq.hapqs, o.gzip, headers ? &w.span_left : nullptr, headers ? &w.span_right : nullptr);
         write_nosnp_reads(w.out_dir, w.snpless, o.gzip);
     }
     return row;

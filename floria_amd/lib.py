@@ -537,7 +537,7 @@ class FloriaHip:
     def drop_monomorphic(self, contigs, snp_counts, error, with_set_order=False):
         """floria_hip_drop_monomorphic: remove_monomorphic_allele (utils_frags.rs:713-772) on resident contigs (a list of ResidentContigs or a ContigBatch) whose
         SNP counts are snp_counts -> (ContigBatch of the filtered contigs, dict(read_off uint64 [n + 1], old_read uint32, removed uint8 [sum of snp_counts],
-        n_removed_snps, n_removed_cells, n_dropped_reads)).  The inputs stay as they are."""
+        n_removed_snps, n_removed_cells, n_dropped_reads, new_first / new_last uint32 [reads of the result]: the survivors' first / last SNP)).  The inputs stay as they are."""
         n = len(contigs)
         arr = contigs._arr if isinstance(contigs, ContigBatch) else (C.c_void_p * max(n, 1))(*[c._h for c in contigs])
         if len(np.atleast_1d(snp_counts)) != n:
@@ -550,7 +550,8 @@ class FloriaHip:
         r = out.contents
         read_off = capi.np_from(r.read_off, n + 1, np.uint64)
         result = dict(read_off=read_off, old_read=capi.np_from(r.old_read, int(read_off[-1]), np.uint32), removed=capi.np_from(r.removed, int(so[-1]), np.uint8),
-                      n_removed_snps=int(r.n_removed_snps), n_removed_cells=int(r.n_removed_cells), n_dropped_reads=int(r.n_dropped_reads))
+                      n_removed_snps=int(r.n_removed_snps), n_removed_cells=int(r.n_removed_cells), n_dropped_reads=int(r.n_dropped_reads),
+                      new_first=capi.np_from(r.new_first, int(read_off[-1]), np.uint32), new_last=capi.np_from(r.new_last, int(read_off[-1]), np.uint32))
         load().floria_hip_mono_result_free(out)
         return ContigBatch(self, hs, n), result
 

@@ -534,6 +534,8 @@ typedef struct {
     uint32_t* old_read;     /* [read_off[n]] output read r of contig c was input read old_read[read_off[c]+r] of contig c   */
     uint8_t*  removed;      /* [snp_off[n]]  removed[snp_off[c] + s-1] = 1 iff SNP s (1-based) of contig c was removed      */
     uint64_t  n_removed_snps, n_removed_cells, n_dropped_reads;
+    uint32_t* new_first;    /* [read_off[n]] first SNP of output read r of contig c after the removal, at read_off[c]+r: what FLORIA_FIELD_FIRST of out[c] holds   */
+    uint32_t* new_last;     /* [read_off[n]] ... its last SNP (FLORIA_FIELD_LAST): a host that keeps headers only re-maps them without a download                    */
 } floria_mono_result;
 int  floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
                                  const uint64_t* snp_off /* [n_contigs+1], prefix sums of the contigs' SNP counts */,

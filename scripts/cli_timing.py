@@ -3,13 +3,17 @@
     python scripts/cli_timing.py [--contigs 60] [--scale 0.5] [--threads 16] [--sub-rate 0.12] [--realign exact|block:STEP,RULE,TIE ...] [--exe PATH] [--only batched]
 
 --realign (repeatable, needs --only or takes the batched run): the batched run once per scoring, in the order given, e.g. --realign exact --realign block:8,max,right
---pileup-compare N [--threads-list 16,1]: only the batched flow, --pileup host, --pileup device and --pileup fused ALTERNATING, N runs each per thread count, then the
-median and the spread (min .. max) of the ingest time and of the wall time per route (profiles/pileup_device.md, profiles/pileup_fused.md).
+--pileup-compare N [--threads-list 16,1]: only the batched flow, --pileup host, device, fused and resident ALTERNATING, N runs each per thread count, then the
+median and the spread (min .. max) of the ingest time and of the wall time per route, and per route the medians of what the driver reports about its device calls
+(profiles/pileup_device.md, profiles/pileup_fused.md, profiles/pileup_resident.md).
+--config K --epsilon X --block-length N: the data set's synth configuration (4 = long reads [default], 3 = paired short reads) and the run's -e / -l, e.g.
+--config 3 --epsilon 0.04 --block-length 500 for the paired set in the reference arithmetic.
 --realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
 
 Writes BAM / VCF / FASTA under $TMPDIR, runs the driver twice and prints its stage-time lines (stderr of floria-hip)."""
 import argparse
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -33,6 +37,9 @@ def main():
     ap.add_argument("--arith-compare", action="store_true", help="only: the batched flow at -e 0.04 with --arith canonical against --arith reference (the default there)")
     ap.add_argument("--pileup-compare", type=int, default=0, help="only: the batched flow with --pileup host, device and fused alternating, this many runs each")
     ap.add_argument("--threads-list", default=None, help="with --pileup-compare: comma-separated -t values (default: --threads)")
+    ap.add_argument("--config", type=int, default=4, help="synth configuration of the contigs (4: long reads, 3: paired short reads)")
+    ap.add_argument("--epsilon", default="0.03125", help="-e of every run")
+    ap.add_argument("--block-length", default="10000", help="-l of every run")
     a = ap.parse_args()
     if a.exe is None:
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "floria_amd", "host"), "floria-hip"], stdout=subprocess.DEVNULL)
@@ -40,11 +47,11 @@ def main():
     tmp = tempfile.mkdtemp(prefix="floria_cli_")
     prefix = os.path.join(tmp, "d")
     t = time.time()
-    cs = [synth.make_config_contig(4, i, a.scale, keep_layout=True) for i in range(a.contigs)]
+    cs = [synth.make_config_contig(a.config, i, a.scale, keep_layout=True) for i in range(a.contigs)]
     synth_bam.write_dataset(prefix, cs, seed=1, realign=False, sub_rate=a.sub_rate)
     print(f"data set: {a.contigs} contigs, {sum(c.pileup.n_reads for c in cs)} reads, {sum(len(c.snp_pos) for c in cs)} SNPs, "
           f"BAM {os.path.getsize(prefix + '.bam') >> 20} MiB, written in {time.time() - t:.1f}s; host cores {os.cpu_count()}", flush=True)
-    base = [exe, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-e", "0.03125", "-l", "10000", "--snp-count-filter", "50"]
+    base = [exe, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-e", a.epsilon, "-l", a.block_length, "--snp-count-filter", "50"]
     runs = (("batched", ["-t", str(a.threads)]), ("batched, 1 thread", ["-t", "1"]), ("one contig per batch", ["-t", str(a.threads), "--batch-contigs", "1"]),
             ("ingest only: realign DP on the host", ["-t", str(a.threads), "--ingest-only"]), ("ingest only, 1 thread", ["-t", "1", "--ingest-only"]))
     if a.arith_compare:
@@ -55,10 +62,10 @@ def main():
         runs = tuple((f"batched, --realign {spec}" + (" (again)" if spec in a.realign[:k] else ""), ["-t", str(a.threads), "--realign", spec]) for k, spec in enumerate(a.realign))
     if a.pileup_compare:
         threads = [int(x) for x in a.threads_list.split(",")] if a.threads_list else [a.threads]
-        runs = tuple((f"-t {t}, --pileup {route}, run {k + 1}", ["-t", str(t), "--pileup", route]) for t in threads for k in range(a.pileup_compare) for route in ("host", "device", "fused"))
+        runs = tuple((f"-t {t}, --pileup {route}, run {k + 1}", ["-t", str(t), "--pileup", route]) for t in threads for k in range(a.pileup_compare) for route in ("host", "device", "fused", "resident"))
     if a.only:
         runs = tuple(r for r in runs if a.only in r[0])
-    stats = {}
+    stats, calls = {}, {}
     for label, extra in runs:
         out = os.path.join(tmp, "o_" + label.replace(" ", "_").replace(",", ""))
         t = time.time()
@@ -67,15 +74,31 @@ def main():
         if r.returncode:
             print(r.stderr[-2000:])
             raise SystemExit(1)
-        lines = [ln for ln in r.stderr.splitlines() if ln.startswith(("Batches", "Total time", "Preprocessing:", "[read_bam]", "Realignment:", "Pileup on the device:"))]
+        lines = [ln for ln in r.stderr.splitlines() if ln.startswith(("Batches", "Total time", "Preprocessing:", "[read_bam]", "Realignment:", "Pileup on the device:", "Resident contigs:"))]
         print(f"[{label}] wall {wall:.2f}s | " + " | ".join(lines), flush=True)
         if a.pileup_compare:
             ingest = float(next(ln for ln in lines if ln.startswith("Batches")).split("ingest ")[1].split("s")[0])
             stats.setdefault(label.rsplit(", run", 1)[0], []).append((ingest, wall))
+            # what the driver says about its device calls: the pileup call's wall seconds, event seconds and blob bytes; the resident stages' event seconds and bytes back
+            pl = next((ln for ln in lines if ln.startswith("Pileup on the device:")), None)
+            rs = next((ln for ln in lines if ln.startswith("Resident contigs:")), None)
+            d = {}
+            if pl:
+                m = re.search(r"(\d+) blob bytes in (\d+) calls, ([\d.]+)s .*upload ([\d.]+)s, kernels ([\d.]+)s, download ([\d.]+)s", pl)
+                d.update(blob_bytes_up=float(m.group(1)), pileup_calls=float(m.group(2)), pileup_wall_s=float(m.group(3)), pileup_upload_ev_s=float(m.group(4)),
+                         pileup_kernels_ev_s=float(m.group(5)), pileup_download_ev_s=float(m.group(6)))
+            if rs:
+                m = re.search(r"in ([\d.]+)s \(device events ([\d.]+)s\), --ignore-monomorphic filter ([\d.]+)s \(device events ([\d.]+)s.*\); (\d+) bytes came back", rs)
+                d.update(assemble_wall_s=float(m.group(1)), assemble_ev_s=float(m.group(2)), filter_wall_s=float(m.group(3)), filter_ev_s=float(m.group(4)), bytes_back=float(m.group(5)))
+            calls.setdefault(label.rsplit(", run", 1)[0], []).append(d)
     for key, v in stats.items():
         for k, what in enumerate(("ingest", "wall")):
             x = sorted(t[k] for t in v)
             print(f"[{key}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs")
+    for key, v in calls.items():
+        if v and v[0]:
+            med = lambda xs: sorted(xs)[len(xs) // 2]
+            print(f"[{key}] device calls (medians): " + ", ".join(f"{k} {med([d[k] for d in v]):g}" for k in v[0]))
 
 
 if __name__ == "__main__":
