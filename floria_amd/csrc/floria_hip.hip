@@ -56,13 +56,16 @@ namespace {
 thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
-#define HIPCHK(expr)                                                                                   \
+// HIPCHK_AS: the message is `prefix` + the error string ("assemble: ", "contig upload: ", ...); HIPCHK: the expression's own text is the prefix.  Both RETURN, so
+// whatever a function owns by then (an arena, a result, handles) is released by a guard object, never by hand.
+#define HIPCHK_AS(prefix, expr)                                                                        \
     do {                                                                                               \
         hipError_t _e = (expr);                                                                        \
         if (_e != hipSuccess)                                                                          \
             return fail(_e == hipErrorOutOfMemory ? FLORIA_E_NOMEM : FLORIA_E_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                            \
+                        std::string(prefix) + hipGetErrorString(_e));                                  \
     } while (0)
+#define HIPCHK(expr) HIPCHK_AS(#expr ": ", expr)
 
 constexpr double DIV_FACTOR  = 0.25;   // constants.rs:5
 constexpr double PROB_CUTOFF = 0.01;   // constants.rs:6
@@ -388,8 +391,14 @@ struct EventTimer {
         (void)hipEventElapsedTime(&ms, ev.front().first, ev.back().second);
         return ms;
     }
+    void publish(floria_timing& tm);
 };
 enum { K_BEAM = 0, K_OPT = 1, K_SEL = 2, K_H2D = 3, K_D2H = 4, K_REASSIGN = 5, K_PHASE = 6, K_PILEUP = 7 };
+// the closing line of every call but S1 (which has fields and rules of its own): the sums by kind and the span, into a timing the call reset when it began
+// (a kind the call never timed sums to the 0 the field holds anyway)
+void EventTimer::publish(floria_timing& tm) {
+    tm.h2d_ms = sum(K_H2D); tm.d2h_ms = sum(K_D2H); tm.pileup_ms = sum(K_PILEUP); tm.select_ms = sum(K_SEL); tm.reassign_ms = sum(K_REASSIGN); tm.total_ms = span();
+}
 
 void sync_all(floria_hip_ctx* ctx) {
     for (uint32_t g = 0; g < floria_hip_ctx::MAX_LANES; ++g) if (ctx->gstream[g]) (void)hipStreamSynchronize(ctx->gstream[g]);
@@ -1020,6 +1029,17 @@ static inline uint32_t chain_grid(const floria_hip_ctx* ctx, uint32_t grid) {
     const uint32_t cap = ctx->knobs.chain_wgs;
     return cap && grid > cap ? cap : grid;
 }
+// ... of the chain's usual shape: `per_wg` items per workgroup and trip (4 = one wavefront per item), grid-stride beyond 8 workgroups per CU, one workgroup at the least
+static inline uint32_t items_grid(const floria_hip_ctx* ctx, uint64_t items, uint32_t per_wg) {
+    return chain_grid(ctx, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + per_wg - 1) / per_wg, (uint64_t)ctx->n_cu * 8)));
+}
+// counts[0..n) -> their exclusive prefix sums in place, the total in counts[n] (pileup_kernel.h); `tiles`: a word per PILEUP_SCAN_TILE counts.  The caller asks hipGetLastError.
+static inline void launch_offset_scan(const floria_hip_ctx* ctx, uint64_t* counts, uint64_t* tiles, uint32_t n) {
+    const uint32_t n_tiles = (n + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+    hipLaunchKernelGGL(fl::pileup_scan_tiles_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, counts, tiles, n);
+    hipLaunchKernelGGL(fl::pileup_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, tiles, n_tiles, counts + n);
+    hipLaunchKernelGGL(fl::pileup_scan_add_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, counts, (const uint64_t*)tiles, n);
+}
 
 int floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots) {
     if (!ctx) return fail(FLORIA_E_INVALID, "null ctx");
@@ -1155,17 +1175,46 @@ extern "C" {
 
 namespace {
 
-// The plan of one batch upload: where every array of every contig lands in the arena, which host->device transfers carry it
-// (arrays of consecutive contigs that are back to back in host memory merge into one transfer) and the flatten kernel's tables.
-// The cell arrays (snp, allele, qual — 99 % of the bytes) are planned per CHUNK of consecutive contigs, so that a caller can
-// start work on chunk g while chunk g+1 is still on the wire (floria_hip_phase_pileups_batch).
+// Where the regions of a batch arena lie, for R reads and C cells in n contigs.  There is one definition, and one builder (UploadPlan::open below) that every producer
+// of resident contigs goes through (plan_upload, floria_hip_assemble_contigs, floria_hip_drop_monomorphic), so that their handles cannot differ in layout.  16-B tails:
+// the beam kernel's LDS-DMA moves cells in 16-B pieces.  The set-order region exists only when some contig carries one, the seq_pos region only when some contig carries
+// positions; it lies behind every other region, so no other offset depends on it.
+struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, o_sp = 0, bytes = 0; };
+ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so, bool any_sp) {
+    ArenaLayout Y;
+    Carve X;
+    Y.o_ro = X.seg(4 * (R + n)).off; Y.o_first = X.seg(4 * R).off; Y.o_last = X.seg(4 * R).off; Y.o_snp = X.seg(4 * C + 16).off; Y.o_aw = X.seg(4 * C + 16).off;
+    Y.o_tw = X.seg(16 * R).off; Y.o_meta = X.seg(32 * R).off;
+    Y.o_so = any_so ? X.seg(4 * C + 16).off : 0;
+    Y.o_sp = any_sp ? X.seg(4 * C + 16).off : 0;
+    Y.bytes = X.cursor;
+    return Y;
+}
+// ... and contig i's views into them (rp / cp: reads / cells before every contig)
+void arena_contig(const ArenaLayout& Y, char* D, const std::vector<uint64_t>& rp, const std::vector<uint64_t>& cp, uint32_t i, fl::UploadContig& u) {
+    u.read_off = (const uint32_t*)(D + Y.o_ro + 4 * (rp[i] + i)); u.first = (const uint32_t*)(D + Y.o_first + 4 * rp[i]); u.last = (const uint32_t*)(D + Y.o_last + 4 * rp[i]);
+    u.snp = (const uint32_t*)(D + Y.o_snp + 4 * cp[i]); u.cell_aw = (uint32_t*)(D + Y.o_aw + 4 * cp[i]); u.tw = (uint64_t*)(D + Y.o_tw + 16 * rp[i]); u.meta = (uint32_t*)(D + Y.o_meta + 32 * rp[i]);
+    u.n_reads = (uint32_t)(rp[i + 1] - rp[i]); u.n_cells = (uint32_t)(cp[i + 1] - cp[i]);
+}
+
+// A batch of resident contigs under construction, and the one owner of its arena until the handles take it over.  open() does what every producer needs, in this order:
+// the upload epoch moves on, the batch is one chunk, the arena is laid out, taken and described, the transient tables of the validate + flatten launch (and, with
+// `raw`, the raw allele / qual bytes it reads) are placed in up_tmp, and every contig gets its views and a fresh status word.  What differs per contig stays with the
+// producer, as one loop over so_dev / sp_dev behind open().  commit() turns the status words into an error or into the handles; unless it succeeded, the destructor
+// waits for the device (sync_all), gives the arena back and nulls the caller's handles — so every error path below is a plain return.
+// For a host upload the plan also says which host->device transfers carry the arrays (arrays of consecutive contigs that are back to back in host memory merge into
+// one transfer).  The cell arrays (snp, allele, qual — 99 % of the bytes) are planned per CHUNK of consecutive contigs, so that a caller can start work on chunk g
+// while chunk g+1 is still on the wire (floria_hip_phase_pileups_batch).
 struct UploadPlan {
+    floria_hip_ctx* ctx = nullptr;
+    floria_hip_contig** out = nullptr;                  // [n] the caller's handles
     uint32_t n = 0, n_chunks = 1;
     std::vector<uint64_t> rp, cp;                       // read / cell prefix per contig
     uint64_t R = 0, C = 0;
-    Arena* A = nullptr;
+    Arena* A = nullptr;                                 // (null again once the handles own it)
+    ArenaLayout Y;
     char *D = nullptr, *T = nullptr;                    // arena base, transient base
-    size_t t_cd = 0, t_rp = 0, t_st = 0;
+    size_t t_al = 0, t_q = 0, t_cd = 0, t_rp = 0, t_st = 0, t_more = 0;      // transient: raw alleles, raw quals, contig table, read prefix, status words, the caller's own bytes
     std::vector<fl::UploadContig> ucd;
     std::vector<fl::UploadStatus> ust;
     std::vector<fl::PackedContig> upk;                  // packed uploads: what expand_kernel reads / writes (device table at t_pk)
@@ -1175,41 +1224,52 @@ struct UploadPlan {
     std::vector<std::vector<CopyRun>> chunk_runs;       // snp, allele, qual per chunk
     std::vector<uint32_t> chunk_first;                  // [n_chunks+1] contig boundaries
     std::vector<uint32_t> contig_chunk;                 // [n]
-    std::vector<const uint32_t*> so_dev;                // [n] device copy of the contig's set_order (include/floria_hip.h), null where the host gave none
+    std::vector<const uint32_t*> so_dev;                // [n] device copy of the contig's set_order (include/floria_hip.h), null where it has none
     std::vector<const uint32_t*> sp_dev;                // [n] the contig's part of the seq_pos region, null where it carries no positions (empty: none does)
     bool all_pinned = false;
+
+    UploadPlan() = default;
+    UploadPlan(const UploadPlan&) = delete;
+    UploadPlan& operator=(const UploadPlan&) = delete;
+    ~UploadPlan() { if (A) { sync_all(ctx); release(); for (uint32_t i = 0; out && i < n; ++i) out[i] = nullptr; } }
+    void release() { arena_put(A); A = nullptr; }      // (back to the cache without a wait: nothing was issued yet)
+    uint32_t* so_at(uint32_t i) const { return (uint32_t*)(D + Y.o_so + 4 * cp[i]); }      // where contig i's set order / positions lie if it carries them
+    uint32_t* sp_at(uint32_t i) const { return (uint32_t*)(D + Y.o_sp + 4 * cp[i]); }
+    fl::ContigDev dev(uint32_t i) const { const fl::UploadContig& u = ucd[i]; return fl::ContigDev{u.read_off, u.first, u.last, u.snp, u.cell_aw, u.tw, u.meta, u.n_reads, 0, so_dev[i]}; }      // what the kernels see of contig i
+    // `raw`: the flatten launch reads raw allele / qual bytes from up_tmp (a host upload's DMA or assemble's FILL puts them there), and its tables lie behind them, with
+    // `more` bytes of the caller's at t_more.  Without it nothing of up_tmp is touched: the producer writes the resident form and keeps the tables where it likes.
+    int open(floria_hip_ctx* c, uint32_t n_contigs, std::vector<uint64_t> read_prefix, std::vector<uint64_t> cell_prefix, bool any_so, bool any_sp, floria_hip_contig** handles,
+             bool raw, size_t more = 0) {
+        ctx = c; out = handles; n = n_contigs; rp = std::move(read_prefix); cp = std::move(cell_prefix); R = rp[n]; C = cp[n];
+        ctx->upload_epoch++;                               // (device memory of contigs is about to be rewritten: cached cell orders no longer describe it)
+        n_chunks = 1; chunk_first = {0, n}; contig_chunk.assign(n, 0);
+        Y = layout_arena(R, C, n, any_so, any_sp);
+        A = arena_get(ctx, Y.bytes + 256);
+        if (!A) return FLORIA_E_NOMEM;
+        A->n_contigs = n; A->R = R; A->C = C; A->off_ro = Y.o_ro; A->off_first = Y.o_first; A->off_last = Y.o_last; A->read_prefix = rp; A->host_meta = false;
+        D = A->buf.as<char>();
+        if (raw) {
+            Carve X;
+            const Seg s_al = X.seg(C + 16), s_q = X.seg(C + 16), s_cd = X.seg(sizeof(fl::UploadContig) * n), s_rp = X.seg(8ull * (n + 1)), s_st = X.seg(sizeof(fl::UploadStatus) * n), s_more = X.seg(more);
+            if (int rc = X.place(ctx->up_tmp)) return rc;
+            T = X.base; t_al = s_al.off; t_q = s_q.off; t_cd = s_cd.off; t_rp = s_rp.off; t_st = s_st.off; t_more = s_more.off;
+        }
+        ucd.resize(n); ust.resize(n); so_dev.assign(n, nullptr);
+        if (any_sp) sp_dev.assign(n, nullptr);
+        for (uint32_t i = 0; i < n; ++i) {
+            fl::UploadContig& u = ucd[i];
+            arena_contig(Y, D, rp, cp, i, u);
+            u.allele = raw ? (const uint8_t*)(T + t_al + cp[i]) : nullptr; u.qual = raw ? (const uint8_t*)(T + t_q + cp[i]) : nullptr;
+            ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
+        }
+        return 0;
+    }
+    int commit();
 };
 
-// Where the regions of a batch arena lie, for R reads and C cells in n contigs: the ONE definition every producer of resident contigs uses (plan_upload,
-// floria_hip_assemble_contigs, floria_hip_drop_monomorphic), so that their handles cannot differ in layout.  16-B tails: the beam kernel's LDS-DMA moves cells in
-// 16-B pieces.  The set-order region exists only when some contig carries one, the seq_pos region only when some contig carries positions; it lies behind
-// every other region, so no other offset depends on it.
-struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, o_sp = 0, bytes = 0; };
-ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so, bool any_sp) {
-    ArenaLayout Y;
-    size_t cursor = 0;
-    auto seg = [&](size_t bytes) { const size_t o = cursor; cursor += (bytes + 255) & ~(size_t)255; return o; };
-    Y.o_ro = seg(4 * (R + n)); Y.o_first = seg(4 * R); Y.o_last = seg(4 * R); Y.o_snp = seg(4 * C + 16); Y.o_aw = seg(4 * C + 16); Y.o_tw = seg(16 * R); Y.o_meta = seg(32 * R);
-    Y.o_so = any_so ? seg(4 * C + 16) : 0;
-    Y.o_sp = any_sp ? seg(4 * C + 16) : 0;
-    Y.bytes = cursor;
-    return Y;
-}
-// ... and contig i's views into them (rp / cp: reads / cells before every contig); the transient raw allele / qual pointers are the caller's
-void arena_contig(const ArenaLayout& Y, char* D, const std::vector<uint64_t>& rp, const std::vector<uint64_t>& cp, uint32_t i, fl::UploadContig& u) {
-    u.read_off = (const uint32_t*)(D + Y.o_ro + 4 * (rp[i] + i)); u.first = (const uint32_t*)(D + Y.o_first + 4 * rp[i]); u.last = (const uint32_t*)(D + Y.o_last + 4 * rp[i]);
-    u.snp = (const uint32_t*)(D + Y.o_snp + 4 * cp[i]); u.cell_aw = (uint32_t*)(D + Y.o_aw + 4 * cp[i]); u.tw = (uint64_t*)(D + Y.o_tw + 16 * rp[i]); u.meta = (uint32_t*)(D + Y.o_meta + 32 * rp[i]);
-    u.n_reads = (uint32_t)(rp[i + 1] - rp[i]); u.n_cells = (uint32_t)(cp[i + 1] - cp[i]);
-}
-void arena_describe(Arena* A, const ArenaLayout& Y, uint32_t n, uint64_t R, uint64_t C, const std::vector<uint64_t>& rp) {
-    A->n_contigs = n; A->R = R; A->C = C; A->off_ro = Y.o_ro; A->off_first = Y.o_first; A->off_last = Y.o_last; A->read_prefix = rp; A->host_meta = false;
-}
-
 // (a batch is either CSR pileups or packed ones: `pk` non-null selects the compact wire form, expanded on the device)
-int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_pileup_packed* pk, uint32_t n, uint32_t n_chunks, UploadPlan& P) {
-    P.n = n; P.packed = pk != nullptr;
-    ctx->upload_epoch++;                               // (device memory of contigs is about to be rewritten: cached cell orders no longer describe it)
-    P.rp.assign(n + 1, 0); P.cp.assign(n + 1, 0);
+int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_pileup_packed* pk, uint32_t n, uint32_t n_chunks, floria_hip_contig** out, UploadPlan& P) {
+    std::vector<uint64_t> rp(n + 1, 0), cp(n + 1, 0);
     std::vector<floria_pileup> views;                   // packed: the fields both forms share, so that the code below reads one type
     if (pk) {
         views.resize(n);
@@ -1225,9 +1285,26 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
         if (!pk && p->n_reads && (!p->read_off || !p->snp || !p->allele || !p->qual || !p->first || !p->last)) return fail(FLORIA_E_INVALID, "null pileup field");
         const uint64_t nc = p->n_reads ? p->read_off[p->n_reads] : 0;
         if (nc >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "more than 2^32 cells in one contig");
-        P.rp[i + 1] = P.rp[i] + p->n_reads; P.cp[i + 1] = P.cp[i] + nc;
+        rp[i + 1] = rp[i] + p->n_reads; cp[i + 1] = cp[i] + nc;
     }
-    const uint64_t R = P.R = P.rp[n], C = P.C = P.cp[n];
+    bool any_so = false;                                                                                // host-given set orders (optional, the reference-arithmetic mode reads them)
+    for (uint32_t i = 0; i < n; ++i) any_so = any_so || (pileups[i].n_reads && pileups[i].set_order);
+    // packed: the compact arrays are transient too (bit offsets, presence bits, 2-bit alleles), one sub-range per contig — at the offsets
+    // floria_hip_pack_pileups_batch gives them in host memory, so that a batch packed by it travels as one transfer per field and chunk
+    std::vector<uint64_t> pb(n + 1, 0);                 // presence bytes prefix
+    Carve X;                                            // (offsets inside the plan's t_more bytes)
+    Seg s_bo{}, s_pr{}, s_a2{}, s_pk{};
+    if (pk) {
+        for (uint32_t i = 0; i < n; ++i) pb[i + 1] = pb[i] + (pk[i].n_reads ? ((uint64_t)pk[i].bit_off[pk[i].n_reads] + 7) / 8 : 0) + 1;
+        s_bo = X.seg(4 * (rp[n] + n)); s_pr = X.seg(pb[n] + 16); s_a2 = X.seg(cp[n] / 4 + n + 16); s_pk = X.seg(sizeof(fl::PackedContig) * n);
+    }
+    P.packed = pk != nullptr;
+    if (int rc = P.open(ctx, n, std::move(rp), std::move(cp), any_so, false, out, true, X.cursor)) return rc;      // (uploads carry no positions)
+    const uint64_t C = P.C;
+    const size_t o_ro = P.Y.o_ro, o_first = P.Y.o_first, o_last = P.Y.o_last, o_snp = P.Y.o_snp, t_al = P.t_al, t_q = P.t_q;
+    const size_t t_bo = P.t_more + s_bo.off, t_pr = P.t_more + s_pr.off, t_a2 = P.t_more + s_a2.off;
+    P.t_pk = P.t_more + s_pk.off;
+    char *D = P.D, *T = P.T;
     // chunks: consecutive contigs, balanced by cells
     n_chunks = std::max<uint32_t>(1, std::min<uint32_t>(n_chunks, n));
     P.n_chunks = n_chunks;
@@ -1247,31 +1324,7 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
         }
         for (uint32_t h = g + 1; h < n_chunks; ++h) P.chunk_first[h] = n;          // (fewer non-empty chunks than asked for)
     }
-    // ---- arena layout -------------------------------------------------------------------------------------------------------
-    bool any_so = false;                                                                                // host-given set orders (optional, the reference-arithmetic mode reads them)
-    for (uint32_t i = 0; i < n; ++i) any_so = any_so || (pileups[i].n_reads && pileups[i].set_order);
-    const ArenaLayout Y = layout_arena(R, C, n, any_so, false);      // (uploads carry no positions)
-    const size_t o_ro = Y.o_ro, o_first = Y.o_first, o_last = Y.o_last, o_snp = Y.o_snp, o_so = Y.o_so;
-    Arena* A = P.A = arena_get(ctx, Y.bytes + 256);
-    if (!A) return FLORIA_E_NOMEM;
-    arena_describe(A, Y, n, R, C, P.rp);
-    char* D = P.D = A->buf.as<char>();
-    // transient: raw allele / qual bytes, the kernel's contig table, prefix and status
-    size_t c2 = 0;
-    auto seg2 = [&](size_t bytes) { const size_t o = c2; c2 += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t t_al = seg2(C + 16), t_q = seg2(C + 16);
-    P.t_cd = seg2(sizeof(fl::UploadContig) * n); P.t_rp = seg2(8 * (n + 1)); P.t_st = seg2(sizeof(fl::UploadStatus) * n);
-    // packed: the compact arrays are transient too (bit offsets, presence bits, 2-bit alleles), one sub-range per contig — at the offsets
-    // floria_hip_pack_pileups_batch gives them in host memory, so that a batch packed by it travels as one transfer per field and chunk
-    std::vector<uint64_t> pb(n + 1, 0);                 // presence bytes prefix
-    size_t t_bo = 0, t_pr = 0, t_a2 = 0;
-    if (pk) {
-        for (uint32_t i = 0; i < n; ++i) pb[i + 1] = pb[i] + (pk[i].n_reads ? ((uint64_t)pk[i].bit_off[pk[i].n_reads] + 7) / 8 : 0) + 1;
-        t_bo = seg2(4 * (R + n)); t_pr = seg2(pb[n] + 16); t_a2 = seg2(C / 4 + n + 16); P.t_pk = seg2(sizeof(fl::PackedContig) * n);
-    }
-    if (int rc = ctx->up_tmp.ensure(c2 + 256)) { arena_put(A); P.A = nullptr; return rc; }
-    char* T = P.T = ctx->up_tmp.as<char>();
-    P.ucd.resize(n); P.ust.resize(n);
+    // ---- the transfers ---------------------------------------------------------------------------------------------------------
     auto add_run = [](std::vector<CopyRun>& runs, const void* src, char* dst, size_t bytes) {
         if (!bytes) return;
         // back to back on both sides — or separated by the same few padding bytes on both sides (the field-major layout of floria_hip_pack_pileups_batch
@@ -1298,7 +1351,7 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
                 const floria_pileup* p = &pileups[i];
                 if (!p->n_reads) continue;
                 const uint64_t nc = P.cp[i + 1] - P.cp[i];
-                if (kind == 3) { if (p->set_order) add_run(P.chunk_runs[g], p->set_order, D + o_so + 4 * P.cp[i], 4 * nc); continue; }
+                if (kind == 3) { if (p->set_order) add_run(P.chunk_runs[g], p->set_order, (char*)P.so_at(i), 4 * nc); continue; }
                 if (pk) {
                     if (kind == 0) add_run(P.chunk_runs[g], pk[i].present, T + t_pr + pb[i], pb[i + 1] - pb[i] - 1);
                     else if (kind == 1) add_run(P.chunk_runs[g], pk[i].allele2, T + t_a2 + a2_off(i), (nc + 3) / 4);
@@ -1309,14 +1362,7 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
                 else if (kind == 1) add_run(P.chunk_runs[g], p->allele, T + t_al + P.cp[i], nc);
                 else add_run(P.chunk_runs[g], p->qual, T + t_q + P.cp[i], nc);
             }
-    for (uint32_t i = 0; i < n; ++i) {
-        fl::UploadContig& u = P.ucd[i];
-        arena_contig(Y, D, P.rp, P.cp, i, u);
-        u.allele = (const uint8_t*)(T + t_al + P.cp[i]); u.qual = (const uint8_t*)(T + t_q + P.cp[i]);
-        P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
-    }
-    P.so_dev.assign(n, nullptr);
-    for (uint32_t i = 0; i < n; ++i) if (pileups[i].n_reads && pileups[i].set_order) P.so_dev[i] = (const uint32_t*)(D + o_so + 4 * P.cp[i]);
+    for (uint32_t i = 0; i < n; ++i) if (pileups[i].n_reads && pileups[i].set_order) P.so_dev[i] = P.so_at(i);
     if (pk) {
         P.upk.resize(n);
         for (uint32_t i = 0; i < n; ++i) {
@@ -1355,9 +1401,9 @@ hipError_t launch_flatten(floria_hip_ctx* ctx, UploadPlan& P, uint32_t g, hipStr
     hipLaunchKernelGGL(fl::flatten_kernel, dim3(wgs), dim3(64), 0, st, a);
     return hipGetLastError();
 }
-// status words -> error (if any), else the contig handles
-int finish_upload(floria_hip_ctx* ctx, UploadPlan& P, floria_hip_contig** out) {
-    const uint32_t n = P.n;
+// status words -> error (if any), else the contig handles, which own the arena from here on
+int UploadPlan::commit() {
+    const UploadPlan& P = *this;
     for (uint32_t i = 0; i < n; ++i) if (P.ust[i].err != ~0ull) {
         const std::string r = std::to_string((unsigned long long)(P.ust[i].err >> 8)), ci = n > 1 ? " (contig " + std::to_string(i) + " of the batch)" : std::string();
         switch ((uint32_t)(P.ust[i].err & 0xff)) {
@@ -1370,18 +1416,16 @@ int finish_upload(floria_hip_ctx* ctx, UploadPlan& P, floria_hip_contig** out) {
             default:                   return fail(FLORIA_E_INVALID, "reads not sorted by Frag::cmp at read " + r + ci);
         }
     }
-    if (!out) return 0;
     for (uint32_t i = 0; i < n; ++i) {
         floria_hip_contig* c = new floria_hip_contig();
         c->ctx = ctx; c->arena = P.A; c->idx = i; c->n_reads = P.ucd[i].n_reads; c->n_cells = P.cp[i + 1] - P.cp[i];
         c->max_len = P.ust[i].max_len; c->n_alleles = P.ust[i].max_allele >= 2 ? 4 : 2; c->has_q0 = P.ust[i].has_q0 != 0;
-        c->dev.read_off = P.ucd[i].read_off; c->dev.first = P.ucd[i].first; c->dev.last = P.ucd[i].last; c->dev.cell_snp = P.ucd[i].snp;
-        c->dev.cell_aw = P.ucd[i].cell_aw; c->dev.tw = P.ucd[i].tw; c->dev.meta = P.ucd[i].meta; c->dev.n_reads = P.ucd[i].n_reads;
-        c->dev.set_order = P.so_dev[i];
+        c->dev = dev(i);
         c->seq_pos = P.sp_dev.empty() ? nullptr : P.sp_dev[i];
         out[i] = c;
     }
-    P.A->refs = n;
+    A->refs = n;
+    A = nullptr;
     return 0;
 }
 
@@ -1396,25 +1440,24 @@ static int upload_batch_impl(floria_hip_ctx* ctx, const floria_pileup* pileups, 
     for (uint32_t i = 0; i < n; ++i) out[i] = nullptr;
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(ctx->device));
+    EventTimer Tm(ctx->stream);                         // (before the plan: the plan's destructor waits for the device, the timer's events go after that)
     UploadPlan P;
-    int rc = plan_upload(ctx, pileups, pk, n, 1, P);
-    if (rc) return rc;
-    EventTimer Tm(ctx->stream);
+    if (int rc = plan_upload(ctx, pileups, pk, n, 1, out, P)) return rc;
     const int th = Tm.begin(K_H2D);
     uint64_t pinned_b = 0, staged_b = 0;
     std::vector<CopyRun> runs = P.small_runs;
     runs.insert(runs.end(), P.chunk_runs[0].begin(), P.chunk_runs[0].end());
-    rc = issue_copies(ctx, runs, &pinned_b, &staged_b);
-    hipError_t e = rc ? hipSuccess : issue_tables(ctx, P, ctx->stream);
+    if (int rc = issue_copies(ctx, runs, &pinned_b, &staged_b)) return rc;
+    HIPCHK_AS("contig upload: ", issue_tables(ctx, P, ctx->stream));
     Tm.end(th);
-    if (!rc && e == hipSuccess) { const int tk = Tm.begin(K_SEL); e = launch_flatten(ctx, P, 0, ctx->stream); Tm.end(tk); }
-    if (!rc && e == hipSuccess) e = hipMemcpyAsync(P.ust.data(), P.T + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (!rc && e != hipSuccess) rc = fail(FLORIA_E_DEVICE, std::string("contig upload: ") + hipGetErrorString(e));
-    if (!rc) rc = finish_upload(ctx, P, out);
-    if (rc) { sync_all(ctx); arena_put(P.A); return rc; }
+    const int tk = Tm.begin(K_SEL);
+    HIPCHK_AS("contig upload: ", launch_flatten(ctx, P, 0, ctx->stream));
+    Tm.end(tk);
+    HIPCHK_AS("contig upload: ", hipMemcpyAsync(P.ust.data(), P.T + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK_AS("contig upload: ", hipStreamSynchronize(ctx->stream));
+    if (int rc = P.commit()) return rc;
     ctx->timing = floria_timing{};
-    ctx->timing.h2d_ms = Tm.sum(K_H2D); ctx->timing.select_ms = Tm.sum(K_SEL); ctx->timing.total_ms = Tm.span();
+    Tm.publish(ctx->timing);
     ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
     return 0;
 }
@@ -2065,6 +2108,48 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     return 0;
 }
 
+// "The haplosets of many contigs", as five entry points take them (haploset_stats, haploset_alleles, read_spans, hapq_batch, reassign_batch): group g holds the reads
+// grp_read[grp_off[g] .. grp_off[g + 1]) of contig grp_contig[g] (a null grp_contig: all of contig 0).
+// check() makes the tests that the host's and the kernels' indexing rests on, each before the first dereference it protects: handles non-null and of this context,
+// grp_contig below n_contigs, grp_off ascending, every read id below its contig's n_reads (and a grp_read to read it from).  `who` null: the terse wording of the older
+// entry points; else the entry point's name for the wordier one.  The null tests of contigs / grp_off themselves stay with the caller.
+// carve() + up() place the tables every kernel of them reads in a Carve the caller goes on with, in this order: the contig table (the caller's own type, as bytes),
+// grp_contig, grp_off, grp_read (a segment of `gr_pad` bytes more than the ids), grp_range (null: none).
+struct GroupTables {
+    const void* tab; size_t tab_bytes;
+    const uint32_t* grp_contig; const uint64_t* grp_off; const uint32_t *grp_read, *grp_range;
+    uint32_t n_groups;
+    Seg s_cd{}, s_gc{}, s_go{}, s_gr{}, s_rg{};
+    std::vector<uint32_t> zeros;                      // what a null grp_contig stands for
+
+    static int check(const floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
+                     const uint32_t* grp_read, uint32_t n_groups, const char* who) {
+        for (uint32_t i = 0; i < n_contigs; ++i) {
+            if (!contigs[i]) return fail(FLORIA_E_INVALID, who ? "null argument" : "bad contig handle");
+            if (contigs[i]->ctx != ctx) return fail(FLORIA_E_INVALID, who ? std::string(who) + ": contig " + std::to_string(i) + " belongs to another context" : std::string("bad contig handle"));
+        }
+        for (uint32_t g = 0; g < n_groups; ++g) {
+            const uint32_t c = grp_contig ? grp_contig[g] : 0;
+            if (c >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
+            if (grp_off[g + 1] < grp_off[g]) return fail(FLORIA_E_INVALID, "grp_off decreases");
+            if (grp_off[g + 1] > grp_off[g] && !grp_read) return fail(FLORIA_E_INVALID, "null argument");
+            for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) if (grp_read[i] >= contigs[c]->n_reads) return fail(FLORIA_E_INVALID, "group read id out of range");
+        }
+        return 0;
+    }
+    void carve(Carve& C, size_t gr_pad) {
+        s_cd = C.seg(tab_bytes); s_gc = C.seg(4ull * n_groups); s_go = C.seg(8ull * (n_groups + 1)); s_gr = C.seg(4 * grp_off[n_groups] + gr_pad);
+        s_rg = C.seg(grp_range ? 8ull * n_groups : 0);
+        if (!grp_contig) zeros.assign(n_groups, 0);
+    }
+    int up(const Carve& C, hipStream_t st) const {
+        HIPCHK(C.up(s_cd, tab, tab_bytes, st)); HIPCHK(C.up(s_gc, grp_contig ? grp_contig : zeros.data(), 4ull * n_groups, st));
+        HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), st)); HIPCHK(C.up(s_gr, grp_read, 4 * grp_off[n_groups], st));
+        if (grp_range) HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, st));
+        return 0;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -2119,24 +2204,26 @@ static int phase_pileups_impl(floria_hip_ctx* ctx, const floria_pileup* pileups,
     if (ctx->knobs.arith && !ctx->knobs.upload_chunks) want_chunks = std::min<uint32_t>(want_chunks, 2);
     // (measured, config 4, H2D-inclusive: 500 contigs / 0.66 GB: 2 chunks 60.5 ms, 3-4 chunks 56.5; 1000 contigs / 1.33 GB: 2 chunks 86 ms, 4-5 chunks 77; 2000 contigs: 5 chunks)
     // batches small enough for speculative ploidy stages (s1_core) keep chunk groups x stage width within the hardware queues
-    UploadPlan UP;
     uint32_t chunk_cap = floria_hip_ctx::MAX_GROUPS;
     if (!ctx->knobs.upload_chunks && ctx->knobs.speculate < 0 && prm->max_ploidy >= 3) {
         if (n_blocks <= (uint32_t)ctx->n_cu * 18) chunk_cap = std::max<uint32_t>(1, 10 / prm->max_ploidy);          // (the thresholds of s1_core's stage plan)
         else if (n_blocks <= (uint32_t)ctx->n_cu * 23 && prm->max_ploidy >= 4) chunk_cap = std::max<uint32_t>(1, 10 / std::max<uint32_t>(3, prm->max_ploidy - 3));
     }
-    int rc = plan_upload(ctx, pileups, pk, n_contigs, std::min<uint32_t>(std::min(want_chunks, chunk_cap), floria_hip_ctx::MAX_GROUPS), UP);
-    if (rc) return rc;
-    std::vector<floria_hip_contig*> handles(n_contigs, nullptr);
-    auto drop = [&](int code) { sync_all(ctx); for (auto* h : handles) if (h) { h->arena = nullptr; delete h; } arena_put(UP.A); return code; };
-    bool pipelined = UP.all_pinned && UP.n_chunks > 1;
-    const bool arith_pipe = pipelined && ctx->knobs.arith != 0;      // reference-arithmetic mode: every chunk's cell orders are computed behind its flatten launch (round 6; until then this mode uploaded the whole batch first)
+    // what an error return releases, each by a guard of its own: the result, the handles once they own the arena (UploadPlan::commit), and — by the plan itself, which
+    // stands last so that it waits for the device before any host array a copy reads from goes — the arena until then
+    struct Result { floria_block_result* r = nullptr; ~Result() { floria_hip_block_result_free(r); } } res;
+    struct Handles { std::vector<floria_hip_contig*> v; ~Handles() { for (auto* h : v) floria_hip_contig_free(h); } } own{std::vector<floria_hip_contig*>(n_contigs, nullptr)};
+    std::vector<floria_hip_contig*>& handles = own.v;
+    floria_block_result*& R = res.r;
     OrderPlan OP;
     std::vector<fl::ContigDev> pipe_cdev;
     std::vector<uint64_t> pipe_cells;
+    UploadPlan UP;
+    if (int rc = plan_upload(ctx, pileups, pk, n_contigs, std::min<uint32_t>(std::min(want_chunks, chunk_cap), floria_hip_ctx::MAX_GROUPS), handles.data(), UP)) return rc;
+    bool pipelined = UP.all_pinned && UP.n_chunks > 1;
+    const bool arith_pipe = pipelined && ctx->knobs.arith != 0;      // reference-arithmetic mode: every chunk's cell orders are computed behind its flatten launch (round 6; until then this mode uploaded the whole batch first)
     const uint64_t order_scratch = 64ull << 20;
     uint64_t pinned_b = 0, staged_b = 0;
-    floria_block_result* R = nullptr;
     if (pipelined) {
         if (!ctx->copy_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         if (!ctx->flat_stream) {                    // highest priority: when wave slots free up, a waiting flatten launch goes first
@@ -2148,48 +2235,41 @@ static int phase_pileups_impl(floria_hip_ctx* ctx, const floria_pileup* pileups,
             if (!ctx->ev_chunk[g]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_chunk[g], hipEventDisableTiming));
             if (!ctx->ev_copied[g]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_copied[g], hipEventDisableTiming));
         }
-        rc = issue_copies(ctx, UP.small_runs, &pinned_b, &staged_b);                       // main stream: read_off / first / last + tables
-        hipError_t e = rc ? hipSuccess : issue_tables(ctx, UP, ctx->stream);
+        if (int rc = issue_copies(ctx, UP.small_runs, &pinned_b, &staged_b)) return rc;     // main stream: read_off / first / last + tables
+        HIPCHK_AS("pipelined upload: ", issue_tables(ctx, UP, ctx->stream));
         pipe_cdev.resize(n_contigs); pipe_cells.resize(n_contigs);
-        for (uint32_t i = 0; i < n_contigs; ++i) {
-            fl::ContigDev& d = pipe_cdev[i];
-            d.read_off = UP.ucd[i].read_off; d.first = UP.ucd[i].first; d.last = UP.ucd[i].last; d.cell_snp = UP.ucd[i].snp;
-            d.cell_aw = UP.ucd[i].cell_aw; d.tw = UP.ucd[i].tw; d.meta = UP.ucd[i].meta; d.n_reads = n_reads_of(i);
-            d.set_order = UP.so_dev[i];
-            pipe_cells[i] = UP.cp[i + 1] - UP.cp[i];
-        }
+        for (uint32_t i = 0; i < n_contigs; ++i) { pipe_cdev[i] = UP.dev(i); pipe_cells[i] = UP.cp[i + 1] - UP.cp[i]; }
         size_t ord_cdev_off = 0, ord_todo_words = 0;
-        if (arith_pipe && !rc && e == hipSuccess) {
+        if (arith_pipe) {
             // the order kernels' tables: prefix sums + status word | the contigs' device arrays; the todo lists of the chunks (one count word each) + the emulation's scratch
             order_plan(pipe_cdev, pipe_cells, OP);
             ord_cdev_off = (OP.pre.size() * 8 + 255) & ~(size_t)255;
             ord_todo_words = OP.R_all + UP.n_chunks;
-            rc = ctx->arith_tab.ensure(ord_cdev_off + sizeof(fl::ContigDev) * n_contigs);
-            if (!rc) rc = ctx->arith_ord.ensure(8 * OP.cells + 16);
-            if (!rc) rc = ctx->arith_scr.ensure(((8 * ord_todo_words + 255) & ~(size_t)255) + order_scratch);
-            if (!rc) e = hipMemcpyAsync(ctx->arith_tab.p, OP.pre.data(), OP.pre.size() * 8, hipMemcpyHostToDevice, ctx->stream);       // (OP / pipe_cdev live until this call returns, behind a sync)
-            if (!rc && e == hipSuccess) e = hipMemcpyAsync(ctx->arith_tab.as<char>() + ord_cdev_off, pipe_cdev.data(), sizeof(fl::ContigDev) * n_contigs, hipMemcpyHostToDevice, ctx->stream);
-            for (uint32_t g = 0; g < UP.n_chunks && !rc && e == hipSuccess; ++g) e = hipMemsetAsync(ctx->arith_scr.as<uint64_t>() + OP.pre[UP.chunk_first[g]] + g, 0, 8, ctx->stream);      // the chunks' todo counters
             ctx->ord_epoch = ~0ull;                                                            // (the cached orders are being overwritten)
+            if (int rc = ctx->arith_tab.ensure(ord_cdev_off + sizeof(fl::ContigDev) * n_contigs)) return rc;
+            if (int rc = ctx->arith_ord.ensure(8 * OP.cells + 16)) return rc;
+            if (int rc = ctx->arith_scr.ensure(((8 * ord_todo_words + 255) & ~(size_t)255) + order_scratch)) return rc;
+            // (OP / pipe_cdev live until this call returns, behind a sync)
+            HIPCHK_AS("pipelined upload: ", hipMemcpyAsync(ctx->arith_tab.p, OP.pre.data(), OP.pre.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK_AS("pipelined upload: ", hipMemcpyAsync(ctx->arith_tab.as<char>() + ord_cdev_off, pipe_cdev.data(), sizeof(fl::ContigDev) * n_contigs, hipMemcpyHostToDevice, ctx->stream));
+            for (uint32_t g = 0; g < UP.n_chunks; ++g)                                         // the chunks' todo counters
+                HIPCHK_AS("pipelined upload: ", hipMemsetAsync(ctx->arith_scr.as<uint64_t>() + OP.pre[UP.chunk_first[g]] + g, 0, 8, ctx->stream));
         }
-        if (!rc && e == hipSuccess) e = hipEventRecord(ctx->ev_chunk[UP.n_chunks], ctx->stream);
-        if (!rc && e == hipSuccess) e = hipStreamWaitEvent(ctx->flat_stream, ctx->ev_chunk[UP.n_chunks], 0);
-        for (uint32_t g = 0; g < UP.n_chunks && !rc && e == hipSuccess; ++g) {             // copy stream: the cells of chunk g, back to back with chunk g+1;
-            for (const CopyRun& r : UP.chunk_runs[g]) { pinned_b += r.bytes; if (e == hipSuccess) e = hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyHostToDevice, ctx->copy_stream); }
-            if (e == hipSuccess) e = hipEventRecord(ctx->ev_copied[g], ctx->copy_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(ctx->flat_stream, ctx->ev_copied[g], 0);       // flatten stream: validate + flatten chunk g
-            if (e == hipSuccess) e = launch_flatten(ctx, UP, g, ctx->flat_stream);
-            if (e == hipSuccess && arith_pipe) {                                            // ... and the iteration orders of its reads' position sets (arith_kernel.h)
+        HIPCHK_AS("pipelined upload: ", hipEventRecord(ctx->ev_chunk[UP.n_chunks], ctx->stream));
+        HIPCHK_AS("pipelined upload: ", hipStreamWaitEvent(ctx->flat_stream, ctx->ev_chunk[UP.n_chunks], 0));
+        for (uint32_t g = 0; g < UP.n_chunks; ++g) {                                           // copy stream: the cells of chunk g, back to back with chunk g+1;
+            for (const CopyRun& r : UP.chunk_runs[g]) { pinned_b += r.bytes; HIPCHK_AS("pipelined upload: ", hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyHostToDevice, ctx->copy_stream)); }
+            HIPCHK_AS("pipelined upload: ", hipEventRecord(ctx->ev_copied[g], ctx->copy_stream));
+            HIPCHK_AS("pipelined upload: ", hipStreamWaitEvent(ctx->flat_stream, ctx->ev_copied[g], 0));       // flatten stream: validate + flatten chunk g
+            HIPCHK_AS("pipelined upload: ", launch_flatten(ctx, UP, g, ctx->flat_stream));
+            if (arith_pipe) {                                                                  // ... and the iteration orders of its reads' position sets (arith_kernel.h)
                 const uint32_t c0 = UP.chunk_first[g], c1 = UP.chunk_first[g + 1];
-                const int orc = order_launch(ctx, OP, (const fl::ContigDev*)(ctx->arith_tab.as<char>() + ord_cdev_off), c0, c1, ctx->arith_scr.as<uint64_t>() + OP.pre[c0] + g,
-                                             ctx->arith_scr.as<uint8_t>() + ((8 * ord_todo_words + 255) & ~(size_t)255), order_scratch, 0,
-                                             &((const fl::UploadStatus*)(UP.T + UP.t_st) + c0)->max_len, ctx->flat_stream);
-                if (orc) rc = orc;
+                if (int rc = order_launch(ctx, OP, (const fl::ContigDev*)(ctx->arith_tab.as<char>() + ord_cdev_off), c0, c1, ctx->arith_scr.as<uint64_t>() + OP.pre[c0] + g,
+                                          ctx->arith_scr.as<uint8_t>() + ((8 * ord_todo_words + 255) & ~(size_t)255), order_scratch, 0,
+                                          &((const fl::UploadStatus*)(UP.T + UP.t_st) + c0)->max_len, ctx->flat_stream)) return rc;
             }
-            if (e == hipSuccess) e = hipEventRecord(ctx->ev_chunk[g], ctx->flat_stream);
+            HIPCHK_AS("pipelined upload: ", hipEventRecord(ctx->ev_chunk[g], ctx->flat_stream));
         }
-        if (!rc && e != hipSuccess) rc = fail(FLORIA_E_DEVICE, std::string("pipelined upload: ") + hipGetErrorString(e));
-        if (rc) return drop(rc);
         S1Contigs SC;
         SC.cdev = pipe_cdev;
         if (arith_pipe) { SC.n_cells = pipe_cells; SC.orders_in_flight = true; }
@@ -2199,40 +2279,32 @@ static int phase_pileups_impl(floria_hip_ctx* ctx, const floria_pileup* pileups,
         // not starved by persistent grids that already own every wave slot.  Measured on config 4 (5 chunks, three runs each, ms per step; chunk -> group):
         // 0|111|2 106.7, 0|11|22 107.7, 00|11|2 108.0, 000|11 108.9, 00|111 108.9, 0|1111 109.3, a group per chunk 109.6, one group 109.4
         if (pk) { SC.chunk_groups = 3; SC.ends_apart = true; }
-        rc = s1_core(ctx, SC, blk_contig, blk_start, blk_end, n_blocks, prm, &R);
-        if (rc) return drop(rc);
+        if (int rc = s1_core(ctx, SC, blk_contig, blk_start, blk_end, n_blocks, prm, &R)) return rc;
         const floria_timing tm = ctx->timing;
-        hipError_t e2 = hipMemcpy(UP.ust.data(), UP.T + UP.t_st, sizeof(fl::UploadStatus) * n_contigs, hipMemcpyDeviceToHost);
-        if (e2 != hipSuccess) { floria_hip_block_result_free(R); return drop(fail(FLORIA_E_DEVICE, std::string("upload status: ") + hipGetErrorString(e2))); }
-        rc = finish_upload(ctx, UP, handles.data());
-        if (!rc && arith_pipe) {
+        HIPCHK_AS("upload status: ", hipMemcpy(UP.ust.data(), UP.T + UP.t_st, sizeof(fl::UploadStatus) * n_contigs, hipMemcpyDeviceToHost));
+        if (int rc = UP.commit()) return rc;
+        if (arith_pipe) {
             uint64_t bad = 0;
-            e2 = hipMemcpy(&bad, ctx->arith_tab.as<uint64_t>() + 2 * (size_t)n_contigs + 2, 8, hipMemcpyDeviceToHost);
-            if (e2 != hipSuccess) rc = fail(FLORIA_E_DEVICE, std::string("set-order status: ") + hipGetErrorString(e2));
-            else rc = order_bad_read(OP, bad);
-            if (!rc) { ctx->ord_epoch = ctx->upload_epoch; ctx->ord_sig = OP.sig; }          // S2 / the next S1 call over these contigs reuses the orders
-            if (rc) { floria_hip_block_result_free(R); for (auto* h : handles) floria_hip_contig_free(h); return rc; }      // (the handles own the arena by now)
+            HIPCHK_AS("set-order status: ", hipMemcpy(&bad, ctx->arith_tab.as<uint64_t>() + 2 * (size_t)n_contigs + 2, 8, hipMemcpyDeviceToHost));
+            if (int rc = order_bad_read(OP, bad)) return rc;
+            ctx->ord_epoch = ctx->upload_epoch; ctx->ord_sig = OP.sig;                      // S2 / the next S1 call over these contigs reuses the orders
         }
-        if (rc) { floria_hip_block_result_free(R); for (auto*& h : handles) h = nullptr; return drop(rc); }
         bool plan_ok = true;
         for (auto* h : handles) plan_ok = plan_ok && h->n_alleles == 2 && !h->has_q0;
         if (!plan_ok) {                                                                   // rare: phase again with the kernels this batch needs
             floria_hip_block_result_free(R); R = nullptr;
-            rc = floria_hip_phase_blocks_batch(ctx, handles.data(), n_contigs, blk_contig, blk_start, blk_end, n_blocks, prm, &R);
-            if (rc) { for (auto* h : handles) floria_hip_contig_free(h); return rc; }
+            if (int rc = floria_hip_phase_blocks_batch(ctx, handles.data(), n_contigs, blk_contig, blk_start, blk_end, n_blocks, prm, &R)) return rc;
         } else ctx->timing = tm;
     } else {
-        arena_put(UP.A);                                                                  // (back to the cache: the plain upload takes it from there)
-        rc = upload_batch_impl(ctx, pileups, pk, n_contigs, handles.data());
-        if (rc) return rc;
+        UP.release();                                                                     // (back to the cache: the plain upload takes it from there)
+        if (int rc = upload_batch_impl(ctx, pileups, pk, n_contigs, handles.data())) return rc;
         pinned_b = ctx->timing.upload_pinned_bytes; staged_b = ctx->timing.upload_staged_bytes;
-        rc = floria_hip_phase_blocks_batch(ctx, handles.data(), n_contigs, blk_contig, blk_start, blk_end, n_blocks, prm, &R);
-        if (rc) { for (auto* h : handles) floria_hip_contig_free(h); return rc; }
+        if (int rc = floria_hip_phase_blocks_batch(ctx, handles.data(), n_contigs, blk_contig, blk_start, blk_end, n_blocks, prm, &R)) return rc;
     }
     ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b; ctx->timing.upload_chunks = pipelined ? UP.n_chunks : 1;
-    if (keep) for (uint32_t i = 0; i < n_contigs; ++i) keep[i] = handles[i];
-    else { for (auto* h : handles) floria_hip_contig_free(h); ctx->batch_token = 0; R->batch_token = 0; }     // nothing stays resident: no hap graph for this batch
-    *out = R;
+    if (keep) { for (uint32_t i = 0; i < n_contigs; ++i) keep[i] = handles[i]; handles.clear(); }
+    else { ctx->batch_token = 0; R->batch_token = 0; }     // nothing stays resident (the handles go with this call): no hap graph for this batch
+    *out = R; R = nullptr;
     return 0;
 }
 
@@ -2351,35 +2423,28 @@ int floria_hip_haploset_stats(floria_hip_ctx* ctx, const floria_hip_contig* cons
                               const uint32_t* grp_range, uint32_t n_groups, double* out4) {
     if (!ctx || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range || !out4))) return fail(FLORIA_E_INVALID, "null argument");
     if (n_groups == 0) return 0;
+    if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, nullptr)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    ctx->batch_token = 0;
+    ctx->batch_token = 0;                                  // misc is about to be overwritten (floria_hip_hap_graph checks the token)
     uint32_t A = 2;
     std::vector<fl::ContigDev> cdev(n_contigs);
-    for (uint32_t i = 0; i < n_contigs; ++i) {
-        if (!contigs[i] || contigs[i]->ctx != ctx) return fail(FLORIA_E_INVALID, "bad contig handle");
-        A = std::max(A, contigs[i]->n_alleles); cdev[i] = contigs[i]->dev;
-    }
-    std::vector<uint32_t> gc(n_groups, 0);
+    for (uint32_t i = 0; i < n_contigs; ++i) { A = std::max(A, contigs[i]->n_alleles); cdev[i] = contigs[i]->dev; }
     std::vector<uint64_t> hoff(n_groups + 1, 0);
     for (uint32_t g = 0; g < n_groups; ++g) {
-        gc[g] = grp_contig ? grp_contig[g] : 0;
-        if (gc[g] >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
-        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) if (grp_read[i] >= contigs[gc[g]]->n_reads) return fail(FLORIA_E_INVALID, "group read id out of range");
         const uint32_t lo = grp_range[2 * g], hi = grp_range[2 * g + 1];
         hoff[g + 1] = hoff[g] + (hi >= lo ? (uint64_t)(hi - lo + 1) * A : 0);
     }
-    const uint64_t n_reads_tot = grp_off[n_groups];
     Carve C;
-    const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4ull * n_reads_tot + 4),
-              s_rg = C.seg(8ull * n_groups), s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * hoff[n_groups] + 4), s_out = C.seg(32ull * n_groups);
-    int rc = C.place(ctx->misc); if (rc) return rc;
-    HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, gc.data(), 4ull * n_groups, ctx->stream));
-    HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4ull * n_reads_tot, ctx->stream));
-    HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, ctx->stream)); HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
+    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
+    G.carve(C, 4);
+    const Seg s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * hoff[n_groups] + 4), s_out = C.seg(32ull * n_groups);
+    if (int rc = C.place(ctx->misc)) return rc;
+    if (int rc = G.up(C, ctx->stream)) return rc;
+    HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
     HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
     fl::StatsArgs a{};
-    a.contigs = C.at<const fl::ContigDev>(s_cd); a.grp_contig = C.at<const uint32_t>(s_gc); a.grp_off = C.at<const uint64_t>(s_go);
-    a.grp_read = C.at<const uint32_t>(s_gr); a.grp_range = C.at<const uint32_t>(s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
+    a.contigs = C.at<const fl::ContigDev>(G.s_cd); a.grp_contig = C.at<const uint32_t>(G.s_gc); a.grp_off = C.at<const uint64_t>(G.s_go);
+    a.grp_read = C.at<const uint32_t>(G.s_gr); a.grp_range = C.at<const uint32_t>(G.s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
     a.hist = C.at<uint32_t>(s_h); a.out = C.at<double>(s_out); a.n_groups = n_groups;
     if (A == 2) hipLaunchKernelGGL(fl::stats_kernel<2>, dim3(n_groups), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(fl::stats_kernel<4>, dim3(n_groups), dim3(256), 0, ctx->stream, a);
@@ -2583,13 +2648,11 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
         // (the table travels from its first used entry: the kernels index it with the caller's offsets)
         a.snp_pos = C.at<const int64_t>(s_sp) - snp_b; a.alleles = C.at<const uint8_t>(s_al) - 4 * snp_b; a.n_alleles = C.at<const uint8_t>(s_na) - snp_b;
         a.cell_off = C.at<uint64_t>(s_off); a.ref_end = C.at<int64_t>(s_re); a.n_records = n;
-        const uint32_t grid = chain_grid(ctx, (uint32_t)std::min<uint64_t>(((uint64_t)n + 3) / 4, (uint64_t)ctx->n_cu * 8));      // one wavefront per record, grid-stride beyond 8 workgroups per CU
+        const uint32_t grid = items_grid(ctx, n, 4);      // one wavefront per record
         int t = T.begin(K_PILEUP);
         hipLaunchKernelGGL(fl::pileup_walk_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(fl::pileup_scan_tiles_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, a.cell_off, C.at<uint64_t>(s_tile), n);
-        hipLaunchKernelGGL(fl::pileup_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, C.at<uint64_t>(s_tile), n_tiles, a.cell_off + n);
-        hipLaunchKernelGGL(fl::pileup_scan_add_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a.cell_off, C.at<const uint64_t>(s_tile), n);
+        launch_offset_scan(ctx, a.cell_off, C.at<uint64_t>(s_tile), n);
         HIPCHK(hipGetLastError());
         T.end(t);
         t = T.begin(K_D2H);
@@ -2612,7 +2675,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
             r.alleles = a.alleles; r.n_alleles = a.n_alleles; r.ref_off = C.at<const uint64_t>(s_roff); r.ref_seq = C.at<const uint8_t>(s_ref) - ref_b;
             r.snp = a.snp; r.seq_pos = a.seq_pos; r.allele = a.allele; r.undecided = O.at<uint8_t>(o_und); r.counts = C.at<uint64_t>(s_cnt);
             r.n_cells = total; r.n_records = n;
-            const uint32_t ggrid = chain_grid(ctx, (uint32_t)std::min<uint64_t>((total + 7) / 8, (uint64_t)ctx->n_cu * 8));      // 8 cells per workgroup and trip
+            const uint32_t ggrid = items_grid(ctx, total, 8);      // 8 cells per workgroup and trip
             t = T.begin(K_PILEUP);
             HIPCHK(hipMemsetAsync(r.counts, 0, 8ull * fl::RG_N_COUNTS, ctx->stream));
             hipLaunchKernelGGL(fl::realign_decide_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, r);
@@ -2637,7 +2700,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
                 hipLaunchKernelGGL(fl::realign_fill_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, r);
                 HIPCHK(hipGetLastError());
                 HIPCHK(walk ? launch_realign_walk(ctx, *walk, ra) : launch_realign(ctx, ra));
-                const uint32_t sgrid = chain_grid(ctx, (uint32_t)std::min<uint64_t>((n_work + 255) / 256, (uint64_t)ctx->n_cu * 8));
+                const uint32_t sgrid = items_grid(ctx, n_work, 256);
                 hipLaunchKernelGGL(fl::realign_scatter_kernel, dim3(sgrid), dim3(256), 0, ctx->stream, (const uint8_t*)ra.best, (const uint64_t*)r.wcell, n_work, r.allele, r.counts);
                 HIPCHK(hipGetLastError());
                 T.end(t);
@@ -2663,7 +2726,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
         HIPCHK(hipMemcpyAsync(R->ref_end, a.ref_end, 8ull * n, hipMemcpyDeviceToHost, ctx->stream));
         T.end(t);
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.total_ms = T.span();
+        T.publish(ctx->timing);
         ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
         if (F && total) {
             if (hc[fl::RG_APPENDED] != hc[fl::RG_SCORED]) return fail(FLORIA_E_DEVICE, "realign: the work list holds another number of windows than were counted");
@@ -2799,7 +2862,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
     a.part_off = C.at<const uint64_t>(s_po); a.part_rec = C.at<const uint32_t>(s_pr); a.frag_ctg = C.at<const uint32_t>(s_fc); a.frag_off = C.at<const uint64_t>(s_fo);
     a.frag_cells = C.at<uint64_t>(s_cnt); a.n_frags = NF;
     std::vector<uint64_t> cp(n + 1, 0);
-    const uint32_t grid = chain_grid(ctx, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((NF + 3) / 4, (uint64_t)ctx->n_cu * 8)));      // one wavefront per fragment, grid-stride beyond 8 workgroups per CU
+    const uint32_t grid = items_grid(ctx, NF, 4);      // one wavefront per fragment
     int t = T.begin(K_H2D);
     if (NF) { HIPCHK(C.up(s_po, plan->part_off, 8 * (NF + 1), ctx->stream)); HIPCHK(C.up(s_pr, plan->part_rec, 4 * NP, ctx->stream)); HIPCHK(C.up(s_fc, frag_ctg.data(), 4 * NF, ctx->stream)); }
     HIPCHK(C.up(s_fo, plan->frag_off, 8ull * (n + 1), ctx->stream));
@@ -2808,9 +2871,7 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
         t = T.begin(K_PILEUP);
         hipLaunchKernelGGL((fl::assemble_kernel<false, false>), dim3(grid), dim3(256), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(fl::pileup_scan_tiles_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, a.frag_cells, C.at<uint64_t>(s_tile), nf32);
-        hipLaunchKernelGGL(fl::pileup_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, C.at<uint64_t>(s_tile), n_tiles, a.frag_cells + NF);
-        hipLaunchKernelGGL(fl::pileup_scan_add_kernel, dim3((nf32 + 255) / 256), dim3(256), 0, ctx->stream, a.frag_cells, C.at<const uint64_t>(s_tile), nf32);
+        launch_offset_scan(ctx, a.frag_cells, C.at<uint64_t>(s_tile), nf32);
         hipLaunchKernelGGL(fl::assemble_totals_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, (const uint64_t*)a.frag_cells, a.frag_off, C.at<uint64_t>(s_tot), n + 1);
         HIPCHK(hipGetLastError());
         T.end(t);
@@ -2823,94 +2884,74 @@ static int assemble_impl(floria_hip_ctx* ctx, const floria_record_summary* Y, co
         if (cp[i + 1] < cp[i]) return fail(FLORIA_E_DEVICE, "assemble: the cell offsets do not ascend");
         if (cp[i + 1] - cp[i] >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "more than 2^32 cells in one contig");
     }
-    // ---- the arena, laid out as plan_upload lays out a CSR batch of these sizes ----
-    UploadPlan P;
-    P.n = n; P.n_chunks = 1; P.packed = false;
-    ctx->upload_epoch++;
-    P.rp.assign(n + 1, 0); P.cp = cp;
-    for (uint32_t i = 0; i < n; ++i) P.rp[i + 1] = plan->frag_off[i + 1];
-    const uint64_t R = P.R = NF, CC = P.C = cp[n];
-    P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
+    // ---- the arena, as an upload of a CSR batch of these sizes would have it ----
+    std::vector<uint64_t> rp(n + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) rp[i + 1] = plan->frag_off[i + 1];
+    const uint64_t CC = cp[n];
     const bool derive_so = any_merged && CC != 0;
     const bool any_so = (plan->set_order != nullptr && CC != 0) || derive_so;
-    const ArenaLayout AL = layout_arena(R, CC, n, any_so, keep_sp);
-    const size_t o_ro = AL.o_ro, o_first = AL.o_first, o_last = AL.o_last, o_snp = AL.o_snp, o_so = AL.o_so;
-    Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
-    if (!AR) return FLORIA_E_NOMEM;
-    arena_describe(AR, AL, n, R, CC, P.rp);
-    char* D = P.D = AR->buf.as<char>();
-    if (keep_sp) { P.sp_dev.assign(n, nullptr); for (uint32_t i = 0; i < n; ++i) P.sp_dev[i] = (const uint32_t*)(D + AL.o_sp + 4 * cp[i]); }
-    size_t c2 = 0;
-    auto seg2 = [&](size_t bytes) { const size_t o = c2; c2 += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t t_al = seg2(CC + 16), t_q = seg2(CC + 16);
-    P.t_cd = seg2(sizeof(fl::UploadContig) * n); P.t_rp = seg2(8ull * (n + 1)); P.t_st = seg2(sizeof(fl::UploadStatus) * n);
-    const auto drop = [&](int rc) { sync_all(ctx); arena_put(AR); return rc; };
-    if (int rc = ctx->up_tmp.ensure(c2 + 256)) return drop(rc);
-    char* TT = P.T = ctx->up_tmp.as<char>();
-    P.ucd.resize(n); P.ust.resize(n); P.so_dev.assign(n, nullptr);
+    UploadPlan P;
+    if (int rc = P.open(ctx, n, std::move(rp), std::move(cp), any_so, keep_sp, out, true)) return rc;
     for (uint32_t i = 0; i < n; ++i) {
-        fl::UploadContig& u = P.ucd[i];
-        arena_contig(AL, D, P.rp, cp, i, u);
-        u.allele = (const uint8_t*)(TT + t_al + cp[i]); u.qual = (const uint8_t*)(TT + t_q + cp[i]);
-        P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
-        if (any_so && u.n_reads && (!derive_so || merged[i])) P.so_dev[i] = (const uint32_t*)(D + o_so + 4 * cp[i]);
+        if (keep_sp) P.sp_dev[i] = P.sp_at(i);
+        if (any_so && P.ucd[i].n_reads && (!derive_so || merged[i])) P.so_dev[i] = P.so_at(i);
     }
+    char *D = P.D, *so_all = D + P.Y.o_so;
     // ---- FILL writes the raw CSR arrays where an upload's DMA would have put them; then the upload's own validate + flatten launch ----
-    a.read_off = (uint32_t*)(D + o_ro); a.first = (uint32_t*)(D + o_first); a.last = (uint32_t*)(D + o_last);
-    a.out_snp = (uint32_t*)(D + o_snp); a.out_allele = (uint8_t*)(TT + t_al); a.out_qual = (uint8_t*)(TT + t_q);
-    if (keep_sp) { a.seq_pos = ctx->res_seq_pos; a.part_mate = part_mate ? C.at<const uint8_t>(s_pm) : nullptr; a.out_sp = (uint32_t*)(D + AL.o_sp); a.sp_overflow = C.at<uint32_t>(s_spf); }
+    a.read_off = (uint32_t*)(D + P.Y.o_ro); a.first = (uint32_t*)(D + P.Y.o_first); a.last = (uint32_t*)(D + P.Y.o_last);
+    a.out_snp = (uint32_t*)(D + P.Y.o_snp); a.out_allele = (uint8_t*)(P.T + P.t_al); a.out_qual = (uint8_t*)(P.T + P.t_q);
+    if (keep_sp) { a.seq_pos = ctx->res_seq_pos; a.part_mate = part_mate ? C.at<const uint8_t>(s_pm) : nullptr; a.out_sp = (uint32_t*)(D + P.Y.o_sp); a.sp_overflow = C.at<uint32_t>(s_spf); }
     uint32_t sp_overflow = 0;
     uint64_t pinned_b = 0, staged_b = 0;
-    int rc = 0;
-    hipError_t e = hipSuccess;
     t = T.begin(K_H2D);
-    if (any_so && !derive_so) { std::vector<CopyRun> runs{{(const char*)plan->set_order, D + o_so, (size_t)(4 * CC)}}; rc = issue_copies(ctx, runs, &pinned_b, &staged_b); }
-    if (!rc && derive_so) e = C.up(s_mg, merged.data(), 4ull * n, ctx->stream);
-    if (!rc && e == hipSuccess) e = issue_tables(ctx, P, ctx->stream);
-    if (!rc && e == hipSuccess && keep_sp) { e = hipMemsetAsync(C.at(s_spf), 0, 16, ctx->stream); if (e == hipSuccess && part_mate) e = C.up(s_pm, part_mate, NP, ctx->stream); }
+    if (any_so && !derive_so) { std::vector<CopyRun> runs{{(const char*)plan->set_order, so_all, (size_t)(4 * CC)}}; if (int rc = issue_copies(ctx, runs, &pinned_b, &staged_b)) return rc; }
+    if (derive_so) HIPCHK_AS("assemble: ", C.up(s_mg, merged.data(), 4ull * n, ctx->stream));
+    HIPCHK_AS("assemble: ", issue_tables(ctx, P, ctx->stream));
+    if (keep_sp) { HIPCHK_AS("assemble: ", hipMemsetAsync(C.at(s_spf), 0, 16, ctx->stream)); if (part_mate) HIPCHK_AS("assemble: ", C.up(s_pm, part_mate, NP, ctx->stream)); }
     T.end(t);
-    if (!rc && e == hipSuccess && NF) {
+    if (NF) {
         t = T.begin(K_PILEUP);
         if (keep_sp) hipLaunchKernelGGL((fl::assemble_kernel<true, true>), dim3(grid), dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL((fl::assemble_kernel<true, false>), dim3(grid), dim3(256), 0, ctx->stream, a);
-        e = hipGetLastError();
-        if (e == hipSuccess && derive_so) {
+        HIPCHK_AS("assemble: ", hipGetLastError());
+        if (derive_so) {
             // the set orders of the merged contigs' fragments, where an uploaded set_order would lie.  Preset to all ones: whatever the kernels leave unwritten
             // is no permutation, and the cell orders below refuse it.
             oa.cell_off = a.cell_off; oa.snp = a.snp; oa.part_off = a.part_off; oa.part_rec = a.part_rec; oa.frag_ctg = a.frag_ctg; oa.frag_cells = a.frag_cells;
-            oa.merged_snp = a.out_snp; oa.ctg_merged = C.at<const uint32_t>(s_mg); oa.set_order = (uint32_t*)(D + o_so); oa.todo = C.at<uint64_t>(s_todo);
+            oa.merged_snp = a.out_snp; oa.ctg_merged = C.at<const uint32_t>(s_mg); oa.set_order = (uint32_t*)so_all; oa.todo = C.at<uint64_t>(s_todo);
             oa.n_frags = NF; oa.n_parts = NP; oa.total_cells = CC; oa.n_records = n_rec; oa.n_contigs = n; oa.force_general = ctx->knobs.asm_order_general;
-            e = hipMemsetAsync(D + o_so, 0xff, 4 * CC, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(oa.todo, 0, 8, ctx->stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(fl::assemble_order_kernel, dim3(grid), dim3(256), 0, ctx->stream, oa);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess && n_general) {
+            HIPCHK_AS("assemble: ", hipMemsetAsync(so_all, 0xff, 4 * CC, ctx->stream));
+            HIPCHK_AS("assemble: ", hipMemsetAsync(oa.todo, 0, 8, ctx->stream));
+            hipLaunchKernelGGL(fl::assemble_order_kernel, dim3(grid), dim3(256), 0, ctx->stream, oa);
+            HIPCHK_AS("assemble: ", hipGetLastError());
+            if (n_general) {
                 hipLaunchKernelGGL(fl::assemble_order_general_kernel, dim3((oa.n_threads + 63) / 64), dim3(64), 0, ctx->stream, oa);
-                e = hipGetLastError();
+                HIPCHK_AS("assemble: ", hipGetLastError());
             }
         }
         T.end(t);
     }
-    if (!rc && e == hipSuccess) { const int tk = T.begin(K_SEL); e = launch_flatten(ctx, P, 0, ctx->stream); T.end(tk); }
-    if (!rc && e == hipSuccess) { t = T.begin(K_D2H); e = hipMemcpyAsync(P.ust.data(), TT + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && keep_sp) e = hipMemcpyAsync(&sp_overflow, C.at(s_spf), 4, hipMemcpyDeviceToHost, ctx->stream);
-        T.end(t); }
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (!rc && e != hipSuccess) rc = fail(FLORIA_E_DEVICE, std::string("assemble: ") + hipGetErrorString(e));
-    if (!rc && sp_overflow) rc = fail(FLORIA_E_UNSUPPORTED, "assemble: a sequence position of 2^31 and more cannot be kept (the SEQ_POS word has 31 bits for it)");
-    if (!rc) rc = finish_upload(ctx, P, out);
-    if (rc) { for (uint32_t c = 0; c < nc; ++c) out[c] = nullptr; return drop(rc); }
+    t = T.begin(K_SEL);
+    HIPCHK_AS("assemble: ", launch_flatten(ctx, P, 0, ctx->stream));
+    T.end(t);
+    t = T.begin(K_D2H);
+    HIPCHK_AS("assemble: ", hipMemcpyAsync(P.ust.data(), P.T + P.t_st, sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (keep_sp) HIPCHK_AS("assemble: ", hipMemcpyAsync(&sp_overflow, C.at(s_spf), 4, hipMemcpyDeviceToHost, ctx->stream));
+    T.end(t);
+    HIPCHK_AS("assemble: ", hipStreamSynchronize(ctx->stream));
+    if (sp_overflow) return fail(FLORIA_E_UNSUPPORTED, "assemble: a sequence position of 2^31 and more cannot be kept (the SEQ_POS word has 31 bits for it)");
+    if (int rc = P.commit()) return rc;
     if (any_so) {                                          // the cell orders of the batch, now: a set_order that is no permutation is refused here, and "arith" = 1 reuses them
         std::vector<fl::ContigDev> cdev(n); std::vector<uint64_t> ncells(n); uint32_t len_max = 1;
         for (uint32_t i = 0; i < n; ++i) { cdev[i] = out[i]->dev; ncells[i] = out[i]->n_cells; len_max = std::max(len_max, out[i]->max_len); }
-        e = hipMemcpyAsync(C.at(s_cdev), cdev.data(), sizeof(fl::ContigDev) * n, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        rc = e != hipSuccess ? fail(FLORIA_E_DEVICE, std::string("assemble: ") + hipGetErrorString(e)) : cell_orders(ctx, C.at<const fl::ContigDev>(s_cdev), cdev, ncells, len_max);
-        if (rc) { sync_all(ctx); for (uint32_t c = 0; c < nc; ++c) { floria_hip_contig_free(out[c]); out[c] = nullptr; } return rc; }      // (the handles own the arena by now)
+        // (the handles own the arena by now: until the orders stand, an error return frees them, behind the device)
+        struct Handles { floria_hip_ctx* ctx; floria_hip_contig** h; uint32_t n; ~Handles() { if (h) { sync_all(ctx); for (uint32_t c = 0; c < n; ++c) { floria_hip_contig_free(h[c]); h[c] = nullptr; } } } } own{ctx, out, nc};
+        HIPCHK_AS("assemble: ", hipMemcpyAsync(C.at(s_cdev), cdev.data(), sizeof(fl::ContigDev) * n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK_AS("assemble: ", hipStreamSynchronize(ctx->stream));
+        if (int rc = cell_orders(ctx, C.at<const fl::ContigDev>(s_cdev), cdev, ncells, len_max)) return rc;
+        own.h = nullptr;
     }
-    ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.select_ms = T.sum(K_SEL); ctx->timing.total_ms = T.span();
+    T.publish(ctx->timing);
     ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
     return 0;
 }
@@ -2969,8 +3010,9 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
         rp[c + 1] = rp[c] + k->n_reads; cpi[c + 1] = cpi[c] + k->n_cells;
     }
     const uint64_t Rin = rp[n], S = snp_off[n];
-    floria_mono_result* M = nullptr;                          // (allocated behind the last launch: nothing to release on the error paths before it)
-    const auto give_up = [&](int rc) { floria_hip_mono_result_free(M); M = nullptr; return rc; };
+    // (allocated behind the last launch; an error return releases it — after the arena's owner below has waited for the copies into it)
+    struct Result { floria_mono_result* r = nullptr; ~Result() { floria_hip_mono_result_free(r); } } result;
+    floria_mono_result*& M = result.r;
     const auto new_result = [&](uint64_t n_out, uint64_t n_mask) {
         M = (floria_mono_result*)calloc(1, sizeof(floria_mono_result));
         if (!M) return false;
@@ -2980,7 +3022,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
         return M->read_off && M->old_read && M->removed && M->new_first && M->new_last;
     };
     if (n == 0) {
-        if (res) { if (!new_result(0, 0)) return give_up(fail(FLORIA_E_NOMEM, "calloc")); *res = M; }
+        if (res) { if (!new_result(0, 0)) return fail(FLORIA_E_NOMEM, "calloc"); *res = M; M = nullptr; }
         return 0;
     }
     EventTimer T(ctx->stream);
@@ -2991,7 +3033,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     const Seg s_mc = C.seg(sizeof(fl::MonoContig) * n), s_rp = C.seg(8ull * (n + 1)), s_so = C.seg(8ull * (n + 1)), s_ws = C.seg(32 * S + 32), s_zk = C.seg(4 * S + 4), s_rm = C.seg(S + 16),
               s_nr = C.seg(8ull * n), s_k3 = C.seg(12 * Rin + 16), s_cdev = C.seg(sizeof(fl::ContigDev) * n), s_uc = C.seg(sizeof(fl::UploadContig) * n), s_op = C.seg(8ull * (n + 1)),
               s_or = C.seg(4 * Rin + 16), s_st = C.seg(sizeof(fl::UploadStatus) * n), s_sop = C.seg(8ull * n), s_spp = C.seg(8ull * n);
-    if (int rc = C.place(ctx->mono_buf)) return give_up(rc);
+    if (int rc = C.place(ctx->mono_buf)) return rc;
     int t = 0;
     if (with_set_order && Rin) {
         std::vector<fl::ContigDev> cdev(n); std::vector<uint64_t> ncells(n); uint32_t len_max = 1;
@@ -3003,7 +3045,7 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
         t = T.begin(K_ORDER);
         const int orc = cell_orders(ctx, C.at<const fl::ContigDev>(s_cdev), cdev, ncells, len_max);
         T.end(t);
-        if (orc) { sync_all(ctx); return give_up(orc); }
+        if (orc) { sync_all(ctx); return orc; }
     }
     // ---- count, decide, COUNT: three words per input read come back ----
     std::vector<fl::MonoContig> mc(n);
@@ -3041,12 +3083,9 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     // ---- the host's part: drop the empty reads, Frag::cmp with the old index, prefix sums ----
-    UploadPlan P;
-    P.n = n; P.n_chunks = 1; P.packed = false;
-    P.rp.assign(n + 1, 0); P.cp.assign(n + 1, 0);
+    std::vector<uint64_t> rpo(n + 1, 0), cpo(n + 1, 0);       // output reads / cells before contig c
     std::vector<uint32_t> old_read; old_read.reserve(Rin);
     std::vector<uint32_t> ro_all;                              // the output contigs' read_off arrays as the arena holds them: contig c's [n_reads + 1] entries start at rp[c] + c
-    uint64_t kept_cells = 0;
     for (uint32_t c = 0; c < n; ++c) {
         const uint32_t* k = k3.data() + 3 * rp[c];
         const size_t at = old_read.size();
@@ -3058,67 +3097,50 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
         uint64_t cells = 0;
         ro_all.push_back(0);
         for (size_t i = at; i < old_read.size(); ++i) { cells += k[3 * (size_t)old_read[i]]; ro_all.push_back((uint32_t)cells); }
-        if (cells > contigs[c]->n_cells) return give_up(fail(FLORIA_E_DEVICE, "drop_monomorphic: a contig's surviving cells outnumber its cells"));
-        P.rp[c + 1] = old_read.size(); P.cp[c + 1] = P.cp[c] + cells;
-        kept_cells += cells;
+        if (cells > contigs[c]->n_cells) return fail(FLORIA_E_DEVICE, "drop_monomorphic: a contig's surviving cells outnumber its cells");
+        rpo[c + 1] = old_read.size(); cpo[c + 1] = cpo[c] + cells;
     }
-    const uint64_t R = P.R = P.rp[n], CC = P.C = P.cp[n];
-    // ---- the arena, laid out as plan_upload lays out a CSR batch of these sizes ----
-    ctx->upload_epoch++;
-    P.chunk_first = {0, n}; P.contig_chunk.assign(n, 0);
+    const uint64_t R = rpo[n], CC = cpo[n];
+    // ---- the arena, as an upload of a CSR batch of these sizes would have it.  FILL writes the resident form, so no raw bytes exist and the tables stay in mono_buf ----
     const bool any_so = with_set_order != 0 && CC != 0;
     bool any_sp = false;                                       // an output contig carries positions iff its input does
     for (uint32_t i = 0; i < n; ++i) any_sp = any_sp || contigs[i]->seq_pos != nullptr;
-    const ArenaLayout AL = layout_arena(R, CC, n, any_so, any_sp);
-    Arena* AR = P.A = arena_get(ctx, AL.bytes + 256);
-    if (!AR) return give_up(FLORIA_E_NOMEM);
-    arena_describe(AR, AL, n, R, CC, P.rp);
-    char* D = P.D = AR->buf.as<char>();
-    const auto drop = [&](int rc) { sync_all(ctx); arena_put(AR); for (uint32_t c = 0; c < n; ++c) out[c] = nullptr; return give_up(rc); };
-    P.ucd.resize(n); P.ust.resize(n); P.so_dev.assign(n, nullptr);
+    UploadPlan P;
+    if (int rc = P.open(ctx, n, std::move(rpo), std::move(cpo), any_so, any_sp, out, false)) return rc;
     std::vector<uint32_t*> sop(n, nullptr), spp(n, nullptr);
-    if (any_sp) P.sp_dev.assign(n, nullptr);
     for (uint32_t i = 0; i < n; ++i) {
-        fl::UploadContig& u = P.ucd[i];
-        arena_contig(AL, D, P.rp, P.cp, i, u);
-        if (contigs[i]->seq_pos) { spp[i] = (uint32_t*)(D + AL.o_sp + 4 * P.cp[i]); P.sp_dev[i] = spp[i]; }
-        u.allele = nullptr; u.qual = nullptr;                   // (the raw bytes of an upload do not exist here: FILL writes the resident form)
-        P.ust[i] = fl::UploadStatus{~0ull, 0, 0, 0, 0};
-        if (any_so && u.n_reads) { sop[i] = (uint32_t*)(D + AL.o_so + 4 * P.cp[i]); P.so_dev[i] = sop[i]; }
+        if (contigs[i]->seq_pos) P.sp_dev[i] = spp[i] = P.sp_at(i);
+        if (any_so && P.ucd[i].n_reads) P.so_dev[i] = sop[i] = P.so_at(i);
     }
     a.out = C.at<const fl::UploadContig>(s_uc); a.out_prefix = C.at<const uint64_t>(s_op); a.old_read = C.at<const uint32_t>(s_or); a.status = C.at<fl::UploadStatus>(s_st);
     a.Rq1 = ctx->d_hash.as<uint64_t>(); a.Rq2 = ctx->d_hash.as<uint64_t>() + 2ull * ctx->hash_len;
     a.out_set_order = C.at<uint32_t* const>(s_sop); a.ord = ctx->cur_ord; a.n_reads_out = R;
     a.out_seq_pos = any_sp ? C.at<uint32_t* const>(s_spp) : nullptr;
-    hipError_t e = hipSuccess;
     t = T.begin(K_H2D);
-    e = C.up(s_uc, P.ucd.data(), sizeof(fl::UploadContig) * n, ctx->stream);
-    if (e == hipSuccess) e = C.up(s_op, P.rp.data(), 8ull * (n + 1), ctx->stream);
-    if (e == hipSuccess) e = C.up(s_or, old_read.data(), 4 * R, ctx->stream);
-    if (e == hipSuccess) e = C.up(s_st, P.ust.data(), sizeof(fl::UploadStatus) * n, ctx->stream);
-    if (e == hipSuccess) e = C.up(s_sop, sop.data(), 8ull * n, ctx->stream);
-    if (e == hipSuccess && any_sp) e = C.up(s_spp, spp.data(), 8ull * n, ctx->stream);
-    if (e == hipSuccess && R) e = hipMemcpyAsync(D + AL.o_ro, ro_all.data(), 4 * ro_all.size(), hipMemcpyHostToDevice, ctx->stream);
+    HIPCHK_AS("drop_monomorphic: ", C.up(s_uc, P.ucd.data(), sizeof(fl::UploadContig) * n, ctx->stream));
+    HIPCHK_AS("drop_monomorphic: ", C.up(s_op, P.rp.data(), 8ull * (n + 1), ctx->stream));
+    HIPCHK_AS("drop_monomorphic: ", C.up(s_or, old_read.data(), 4 * R, ctx->stream));
+    HIPCHK_AS("drop_monomorphic: ", C.up(s_st, P.ust.data(), sizeof(fl::UploadStatus) * n, ctx->stream));
+    HIPCHK_AS("drop_monomorphic: ", C.up(s_sop, sop.data(), 8ull * n, ctx->stream));
+    if (any_sp) HIPCHK_AS("drop_monomorphic: ", C.up(s_spp, spp.data(), 8ull * n, ctx->stream));
+    if (R) HIPCHK_AS("drop_monomorphic: ", hipMemcpyAsync(P.D + P.Y.o_ro, ro_all.data(), 4 * ro_all.size(), hipMemcpyHostToDevice, ctx->stream));
     T.end(t);
-    if (e == hipSuccess && R) {
-        const uint32_t grid = chain_grid(ctx, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((R + 3) / 4, (uint64_t)ctx->n_cu * 8)));      // one wavefront per output read, grid-stride beyond 8 workgroups per CU
+    if (R) {
+        const uint32_t grid = items_grid(ctx, R, 4);      // one wavefront per output read
         t = T.begin(K_FILL);
         hipLaunchKernelGGL(fl::mono_filter_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, a);
         T.end(t);
         if (any_so) { t = T.begin(K_ORDER); hipLaunchKernelGGL(fl::mono_order_kernel, dim3(grid), dim3(256), 0, ctx->stream, a); T.end(t); }
-        e = hipGetLastError();
+        HIPCHK_AS("drop_monomorphic: ", hipGetLastError());
     }
-    if (e == hipSuccess) {
-        t = T.begin(K_D2H);
-        e = hipMemcpyAsync(P.ust.data(), C.at(s_st), sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && res) {
-            if (!new_result(R, S)) { T.end(t); return drop(fail(FLORIA_E_NOMEM, "calloc")); }
-            if (S) e = hipMemcpyAsync(M->removed, C.at(s_rm), S, hipMemcpyDeviceToHost, ctx->stream);
-        }
-        T.end(t);
+    t = T.begin(K_D2H);
+    HIPCHK_AS("drop_monomorphic: ", hipMemcpyAsync(P.ust.data(), C.at(s_st), sizeof(fl::UploadStatus) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (res) {
+        if (!new_result(R, S)) return fail(FLORIA_E_NOMEM, "calloc");
+        if (S) HIPCHK_AS("drop_monomorphic: ", hipMemcpyAsync(M->removed, C.at(s_rm), S, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return drop(fail(e == hipErrorOutOfMemory ? FLORIA_E_NOMEM : FLORIA_E_DEVICE, std::string("drop_monomorphic: ") + hipGetErrorString(e)));
+    T.end(t);
+    HIPCHK_AS("drop_monomorphic: ", hipStreamSynchronize(ctx->stream));
     if (M) {
         memcpy(M->read_off, P.rp.data(), 8ull * (n + 1));
         if (R) memcpy(M->old_read, old_read.data(), 4 * R);
@@ -3127,13 +3149,13 @@ int floria_hip_drop_monomorphic(floria_hip_ctx* ctx, const floria_hip_contig* co
             for (uint64_t i = P.rp[c]; i < P.rp[c + 1]; ++i) { M->new_first[i] = k[3 * (size_t)old_read[i] + 1]; M->new_last[i] = k[3 * (size_t)old_read[i] + 2]; }
         }
         for (uint32_t c = 0; c < n; ++c) M->n_removed_snps += n_rm[c];
-        M->n_removed_cells = cpi[n] - kept_cells; M->n_dropped_reads = Rin - R;
+        M->n_removed_cells = cpi[n] - CC; M->n_dropped_reads = Rin - R;
     }
-    if (int rc = finish_upload(ctx, P, out)) return drop(rc);
-    ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.total_ms = T.span();
+    if (int rc = P.commit()) return rc;
+    T.publish(ctx->timing);
     const int kinds[6] = {K_CLEAR, K_COUNT, K_DECIDE, K_FCOUNT, K_FILL, K_ORDER};
     for (int k = 0; k < 6; ++k) { ctx->mono_ms[k] = T.sum(kinds[k]); ctx->timing.pileup_ms += ctx->mono_ms[k]; }
-    if (res) *res = M;
+    if (res) { *res = M; M = nullptr; }
     return 0;
 }
 
@@ -3143,19 +3165,12 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
     if (!ctx || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range || !pos_off))) return fail(FLORIA_E_INVALID, "null argument");
     if (n_groups == 0) return 0;
     if (grp_off[n_groups] && !grp_read) return fail(FLORIA_E_INVALID, "null argument");
+    if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, nullptr)) return rc;
     std::vector<fl::ContigDev> cdev(n_contigs);
-    for (uint32_t i = 0; i < n_contigs; ++i) {
-        if (!contigs[i] || contigs[i]->ctx != ctx) return fail(FLORIA_E_INVALID, "bad contig handle");
-        cdev[i] = contigs[i]->dev;
-    }
-    std::vector<uint32_t> gc(n_groups, 0);
+    for (uint32_t i = 0; i < n_contigs; ++i) cdev[i] = contigs[i]->dev;
     std::vector<uint64_t> hoff(n_groups + 1, 0);
     if (pos_off[0] != 0) return fail(FLORIA_E_INVALID, "haploset_alleles: pos_off does not start at 0");
     for (uint32_t g = 0; g < n_groups; ++g) {
-        gc[g] = grp_contig ? grp_contig[g] : 0;
-        if (gc[g] >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
-        if (grp_off[g + 1] < grp_off[g]) return fail(FLORIA_E_INVALID, "grp_off decreases");
-        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) if (grp_read[i] >= contigs[gc[g]]->n_reads) return fail(FLORIA_E_INVALID, "group read id out of range");
         const uint32_t lo = grp_range[2 * g], hi = grp_range[2 * g + 1];
         const uint64_t len = hi >= lo ? (uint64_t)(hi - lo) + 1 : 0;
         if (pos_off[g + 1] < pos_off[g] || pos_off[g + 1] - pos_off[g] != len)
@@ -3167,18 +3182,17 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
     if (!counts) return fail(FLORIA_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(ctx->device));
     ctx->batch_token = 0;                                  // misc is about to be overwritten (floria_hip_hap_graph checks the token)
-    const uint64_t n_reads_tot = grp_off[n_groups];
     Carve C;
-    const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4ull * n_reads_tot + 4),
-              s_rg = C.seg(8ull * n_groups), s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * n_counts + 4);
-    int rc = C.place(ctx->misc); if (rc) return rc;
-    HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, gc.data(), 4ull * n_groups, ctx->stream));
-    HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4ull * n_reads_tot, ctx->stream));
-    HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, ctx->stream)); HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
+    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
+    G.carve(C, 4);
+    const Seg s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * n_counts + 4);
+    if (int rc = C.place(ctx->misc)) return rc;
+    if (int rc = G.up(C, ctx->stream)) return rc;
+    HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
     HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
     fl::StatsArgs a{};
-    a.contigs = C.at<const fl::ContigDev>(s_cd); a.grp_contig = C.at<const uint32_t>(s_gc); a.grp_off = C.at<const uint64_t>(s_go);
-    a.grp_read = C.at<const uint32_t>(s_gr); a.grp_range = C.at<const uint32_t>(s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
+    a.contigs = C.at<const fl::ContigDev>(G.s_cd); a.grp_contig = C.at<const uint32_t>(G.s_gc); a.grp_off = C.at<const uint64_t>(G.s_go);
+    a.grp_read = C.at<const uint32_t>(G.s_gr); a.grp_range = C.at<const uint32_t>(G.s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
     a.hist = C.at<uint32_t>(s_h); a.out = nullptr; a.n_groups = n_groups;
     hipLaunchKernelGGL(fl::alleles_kernel, dim3(n_groups), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
@@ -3191,40 +3205,33 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
 int floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
                           const uint32_t* grp_read, const uint32_t* grp_range, uint32_t n_groups, uint32_t* left, uint32_t* right) {
     if (!ctx || (n_contigs && !contigs) || (n_groups && (!grp_contig || !grp_off || !grp_range))) return fail(FLORIA_E_INVALID, "null argument");
+    if (n_groups && grp_off[0] != 0) return fail(FLORIA_E_INVALID, "read_spans: grp_off does not start at 0");      // (here grp_read has grp_off[n_groups] entries: tested before any is read)
+    if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, "read_spans")) return rc;
     std::vector<fl::SpanContig> sc(n_contigs);
     for (uint32_t i = 0; i < n_contigs; ++i) {
         const floria_hip_contig* k = contigs[i];
-        if (!k) return fail(FLORIA_E_INVALID, "null argument");
-        if (k->ctx != ctx) return fail(FLORIA_E_INVALID, "read_spans: contig " + std::to_string(i) + " belongs to another context");
         if (!k->seq_pos) return fail(FLORIA_E_INVALID, "the contig carries no seq_pos");
         sc[i] = fl::SpanContig{k->dev.read_off, k->dev.cell_snp, k->seq_pos, k->n_reads, (uint32_t)k->n_cells};
     }
     if (n_groups == 0) return 0;
-    if (grp_off[0] != 0) return fail(FLORIA_E_INVALID, "read_spans: grp_off does not start at 0");
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        if (grp_contig[g] >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
-        if (grp_off[g + 1] < grp_off[g]) return fail(FLORIA_E_INVALID, "grp_off decreases");
-    }
     const uint64_t N = grp_off[n_groups];
     if (N == 0) return 0;
-    if (!grp_read || !left || !right) return fail(FLORIA_E_INVALID, "null argument");
+    if (!left || !right) return fail(FLORIA_E_INVALID, "null argument");
     if (N >= (1ull << 32) * 256) return fail(FLORIA_E_UNSUPPORTED, "read_spans: 2^40 and more entries in one call");
-    for (uint32_t g = 0; g < n_groups; ++g)
-        for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) if (grp_read[i] >= contigs[grp_contig[g]]->n_reads) return fail(FLORIA_E_INVALID, "group read id out of range");
     HIPCHK(hipSetDevice(ctx->device));
     Carve C;
-    const Seg s_cd = C.seg(sizeof(fl::SpanContig) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4 * N), s_rg = C.seg(8ull * n_groups),
-              s_l = C.seg(4 * N), s_r = C.seg(4 * N);
+    GroupTables G{sc.data(), sizeof(fl::SpanContig) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
+    G.carve(C, 0);
+    const Seg s_l = C.seg(4 * N), s_r = C.seg(4 * N);
     if (int rc = C.place(ctx->span_buf)) return rc;
     EventTimer T(ctx->stream);
     ctx->timing = floria_timing{};
     int t = T.begin(K_H2D);
-    HIPCHK(C.up(s_cd, sc.data(), sizeof(fl::SpanContig) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, grp_contig, 4ull * n_groups, ctx->stream));
-    HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4 * N, ctx->stream)); HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, ctx->stream));
+    if (int rc = G.up(C, ctx->stream)) return rc;
     T.end(t);
     fl::SpanArgs a{};
-    a.contigs = C.at<const fl::SpanContig>(s_cd); a.grp_contig = C.at<const uint32_t>(s_gc); a.grp_off = C.at<const uint64_t>(s_go); a.grp_read = C.at<const uint32_t>(s_gr);
-    a.grp_range = C.at<const uint32_t>(s_rg); a.left = C.at<uint32_t>(s_l); a.right = C.at<uint32_t>(s_r); a.n_entries = N; a.n_groups = n_groups; a.n_contigs = n_contigs;
+    a.contigs = C.at<const fl::SpanContig>(G.s_cd); a.grp_contig = C.at<const uint32_t>(G.s_gc); a.grp_off = C.at<const uint64_t>(G.s_go); a.grp_read = C.at<const uint32_t>(G.s_gr);
+    a.grp_range = C.at<const uint32_t>(G.s_rg); a.left = C.at<uint32_t>(s_l); a.right = C.at<uint32_t>(s_r); a.n_entries = N; a.n_groups = n_groups; a.n_contigs = n_contigs;
     t = T.begin(K_PILEUP);
     hipLaunchKernelGGL(fl::read_spans_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
@@ -3234,7 +3241,7 @@ int floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* c
     HIPCHK(hipMemcpyAsync(right, a.right, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
     T.end(t);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.pileup_ms = T.sum(K_PILEUP); ctx->timing.total_ms = T.span();
+    T.publish(ctx->timing);
     return 0;
 }
 
@@ -3319,20 +3326,19 @@ int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* c
         ctx->batch_token = 0;
         std::vector<fl::ContigDev> cdev(n_contigs);
         for (uint32_t c = 0; c < n_contigs; ++c) cdev[c] = contigs[c]->dev;
-        const uint64_t n_reads_tot = grp_off[n_groups];
         Carve C;
-        const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_gc = C.seg(4ull * n_groups), s_go = C.seg(8ull * (n_groups + 1)), s_gr = C.seg(4ull * n_reads_tot + 4),
-                  s_lo = C.seg(4ull * n_groups), s_len = C.seg(4ull * n_groups), s_co = C.seg(8ull * (n_groups + 1)), s_h = C.seg(8ull * coff[n_groups] * A + 8),
+        GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, nullptr, n_groups};
+        G.carve(C, 4);
+        const Seg s_lo = C.seg(4ull * n_groups), s_len = C.seg(4ull * n_groups), s_co = C.seg(8ull * (n_groups + 1)), s_h = C.seg(8ull * coff[n_groups] * A + 8),
                   s_c = C.seg(coff[n_groups] + 8), s_pi = C.seg(4ull * n_pairs), s_pj = C.seg(4ull * n_pairs), s_sd = C.seg(8ull * n_pairs);
         rc = C.place(ctx->misc); if (rc) return rc;
-        HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(s_gc, gc.data(), 4ull * n_groups, ctx->stream));
-        HIPCHK(C.up(s_go, grp_off, 8ull * (n_groups + 1), ctx->stream)); HIPCHK(C.up(s_gr, grp_read, 4ull * n_reads_tot, ctx->stream));
+        rc = G.up(C, ctx->stream); if (rc) return rc;
         HIPCHK(C.up(s_lo, lo.data(), 4ull * n_groups, ctx->stream)); HIPCHK(C.up(s_len, len.data(), 4ull * n_groups, ctx->stream)); HIPCHK(C.up(s_co, coff.data(), 8ull * (n_groups + 1), ctx->stream));
         HIPCHK(C.up(s_pi, pi.data(), 4ull * n_pairs, ctx->stream)); HIPCHK(C.up(s_pj, pj.data(), 4ull * n_pairs, ctx->stream));
         HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
         fl::ConsensusArgs ca{};
-        ca.contigs = C.at<const fl::ContigDev>(s_cd); ca.grp_contig = C.at<const uint32_t>(s_gc);
-        ca.grp_off = C.at<const uint64_t>(s_go); ca.grp_read = C.at<const uint32_t>(s_gr);
+        ca.contigs = C.at<const fl::ContigDev>(G.s_cd); ca.grp_contig = C.at<const uint32_t>(G.s_gc);
+        ca.grp_off = C.at<const uint64_t>(G.s_go); ca.grp_read = C.at<const uint32_t>(G.s_gr);
         ca.span_lo = C.at<const uint32_t>(s_lo); ca.span_len = C.at<const uint32_t>(s_len); ca.cons_off = C.at<const uint64_t>(s_co);
         ca.hist = C.at<unsigned long long>(s_h); ca.cons = C.at<uint8_t>(s_c); ca.n_groups = n_groups;
         if (A == 2) hipLaunchKernelGGL(fl::consensus_kernel<2>, dim3(n_groups), dim3(256), 0, ctx->stream, ca);
@@ -3387,22 +3393,18 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
     if (!ctx || !out || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range))) return fail(FLORIA_E_INVALID, "null argument");
     if ((read_order == nullptr) != (order_off == nullptr)) return fail(FLORIA_E_INVALID, "read_order and order_off go together");
     *out = nullptr;
+    if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, nullptr)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     ctx->timing = floria_timing{};
     ctx->batch_token = 0;                      // misc is about to be overwritten
     uint32_t A = 2;
     for (uint32_t i = 0; i < n_contigs; ++i) {
-        if (!contigs[i] || contigs[i]->ctx != ctx) return fail(FLORIA_E_INVALID, "bad contig handle");
         A = std::max(A, contigs[i]->n_alleles);
         if (int rc0 = host_meta(contigs[i])) return rc0;
     }
     // groups of each contig, in input order (contig-local group id = rank among the contig's groups)
     std::vector<std::vector<uint32_t>> cg(n_contigs);
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        const uint32_t ci = grp_contig ? grp_contig[g] : 0;
-        if (ci >= n_contigs) return fail(FLORIA_E_INVALID, "grp_contig out of range");
-        cg[ci].push_back(g);
-    }
+    for (uint32_t g = 0; g < n_groups; ++g) cg[grp_contig ? grp_contig[g] : 0].push_back(g);
     std::vector<uint64_t> r2g_off_base(n_contigs), r2g_base(n_contigs), grp_base(n_contigs), assign_base(n_contigs);
     std::vector<uint64_t> r2g_off_all, hist_off_all;
     std::vector<uint32_t> r2g_all, gpos0_all, multi_all;
@@ -3421,8 +3423,7 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
         for (uint32_t lg = 0; lg < cg[ci].size(); ++lg) {
             const uint32_t g = cg[ci][lg];
             for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) {
-                const uint32_t r = grp_read[i];
-                if (r >= N) return fail(FLORIA_E_INVALID, "group read id out of range");
+                const uint32_t r = grp_read[i];                                 // (validated above)
                 if (last[r] == lg) continue;
                 last[r] = lg;
                 off[r + 1]++;
@@ -3540,7 +3541,7 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
         HIPCHK(hipMemcpyAsync(assign.data(), C.at(s_as), 4ull * n_assign, hipMemcpyDeviceToHost, ctx->stream));
         T.end(td);
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        ctx->timing.reassign_ms = T.sum(K_REASSIGN); ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.total_ms = T.span();
+        T.publish(ctx->timing);
     }
     // ---- host bookkeeping per contig: rebuild groups, separate_broken_haplogroups (:27-98), sort_parts (:276-288) ----
     floria_groups** arr = (floria_groups**)calloc(std::max(1u, n_contigs), sizeof(floria_groups*));

@@ -239,3 +239,90 @@ def test_reassign_batch_mixes_chain_and_parallel_contigs(gpu_ctx, hip_lib, oracl
     finally:
         for x in res:
             x.free()
+
+
+# ---- 5. the group arguments the five haploset entry points share ------------------------------------------------------------------------------------------------
+def test_bad_group_arguments_are_refused_by_all_five_entry_points_and_a_good_call_follows(gpu_ctx, hip_lib):
+    """haploset_stats, haploset_alleles, read_spans, hapq_batch and reassign_batch take the same (contigs, grp_contig, grp_off, grp_read) and make the same four
+    memory-safety tests on the host, before any launch: each is given a grp_off that decreases at group 1, a grp_contig of n_contigs, a read id equal to its
+    contig's n_reads and a handle of another context, returns -1 with the entry point's message for that fault, and then answers the good groups with the very
+    bytes it gave before the refusals."""
+    import ctypes as C
+
+    from tests import assemble_model as am
+    from tests import pileup_model as pm
+    from tests.test_gpu_assemble import free_all, resident
+    from tests.test_gpu_mono import random_contig
+    from tests.test_gpu_spans import assemble_sp, records_of
+
+    L, capi = hip_lib.load(), hip_lib.capi
+    rng = np.random.default_rng(41)
+    pileups = [random_contig(rng, 10, 40), random_contig(rng, 12, 50)]
+    n_snps = [40, 50]
+    up = gpu_ctx.upload_batch(pileups)
+    # read_spans answers only contigs that carry positions: the same two pileups through the resident chain
+    tables = [am.grid_table(n_snps[0]), am.grid_table(n_snps[1], start=50, step=3)]
+    r0, f0 = records_of(pileups[0], tables[0], 0)
+    r1, f1 = records_of(pileups[1], tables[1], 1)
+    recs = r0 + r1
+    plan = am.build_plan(pm.walk_records(recs, tables), [f0, [[i + len(r0) for i in f] for f in f1]])
+    assert all(np.array_equal(a.snp, b.snp) and np.array_equal(a.read_off, b.read_off) for a, b in zip(plan["pileups"], pileups))
+    summary = resident(gpu_ctx, recs, tables)
+    sp = assemble_sp(gpu_ctx, summary, plan, np.zeros(len(plan["part_rec"]), np.uint8))
+    other = hip_lib.FloriaHip(0)
+    foreign = other.upload(pileups[1])
+
+    good = dict(gc=[0, 1, 1], off=[0, 3, 6, 9], reads=[0, 1, 2, 0, 1, 2, 3, 4, 5], rg=[1, 40, 1, 50, 5, 45])
+    pos = [np.ascontiguousarray(100 * np.arange(1, n + 1), np.uint64) for n in n_snps]
+
+    def call(name, handles, gc, off, reads, rg):
+        """-> (return code, message, the call's outputs as bytes)"""
+        n, ng = len(handles), len(gc)
+        arr = (C.c_void_p * n)(*handles)
+        gc, off, reads, rg = np.ascontiguousarray(gc, np.uint32), np.ascontiguousarray(off, np.uint64), np.ascontiguousarray(reads, np.uint32), np.ascontiguousarray(rg, np.uint32)
+        head = (gpu_ctx._h, arr, C.c_uint32(n), capi.ptr(gc, C.c_uint32), capi.ptr(off, C.c_uint64), capi.ptr(reads, C.c_uint32), capi.ptr(rg, C.c_uint32), C.c_uint32(ng))
+        if name == "haploset_stats":
+            outs = [np.zeros((ng, 4), np.float64)]
+            rc = L.floria_hip_haploset_stats(*head, capi.ptr(outs[0], C.c_double))
+        elif name == "haploset_alleles":
+            pos_off = np.zeros(ng + 1, np.uint64)
+            pos_off[1:] = np.cumsum(rg[1::2].astype(np.int64) - rg[0::2] + 1)
+            outs = [np.zeros((int(pos_off[-1]), 4), np.uint32)]
+            rc = L.floria_hip_haploset_alleles(*head, capi.ptr(pos_off, C.c_uint64), capi.ptr(outs[0], C.c_uint32))
+        elif name == "read_spans":
+            outs = [np.zeros(len(reads), np.uint32), np.zeros(len(reads), np.uint32)]
+            rc = L.floria_hip_read_spans(*head, capi.ptr(outs[0], C.c_uint32), capi.ptr(outs[1], C.c_uint32))
+        elif name == "hapq_batch":
+            pp = (C.POINTER(C.c_uint64) * n)(*[capi.ptr(p, C.c_uint64) for p in pos])
+            ns = np.ascontiguousarray(n_snps, np.uint32)
+            outs = [np.zeros(ng, np.uint8), np.zeros(ng, np.float64), np.zeros(n, np.float64)]
+            rc = L.floria_hip_hapq_batch(*head, pp, capi.ptr(ns, C.c_uint32), C.c_uint64(1000), capi.ptr(outs[0], C.c_uint8), capi.ptr(outs[1], C.c_double), capi.ptr(outs[2], C.c_double))
+        else:
+            out = C.POINTER(C.POINTER(capi.CGroups))()
+            rc = L.floria_hip_reassign_batch(*head, None, None, C.c_double(M.EPS), C.byref(out))
+            outs = []
+            if rc == 0:
+                for i in range(n):
+                    g = capi.Groups(out[i].contents)
+                    outs += [np.asarray([g.n_groups], np.uint32), g.grp_off, g.grp_read, g.range]
+                L.floria_hip_groups_array_free(out, C.c_uint32(n))
+        return rc, L.floria_hip_last_error().decode(), b"|".join(o.tobytes() for o in outs)
+
+    try:
+        for name in ("haploset_stats", "haploset_alleles", "read_spans", "hapq_batch", "reassign_batch"):
+            mine = [c._h for c in (sp if name == "read_spans" else up)]
+            rc, msg, want = call(name, mine, **good)
+            assert rc == 0 and len(want) > 8, (name, rc, msg)
+            bad_reads = list(good["reads"]); bad_reads[0] = pileups[0].n_reads
+            faults = (("grp_off decreases", dict(off=[0, 3, 2, 9])),
+                      ("grp_contig out of range", dict(gc=[0, 2, 1])),
+                      ("group read id out of range", dict(reads=bad_reads)),
+                      ("belongs to another context" if name == "read_spans" else "bad contig handle", dict(handles=[mine[0], foreign._h])))
+            for needle, change in faults:
+                rc, msg, _ = call(name, **dict(dict(good, handles=mine), **change))
+                assert rc == -1 and needle in msg, (name, needle, rc, msg)
+                rc, msg, again = call(name, mine, **good)
+                assert rc == 0 and again == want, (name, "after: " + needle, rc, msg)
+    finally:
+        foreign.free(); other.close()
+        free_all(up, sp); summary.free()
