@@ -1,4 +1,5 @@
-"""ctypes mirror of include/floria_hip.h (struct layouts only; no library is loaded here)."""
+"""ctypes mirror of include/floria_hip.h (struct layouts only; no library is loaded here).  The opaque handles (floria_hip_ctx, floria_hip_contig,
+floria_hip_haplosets) have no layout: lib.py holds them as c_void_p (FloriaHip, ResidentContig, Haplosets)."""
 import ctypes as C
 
 import numpy as np

@@ -7,7 +7,7 @@
 //       beam_kernel -> optimize_kernel -> select_kernel (the stop rule sets blk_done so later
 //       ploidies skip finished blocks: no speculative work, results identical)
 //   separate_broken_haplogroups / sort_parts  part_block_manip.rs:27-98,276-288 -> host bookkeeping after
-//       reassign_kernel
+//       reassign_kernel (floria_hip_reassign_batch), or haploset_kernel.h's kernels behind it (floria_hip_reassign_batch_resident: the result stays on the device)
 // There is NO CPU compute fallback: every entry point needs a working HIP device.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +18,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
+#include <new>
 #include <numeric>
 #include <string>
 #include <utility>
@@ -48,6 +50,7 @@
 #include "assemble_order_kernel.h"
 #include "mono_kernel.h"
 #include "span_kernel.h"
+#include "haploset_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -269,6 +272,7 @@ struct floria_hip_ctx {
     double mono_ms[6] = {};                   // the last floria_hip_drop_monomorphic call's device time by kind (floria_hip_mono_timing)
     DevBuf mono_buf;                          // floria_hip_drop_monomorphic: the per-SNP tables, the per-read survivor words and the call's small tables
     DevBuf span_buf;                          // floria_hip_read_spans: the groups, the contig table and the two result arrays (a buffer of its own: no residency ends)
+    DevBuf hs_tmp;                            // floria_hip_reassign_batch_resident: the slot tables between its kernels (the handle has a buffer of its own)
     uint32_t stage_threads = 8;
 };
 
@@ -1001,7 +1005,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -2115,6 +2119,8 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
 // entry points; else the entry point's name for the wordier one.  The null tests of contigs / grp_off themselves stay with the caller.
 // carve() + up() place the tables every kernel of them reads in a Carve the caller goes on with, in this order: the contig table (the caller's own type, as bytes),
 // grp_contig, grp_off, grp_read (a segment of `gr_pad` bytes more than the ids), grp_range (null: none).
+// ... as the kernels see them: where up() put them, or the arrays of a floria_hip_haplosets handle (nothing is uploaded then)
+struct DevGroups { const void* cd = nullptr; const uint32_t* gc = nullptr; const uint64_t* go = nullptr; const uint32_t *gr = nullptr, *rg = nullptr; };
 struct GroupTables {
     const void* tab; size_t tab_bytes;
     const uint32_t* grp_contig; const uint64_t* grp_off; const uint32_t *grp_read, *grp_range;
@@ -2148,7 +2154,15 @@ struct GroupTables {
         if (grp_range) HIPCHK(C.up(s_rg, grp_range, 8ull * n_groups, st));
         return 0;
     }
+    DevGroups dev(const Carve& C) const { return DevGroups{C.at(s_cd), C.at<const uint32_t>(s_gc), C.at<const uint64_t>(s_go), C.at<const uint32_t>(s_gr), grp_range ? C.at<const uint32_t>(s_rg) : nullptr}; }
 };
+
+int stats_core(floria_hip_ctx* ctx, uint32_t A, const uint32_t* grp_range, uint32_t n_groups, GroupTables* G, DevGroups dg, double* out4);
+int alleles_core(floria_hip_ctx* ctx, const uint32_t* grp_range, uint32_t n_groups, const uint64_t* pos_off, GroupTables* G, DevGroups dg, uint32_t* counts);
+int spans_core(floria_hip_ctx* ctx, uint32_t n_contigs, uint64_t N, uint32_t n_groups, GroupTables* G, DevGroups dg, uint32_t* left, uint32_t* right);
+int hapq_core(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const std::vector<uint32_t>& gc, const uint64_t* grp_off, const uint32_t* grp_range,
+              uint32_t n_groups, const std::vector<double>& st, const std::vector<uint32_t>& lo, const std::vector<uint32_t>& len, const uint64_t* const* snp_to_genome_pos,
+              const uint32_t* n_snps, uint64_t block_length, GroupTables* G, DevGroups dg, uint8_t* hapq, double* rel_err, double* avg_err);
 
 }  // namespace
 
@@ -2424,27 +2438,35 @@ int floria_hip_haploset_stats(floria_hip_ctx* ctx, const floria_hip_contig* cons
     if (!ctx || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range || !out4))) return fail(FLORIA_E_INVALID, "null argument");
     if (n_groups == 0) return 0;
     if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, nullptr)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->batch_token = 0;                                  // misc is about to be overwritten (floria_hip_hap_graph checks the token)
     uint32_t A = 2;
     std::vector<fl::ContigDev> cdev(n_contigs);
     for (uint32_t i = 0; i < n_contigs; ++i) { A = std::max(A, contigs[i]->n_alleles); cdev[i] = contigs[i]->dev; }
+    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
+    return stats_core(ctx, A, grp_range, n_groups, &G, DevGroups{}, out4);
+}
+}  // extern "C"
+
+namespace {
+// The consumers of haplosets behind their validation: the groups come up through `G`, or lie on the device already (`G` null, `dg` = a handle's arrays).
+// grp_range and, where given, grp_off are HOST arrays (the caller's, or a handle's header mirror).
+int stats_core(floria_hip_ctx* ctx, uint32_t A, const uint32_t* grp_range, uint32_t n_groups, GroupTables* G, DevGroups dg, double* out4) {
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->batch_token = 0;                                  // misc is about to be overwritten (floria_hip_hap_graph checks the token)
     std::vector<uint64_t> hoff(n_groups + 1, 0);
     for (uint32_t g = 0; g < n_groups; ++g) {
         const uint32_t lo = grp_range[2 * g], hi = grp_range[2 * g + 1];
         hoff[g + 1] = hoff[g] + (hi >= lo ? (uint64_t)(hi - lo + 1) * A : 0);
     }
     Carve C;
-    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
-    G.carve(C, 4);
+    if (G) G->carve(C, 4);
     const Seg s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * hoff[n_groups] + 4), s_out = C.seg(32ull * n_groups);
     if (int rc = C.place(ctx->misc)) return rc;
-    if (int rc = G.up(C, ctx->stream)) return rc;
+    if (G) { if (int rc = G->up(C, ctx->stream)) return rc; dg = G->dev(C); }
     HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
     HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
     fl::StatsArgs a{};
-    a.contigs = C.at<const fl::ContigDev>(G.s_cd); a.grp_contig = C.at<const uint32_t>(G.s_gc); a.grp_off = C.at<const uint64_t>(G.s_go);
-    a.grp_read = C.at<const uint32_t>(G.s_gr); a.grp_range = C.at<const uint32_t>(G.s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
+    a.contigs = (const fl::ContigDev*)dg.cd; a.grp_contig = dg.gc; a.grp_off = dg.go;
+    a.grp_read = dg.gr; a.grp_range = dg.rg; a.hist_off = C.at<const uint64_t>(s_ho);
     a.hist = C.at<uint32_t>(s_h); a.out = C.at<double>(s_out); a.n_groups = n_groups;
     if (A == 2) hipLaunchKernelGGL(fl::stats_kernel<2>, dim3(n_groups), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(fl::stats_kernel<4>, dim3(n_groups), dim3(256), 0, ctx->stream, a);
@@ -2453,6 +2475,8 @@ int floria_hip_haploset_stats(floria_hip_ctx* ctx, const floria_hip_contig* cons
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+}  // namespace
+extern "C" {
 
 // ---- self-test of an assumption the kernels make about the hardware: the f32 screen of stable_binom_cdf_p_rev (beam_slab_kernel.h: binom_screen_f32, hardware rcp / log2)
 // against the host-libm table, over every (n, k) with n <= n_max.  *max_err_per_n receives max |screen - table| / n; the screen's tolerance assumes <= BINOM_SCREEN_C = 2e-5.
@@ -3168,6 +3192,13 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
     if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, nullptr)) return rc;
     std::vector<fl::ContigDev> cdev(n_contigs);
     for (uint32_t i = 0; i < n_contigs; ++i) cdev[i] = contigs[i]->dev;
+    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
+    return alleles_core(ctx, grp_range, n_groups, pos_off, &G, DevGroups{}, counts);
+}
+}  // extern "C"
+
+namespace {
+int alleles_core(floria_hip_ctx* ctx, const uint32_t* grp_range, uint32_t n_groups, const uint64_t* pos_off, GroupTables* G, DevGroups dg, uint32_t* counts) {
     std::vector<uint64_t> hoff(n_groups + 1, 0);
     if (pos_off[0] != 0) return fail(FLORIA_E_INVALID, "haploset_alleles: pos_off does not start at 0");
     for (uint32_t g = 0; g < n_groups; ++g) {
@@ -3183,16 +3214,15 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
     HIPCHK(hipSetDevice(ctx->device));
     ctx->batch_token = 0;                                  // misc is about to be overwritten (floria_hip_hap_graph checks the token)
     Carve C;
-    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
-    G.carve(C, 4);
+    if (G) G->carve(C, 4);
     const Seg s_ho = C.seg(8ull * (n_groups + 1)), s_h = C.seg(4ull * n_counts + 4);
     if (int rc = C.place(ctx->misc)) return rc;
-    if (int rc = G.up(C, ctx->stream)) return rc;
+    if (G) { if (int rc = G->up(C, ctx->stream)) return rc; dg = G->dev(C); }
     HIPCHK(C.up(s_ho, hoff.data(), 8ull * (n_groups + 1), ctx->stream));
     HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
     fl::StatsArgs a{};
-    a.contigs = C.at<const fl::ContigDev>(G.s_cd); a.grp_contig = C.at<const uint32_t>(G.s_gc); a.grp_off = C.at<const uint64_t>(G.s_go);
-    a.grp_read = C.at<const uint32_t>(G.s_gr); a.grp_range = C.at<const uint32_t>(G.s_rg); a.hist_off = C.at<const uint64_t>(s_ho);
+    a.contigs = (const fl::ContigDev*)dg.cd; a.grp_contig = dg.gc; a.grp_off = dg.go;
+    a.grp_read = dg.gr; a.grp_range = dg.rg; a.hist_off = C.at<const uint64_t>(s_ho);
     a.hist = C.at<uint32_t>(s_h); a.out = nullptr; a.n_groups = n_groups;
     hipLaunchKernelGGL(fl::alleles_kernel, dim3(n_groups), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
@@ -3200,6 +3230,8 @@ int floria_hip_haploset_alleles(floria_hip_ctx* ctx, const floria_hip_contig* co
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+}  // namespace
+extern "C" {
 
 // ---- first / last sequence position of a read inside a haploset's SNP range (span_kernel.h) ----------------------------------------------------------------------
 int floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
@@ -3217,21 +3249,27 @@ int floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* c
     const uint64_t N = grp_off[n_groups];
     if (N == 0) return 0;
     if (!left || !right) return fail(FLORIA_E_INVALID, "null argument");
+    GroupTables G{sc.data(), sizeof(fl::SpanContig) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
+    return spans_core(ctx, n_contigs, N, n_groups, &G, DevGroups{}, left, right);
+}
+}  // extern "C"
+
+namespace {
+int spans_core(floria_hip_ctx* ctx, uint32_t n_contigs, uint64_t N, uint32_t n_groups, GroupTables* G, DevGroups dg, uint32_t* left, uint32_t* right) {
     if (N >= (1ull << 32) * 256) return fail(FLORIA_E_UNSUPPORTED, "read_spans: 2^40 and more entries in one call");
     HIPCHK(hipSetDevice(ctx->device));
     Carve C;
-    GroupTables G{sc.data(), sizeof(fl::SpanContig) * n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups};
-    G.carve(C, 0);
+    if (G) G->carve(C, 0);
     const Seg s_l = C.seg(4 * N), s_r = C.seg(4 * N);
     if (int rc = C.place(ctx->span_buf)) return rc;
     EventTimer T(ctx->stream);
     ctx->timing = floria_timing{};
     int t = T.begin(K_H2D);
-    if (int rc = G.up(C, ctx->stream)) return rc;
+    if (G) { if (int rc = G->up(C, ctx->stream)) return rc; dg = G->dev(C); }
     T.end(t);
     fl::SpanArgs a{};
-    a.contigs = C.at<const fl::SpanContig>(G.s_cd); a.grp_contig = C.at<const uint32_t>(G.s_gc); a.grp_off = C.at<const uint64_t>(G.s_go); a.grp_read = C.at<const uint32_t>(G.s_gr);
-    a.grp_range = C.at<const uint32_t>(G.s_rg); a.left = C.at<uint32_t>(s_l); a.right = C.at<uint32_t>(s_r); a.n_entries = N; a.n_groups = n_groups; a.n_contigs = n_contigs;
+    a.contigs = (const fl::SpanContig*)dg.cd; a.grp_contig = dg.gc; a.grp_off = dg.go; a.grp_read = dg.gr;
+    a.grp_range = dg.rg; a.left = C.at<uint32_t>(s_l); a.right = C.at<uint32_t>(s_r); a.n_entries = N; a.n_groups = n_groups; a.n_contigs = n_contigs;
     t = T.begin(K_PILEUP);
     hipLaunchKernelGGL(fl::read_spans_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
@@ -3244,6 +3282,8 @@ int floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* c
     T.publish(ctx->timing);
     return 0;
 }
+}  // namespace
+extern "C" {
 
 // ---- get_hapq (part_block_manip.rs:517-616) for the haplosets of many contigs (the reference calls it once per contig) ----------
 int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig,
@@ -3263,17 +3303,9 @@ int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* c
     int rc = floria_hip_haploset_stats(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, grp_range, n_groups, st.data());
     if (rc) return rc;
     std::vector<uint32_t> gc(n_groups, 0);
-    std::vector<double> weight(n_contigs, 0.), error(n_contigs, 0.);
-    for (uint32_t g = 0; g < n_groups; ++g) {                                    // (accumulated in group order inside each contig, as the reference does)
-        gc[g] = grp_contig ? grp_contig[g] : 0;
-        weight[gc[g]] += st[4ull * g + 3]; error[gc[g]] += st[4ull * g + 2];
-    }
-    for (uint32_t c = 0; c < n_contigs; ++c) avg_err[c] = error[c] / weight[c];
-    // spans of the haplosets' reads (the consensus haplotype has a key wherever a read has a cell) and base ranges (:584-600)
-    uint32_t A = 2;
-    for (uint32_t c = 0; c < n_contigs; ++c) A = std::max(A, contigs[c]->n_alleles);
+    for (uint32_t g = 0; g < n_groups; ++g) gc[g] = grp_contig ? grp_contig[g] : 0;
+    // spans of the haplosets' reads (the consensus haplotype has a key wherever a read has a cell)
     std::vector<uint32_t> lo(n_groups, 0), len(n_groups, 0);
-    std::vector<uint64_t> coff(n_groups + 1, 0), base_range(n_groups, 0);
     for (uint32_t g = 0; g < n_groups; ++g) {
         const floria_hip_contig* c = contigs[gc[g]];
         uint32_t r0 = 0xffffffffu, r1 = 0;
@@ -3281,8 +3313,32 @@ int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* c
             const uint32_t r = grp_read[i];                                 // (validated by floria_hip_haploset_stats)
             r0 = std::min(r0, c->h_first[r]); r1 = std::max(r1, c->h_last[r]);
         }
-        if (!(r0 > r1)) {
-            lo[g] = r0; len[g] = r1 - r0 + 1;
+        if (!(r0 > r1)) { lo[g] = r0; len[g] = r1 - r0 + 1; }
+    }
+    std::vector<fl::ContigDev> cdev(n_contigs);
+    for (uint32_t c = 0; c < n_contigs; ++c) cdev[c] = contigs[c]->dev;
+    GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, nullptr, n_groups};
+    return hapq_core(ctx, contigs, n_contigs, gc, grp_off, grp_range, n_groups, st, lo, len, snp_to_genome_pos, n_snps, block_length, &G, DevGroups{}, hapq, rel_err, avg_err);
+}
+}  // extern "C"
+
+namespace {
+// get_hapq behind the statistics and the read spans (lo / len per group: len 0 = a group without reads): gc, grp_off and grp_range are host arrays
+int hapq_core(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const std::vector<uint32_t>& gc, const uint64_t* grp_off, const uint32_t* grp_range,
+              uint32_t n_groups, const std::vector<double>& st, const std::vector<uint32_t>& lo, const std::vector<uint32_t>& len, const uint64_t* const* snp_to_genome_pos,
+              const uint32_t* n_snps, uint64_t block_length, GroupTables* G, DevGroups dg, uint8_t* hapq, double* rel_err, double* avg_err) {
+    int rc = 0;
+    std::vector<double> weight(n_contigs, 0.), error(n_contigs, 0.);
+    for (uint32_t g = 0; g < n_groups; ++g) {                                    // (accumulated in group order inside each contig, as the reference does)
+        weight[gc[g]] += st[4ull * g + 3]; error[gc[g]] += st[4ull * g + 2];
+    }
+    for (uint32_t c = 0; c < n_contigs; ++c) avg_err[c] = error[c] / weight[c];
+    // base ranges (:584-600)
+    uint32_t A = 2;
+    for (uint32_t c = 0; c < n_contigs; ++c) A = std::max(A, contigs[c]->n_alleles);
+    std::vector<uint64_t> coff(n_groups + 1, 0), base_range(n_groups, 0);
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        if (len[g]) {
             const uint32_t x1 = grp_range[2 * g], x2 = grp_range[2 * g + 1];
             const uint64_t* pos = snp_to_genome_pos ? snp_to_genome_pos[gc[g]] : nullptr;
             const uint32_t ns = n_snps ? n_snps[gc[g]] : 0;
@@ -3324,21 +3380,18 @@ int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* c
     if (n_pairs) {
         HIPCHK(hipSetDevice(ctx->device));
         ctx->batch_token = 0;
-        std::vector<fl::ContigDev> cdev(n_contigs);
-        for (uint32_t c = 0; c < n_contigs; ++c) cdev[c] = contigs[c]->dev;
         Carve C;
-        GroupTables G{cdev.data(), sizeof(fl::ContigDev) * n_contigs, grp_contig, grp_off, grp_read, nullptr, n_groups};
-        G.carve(C, 4);
+        if (G) G->carve(C, 4);
         const Seg s_lo = C.seg(4ull * n_groups), s_len = C.seg(4ull * n_groups), s_co = C.seg(8ull * (n_groups + 1)), s_h = C.seg(8ull * coff[n_groups] * A + 8),
                   s_c = C.seg(coff[n_groups] + 8), s_pi = C.seg(4ull * n_pairs), s_pj = C.seg(4ull * n_pairs), s_sd = C.seg(8ull * n_pairs);
         rc = C.place(ctx->misc); if (rc) return rc;
-        rc = G.up(C, ctx->stream); if (rc) return rc;
+        if (G) { rc = G->up(C, ctx->stream); if (rc) return rc; dg = G->dev(C); }
         HIPCHK(C.up(s_lo, lo.data(), 4ull * n_groups, ctx->stream)); HIPCHK(C.up(s_len, len.data(), 4ull * n_groups, ctx->stream)); HIPCHK(C.up(s_co, coff.data(), 8ull * (n_groups + 1), ctx->stream));
         HIPCHK(C.up(s_pi, pi.data(), 4ull * n_pairs, ctx->stream)); HIPCHK(C.up(s_pj, pj.data(), 4ull * n_pairs, ctx->stream));
         HIPCHK(hipMemsetAsync(C.at(s_h), 0, s_h.bytes, ctx->stream));
         fl::ConsensusArgs ca{};
-        ca.contigs = C.at<const fl::ContigDev>(G.s_cd); ca.grp_contig = C.at<const uint32_t>(G.s_gc);
-        ca.grp_off = C.at<const uint64_t>(G.s_go); ca.grp_read = C.at<const uint32_t>(G.s_gr);
+        ca.contigs = (const fl::ContigDev*)dg.cd; ca.grp_contig = dg.gc;
+        ca.grp_off = dg.go; ca.grp_read = dg.gr;
         ca.span_lo = C.at<const uint32_t>(s_lo); ca.span_len = C.at<const uint32_t>(s_len); ca.cons_off = C.at<const uint64_t>(s_co);
         ca.hist = C.at<unsigned long long>(s_h); ca.cons = C.at<uint8_t>(s_c); ca.n_groups = n_groups;
         if (A == 2) hipLaunchKernelGGL(fl::consensus_kernel<2>, dim3(n_groups), dim3(256), 0, ctx->stream, ca);
@@ -3372,6 +3425,8 @@ int floria_hip_hapq_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* c
     }
     return 0;
 }
+}  // namespace
+extern "C" {
 
 int floria_hip_hapq(floria_hip_ctx* ctx, const floria_hip_contig* contig, const uint64_t* grp_off, const uint32_t* grp_read,
                     const uint32_t* grp_range, uint32_t n_groups, const uint64_t* snp_to_genome_pos, uint32_t n_snps,
@@ -3386,44 +3441,68 @@ int floria_hip_hapq(floria_hip_ctx* ctx, const floria_hip_contig* contig, const 
 // process_reads_for_final_parts for MANY contigs in one launch (one wavefront per contig): the reference calls it once
 // per contig from its serial contig loop (floria.rs:229,359-366); the chain is sequential inside a contig and independent
 // across contigs.
-int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
-                              const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
-                              const uint32_t* grp_range, uint32_t n_groups, const uint32_t* read_order, const uint64_t* order_off,
-                              double epsilon, floria_groups*** out) {
-    if (!ctx || !out || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range))) return fail(FLORIA_E_INVALID, "null argument");
-    if ((read_order == nullptr) != (order_off == nullptr)) return fail(FLORIA_E_INVALID, "read_order and order_off go together");
-    *out = nullptr;
+}  // extern "C"
+
+// The output of one S2 call, resident (include/floria_hip.h): the group tables the consumer kernels read and their two contig tables, in a buffer of its own.
+struct floria_hip_haplosets {
+    floria_hip_ctx* ctx = nullptr;
+    std::vector<const floria_hip_contig*> contigs;                 // the handles the call was given, in its order
+    DevBuf buf;
+    uint64_t n_groups = 0, n_reads = 0;                            // over all contigs
+    std::vector<uint64_t> c_groups, c_reads;                       // per contig: the one copy the S2 call makes
+    uint32_t A = 2;
+    const fl::ContigDev* d_cd = nullptr;
+    const fl::SpanContig* d_sc = nullptr;                          // null unless every contig carries positions
+    const uint32_t* d_gc = nullptr; const uint64_t* d_go = nullptr; const uint32_t *d_gr = nullptr, *d_rg = nullptr;
+    uint32_t *d_lo = nullptr, *d_len = nullptr;                    // get_hapq's read spans per group (hs_span_kernel), computed on first use
+    // header-sized host mirrors (16 B per group, never a read id), fetched from the device on first use: what the consumers' host parts size their tables by
+    bool have_hdr = false, have_span = false;
+    std::vector<uint64_t> h_off; std::vector<uint32_t> h_range, h_gc, h_lo, h_len;
+    ~floria_hip_haplosets() { buf.release(); }
+};
+
+namespace {
+
+// S2 up to the re-insertion kernels, shared by floria_hip_reassign_batch and floria_hip_reassign_batch_resident: validation, the host prologue (read -> candidate
+// groups, the `multi` list, p0 / p1), the call's segments in the context's scratch, the uploads and the launch with its path choice.  `assign` stays on the device.
+struct S2Plan {
+    uint32_t A = 2;
+    std::vector<std::vector<uint32_t>> cg;                         // groups of each contig, in input order (contig-local group id = rank among the contig's groups)
+    std::vector<uint64_t> r2g_off_base, r2g_base, grp_base, assign_base, r2g_off_all, hist_off_all, multi_off_all;
+    std::vector<uint32_t> r2g_all, gpos0_all, multi_all;
+    std::vector<uint32_t> rid_lo, rid_hi;                          // per group, contig-major as gpos0_all: the id window [lo, hi) of its input list (haploset_kernel.h)
+    std::vector<fl::ContigDev> cdev;
+    uint64_t hist_cells = 0, n_assign = 0;
+    Seg s_cd{}, s_rob{}, s_rb{}, s_gb{}, s_ab{}, s_ro{}, s_r2g{}, s_ho{}, s_p0{}, s_hist{}, s_as{}, s_q{}, s_ord{}, s_oo{}, s_mu{}, s_mo{}, s_ls{};
+
+    int prologue(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
+                 const uint32_t* grp_read, uint32_t n_groups, const uint32_t* read_order, const uint64_t* order_off) {
     if (int rc = GroupTables::check(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, nullptr)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     ctx->timing = floria_timing{};
     ctx->batch_token = 0;                      // misc is about to be overwritten
-    uint32_t A = 2;
     for (uint32_t i = 0; i < n_contigs; ++i) {
         A = std::max(A, contigs[i]->n_alleles);
         if (int rc0 = host_meta(contigs[i])) return rc0;
     }
-    // groups of each contig, in input order (contig-local group id = rank among the contig's groups)
-    std::vector<std::vector<uint32_t>> cg(n_contigs);
+    cg.assign(n_contigs, {});
     for (uint32_t g = 0; g < n_groups; ++g) cg[grp_contig ? grp_contig[g] : 0].push_back(g);
-    std::vector<uint64_t> r2g_off_base(n_contigs), r2g_base(n_contigs), grp_base(n_contigs), assign_base(n_contigs);
-    std::vector<uint64_t> r2g_off_all, hist_off_all;
-    std::vector<uint32_t> r2g_all, gpos0_all, multi_all;
-    std::vector<uint64_t> multi_off_all;
-    std::vector<fl::ContigDev> cdev(n_contigs);
-    uint64_t hist_cells = 0, n_assign = 0;
+    r2g_off_base.assign(n_contigs, 0); r2g_base.assign(n_contigs, 0); grp_base.assign(n_contigs, 0); assign_base.assign(n_contigs, 0);
+    cdev.assign(n_contigs, fl::ContigDev{});
     for (uint32_t ci = 0; ci < n_contigs; ++ci) {
         const floria_hip_contig* c = contigs[ci];
         cdev[ci] = c->dev;
         const uint32_t N = c->n_reads;
         // read -> groups (part_block_manip.rs:185-193) by counting sort: groups are visited in ascending local id, so every read's candidate
         // list comes out ascending; groups are sets (a repeated id inside one group counts once)
-        std::vector<uint32_t> p0(cg[ci].size(), UINT32_MAX), p1(cg[ci].size(), 0);
+        std::vector<uint32_t> p0(cg[ci].size(), UINT32_MAX), p1(cg[ci].size(), 0), w0(cg[ci].size(), UINT32_MAX), w1(cg[ci].size(), 0);
         std::vector<uint64_t> off(N + 1, 0);
         std::vector<uint32_t> last(N, UINT32_MAX);
         for (uint32_t lg = 0; lg < cg[ci].size(); ++lg) {
             const uint32_t g = cg[ci][lg];
             for (uint64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) {
                 const uint32_t r = grp_read[i];                                 // (validated above)
+                w0[lg] = std::min(w0[lg], r); w1[lg] = std::max(w1[lg], r + 1);
                 if (last[r] == lg) continue;
                 last[r] = lg;
                 off[r + 1]++;
@@ -3465,21 +3544,28 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
         for (uint32_t lg = 0; lg < cg[ci].size(); ++lg) {
             hist_off_all.push_back(hist_cells);
             gpos0_all.push_back(p0[lg] == UINT32_MAX ? 0 : p0[lg]);
+            rid_lo.push_back(w0[lg] == UINT32_MAX ? 0 : w0[lg]); rid_hi.push_back(w1[lg]);
             hist_cells += p0[lg] == UINT32_MAX ? 0 : (uint64_t)(p1[lg] - p0[lg] + 1) * A;
         }
         n_assign += N;
     }
-    std::vector<int32_t> assign(n_assign, -1);
-    if (n_assign && n_groups) {
-        Carve C;
-        const Seg s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs), s_rob = C.seg(8ull * n_contigs), s_rb = C.seg(8ull * n_contigs), s_gb = C.seg(8ull * n_contigs),
-                  s_ab = C.seg(8ull * n_contigs), s_ro = C.seg(8ull * r2g_off_all.size() + 8), s_r2g = C.seg(4ull * r2g_all.size() + 4),
-                  s_ho = C.seg(8ull * hist_off_all.size() + 8), s_p0 = C.seg(4ull * gpos0_all.size() + 4), s_hist = C.seg(8ull * hist_cells + 8),
-                  s_as = C.seg(4ull * n_assign + 4), s_q = C.seg(16), s_ord = C.seg(read_order ? 4ull * order_off[n_contigs] + 4 : 4),
-                  s_oo = C.seg(8ull * (n_contigs + 1)), s_mu = C.seg(4ull * multi_all.size() + 4), s_mo = C.seg(8ull * (n_contigs + 1)), s_ls = C.seg(4ull * n_contigs + 4);
-        multi_off_all.push_back(multi_all.size());
-        int rc = C.place(ctx->misc); if (rc) return rc;
-        EventTimer T(ctx->stream);
+    multi_off_all.push_back(multi_all.size());
+    return 0;
+    }
+
+    // the call's segments, first in the caller's Carve (it may add its own behind them before it places the Carve in ctx->misc)
+    void carve(Carve& C, uint32_t n_contigs, const uint32_t* read_order, const uint64_t* order_off) {
+        s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs); s_rob = C.seg(8ull * n_contigs); s_rb = C.seg(8ull * n_contigs); s_gb = C.seg(8ull * n_contigs);
+        s_ab = C.seg(8ull * n_contigs); s_ro = C.seg(8ull * r2g_off_all.size() + 8); s_r2g = C.seg(4ull * r2g_all.size() + 4);
+        s_ho = C.seg(8ull * hist_off_all.size() + 8); s_p0 = C.seg(4ull * gpos0_all.size() + 4); s_hist = C.seg(8ull * hist_cells + 8);
+        s_as = C.seg(4ull * n_assign + 4); s_q = C.seg(16); s_ord = C.seg(read_order ? 4ull * order_off[n_contigs] + 4 : 4);
+        s_oo = C.seg(8ull * (n_contigs + 1)); s_mu = C.seg(4ull * multi_all.size() + 4); s_mo = C.seg(8ull * (n_contigs + 1)); s_ls = C.seg(4ull * n_contigs + 4);
+    }
+
+    // uploads + the re-insertion launches, timed into T (K_H2D, K_REASSIGN); the caller goes on in the same stream
+    int run(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const Carve& C, EventTimer& T, const uint32_t* read_order,
+            const uint64_t* order_off, double epsilon) {
+        int rc = 0;
         int th = T.begin(K_H2D);
         HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream));
         HIPCHK(C.up(s_rob, r2g_off_base.data(), 8ull * n_contigs, ctx->stream)); HIPCHK(C.up(s_rb, r2g_base.data(), 8ull * n_contigs, ctx->stream));
@@ -3537,8 +3623,34 @@ int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* cons
         ctx->timing.jobs = multi_all.size();                        // reads that had a choice (the sequential part of S2)
         T.end(tk);
         HIPCHK(hipGetLastError());
+        return 0;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int floria_hip_reassign_batch(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                              const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
+                              const uint32_t* grp_range, uint32_t n_groups, const uint32_t* read_order, const uint64_t* order_off,
+                              double epsilon, floria_groups*** out) {
+    if (!ctx || !out || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range))) return fail(FLORIA_E_INVALID, "null argument");
+    if ((read_order == nullptr) != (order_off == nullptr)) return fail(FLORIA_E_INVALID, "read_order and order_off go together");
+    *out = nullptr;
+    S2Plan P;
+    if (int rc = P.prologue(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, read_order, order_off)) return rc;
+    const std::vector<std::vector<uint32_t>>& cg = P.cg;
+    const std::vector<uint64_t>& assign_base = P.assign_base;
+    std::vector<int32_t> assign(P.n_assign, -1);
+    if (P.n_assign && n_groups) {
+        Carve C;
+        P.carve(C, n_contigs, read_order, order_off);
+        int rc = C.place(ctx->misc); if (rc) return rc;
+        EventTimer T(ctx->stream);
+        rc = P.run(ctx, contigs, n_contigs, C, T, read_order, order_off, epsilon); if (rc) return rc;
         int td = T.begin(K_D2H);
-        HIPCHK(hipMemcpyAsync(assign.data(), C.at(s_as), 4ull * n_assign, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(assign.data(), C.at(P.s_as), 4ull * P.n_assign, hipMemcpyDeviceToHost, ctx->stream));
         T.end(td);
         HIPCHK(hipStreamSynchronize(ctx->stream));
         T.publish(ctx->timing);
@@ -3635,5 +3747,234 @@ void floria_hip_groups_array_free(floria_groups** arr, uint32_t n) {
     free(arr);
 }
 void floria_hip_groups_free(floria_groups* g) { if (g) { free(g->grp_off); free(g->grp_read); free(g->range); free(g); } }
+
+}  // extern "C"
+
+// ---- S2 with its epilogue on the device, and the haplosets as a handle (haploset_kernel.h) ---------------------------------------------------------------------
+namespace {
+
+// a handle's header mirror: grp_off and range per group from the device (16 B per group), grp_contig from the per-contig counts
+int hs_headers(const floria_hip_haplosets* chs) {
+    floria_hip_haplosets* hs = const_cast<floria_hip_haplosets*>(chs);
+    if (hs->have_hdr) return 0;
+    const uint64_t n = hs->n_groups;
+    hs->h_off.assign(n + 1, 0); hs->h_range.assign(2 * n, 0); hs->h_gc.assign(n, 0);
+    uint64_t g = 0;
+    for (uint32_t c = 0; c < hs->c_groups.size(); ++c) for (uint64_t i = 0; i < hs->c_groups[c]; ++i) hs->h_gc[g++] = c;
+    if (n) {
+        HIPCHK(hipSetDevice(hs->ctx->device));
+        HIPCHK(hipMemcpyAsync(hs->h_off.data(), hs->d_go, 8 * (n + 1), hipMemcpyDeviceToHost, hs->ctx->stream));
+        HIPCHK(hipMemcpyAsync(hs->h_range.data(), hs->d_rg, 8 * n, hipMemcpyDeviceToHost, hs->ctx->stream));
+        HIPCHK(hipStreamSynchronize(hs->ctx->stream));
+    }
+    hs->have_hdr = true;
+    return 0;
+}
+
+// what every call that takes a handle refuses before anything else
+int hs_check(const floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs, const char* who) {
+    if (!ctx || !hs || (n_contigs && !contigs)) return fail(FLORIA_E_INVALID, "null argument");
+    if (hs->ctx != ctx) return fail(FLORIA_E_INVALID, std::string(who) + ": the haplosets belong to another context");
+    if (n_contigs != hs->contigs.size()) return fail(FLORIA_E_INVALID, std::string(who) + ": " + std::to_string(n_contigs) + " contigs given, the haplosets were made from " + std::to_string(hs->contigs.size()));
+    for (uint32_t i = 0; i < n_contigs; ++i) {
+        if (!contigs[i]) return fail(FLORIA_E_INVALID, "null argument");
+        if (contigs[i] != hs->contigs[i]) return fail(FLORIA_E_INVALID, std::string(who) + ": contig " + std::to_string(i) + " is not the one the haplosets were made from");
+    }
+    return 0;
+}
+
+DevGroups hs_dev(const floria_hip_haplosets* hs, bool span) { return DevGroups{span ? (const void*)hs->d_sc : (const void*)hs->d_cd, hs->d_gc, hs->d_go, hs->d_gr, hs->d_rg}; }
+
+}  // namespace
+
+extern "C" {
+
+int floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                                       const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
+                                       const uint32_t* grp_range, uint32_t n_groups, const uint32_t* read_order, const uint64_t* order_off,
+                                       double epsilon, floria_hip_haplosets** out) {
+    if (!ctx || !out || (n_contigs && !contigs) || (n_groups && (!grp_off || !grp_range))) return fail(FLORIA_E_INVALID, "null argument");
+    if ((read_order == nullptr) != (order_off == nullptr)) return fail(FLORIA_E_INVALID, "read_order and order_off go together");
+    *out = nullptr;
+    S2Plan P;
+    if (int rc = P.prologue(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, read_order, order_off)) return rc;
+    std::unique_ptr<floria_hip_haplosets> hs(new (std::nothrow) floria_hip_haplosets);
+    if (!hs) return fail(FLORIA_E_NOMEM, "new");
+    hs->ctx = ctx; hs->contigs.assign(contigs, contigs + n_contigs); hs->A = P.A;
+    hs->c_groups.assign(n_contigs, 0); hs->c_reads.assign(n_contigs, 0);
+    if (n_groups == 0) { *out = hs.release(); return 0; }
+    // the input groups contig-major, as the prologue numbers them
+    const uint32_t n_in = n_groups;
+    std::vector<uint64_t> gb(n_contigs + 1, 0);
+    std::vector<uint32_t> in_contig(n_in), in_range(2ull * n_in);
+    for (uint32_t ci = 0; ci < n_contigs; ++ci) {
+        gb[ci + 1] = gb[ci] + P.cg[ci].size();
+        for (uint32_t lg = 0; lg < P.cg[ci].size(); ++lg) {
+            const uint64_t k = gb[ci] + lg; const uint32_t g = P.cg[ci][lg];
+            in_contig[k] = ci; in_range[2 * k] = grp_range[2 * g]; in_range[2 * k + 1] = grp_range[2 * g + 1];
+        }
+    }
+    Carve C;
+    P.carve(C, n_contigs, read_order, order_off);
+    const uint32_t tiles_in = (n_in + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+    const Seg s_gb2 = C.seg(8ull * (n_contigs + 1)), s_ic = C.seg(4ull * n_in), s_ir = C.seg(8ull * n_in), s_rl = C.seg(4ull * n_in), s_rh = C.seg(4ull * n_in),
+              s_no = C.seg(8ull * (n_in + 1)), s_ko = C.seg(8ull * (n_in + 1)), s_ti = C.seg(8ull * tiles_in + 8), s_cnt = C.seg(16ull * n_contigs);
+    int rc = C.place(ctx->misc); if (rc) return rc;
+    EventTimer T(ctx->stream);
+    if (P.n_assign) { rc = P.run(ctx, contigs, n_contigs, C, T, read_order, order_off, epsilon); if (rc) return rc; }
+    else {                                             // no read at all: nothing to re-insert, the groups stay (empty, with their ranges)
+        HIPCHK(C.up(P.s_cd, P.cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(C.up(P.s_ab, P.assign_base.data(), 8ull * n_contigs, ctx->stream));
+    }
+    int th = T.begin(K_H2D);
+    HIPCHK(C.up(s_gb2, gb.data(), 8ull * (n_contigs + 1), ctx->stream)); HIPCHK(C.up(s_ic, in_contig.data(), 4ull * n_in, ctx->stream));
+    HIPCHK(C.up(s_ir, in_range.data(), 8ull * n_in, ctx->stream)); HIPCHK(C.up(s_rl, P.rid_lo.data(), 4ull * n_in, ctx->stream));
+    HIPCHK(C.up(s_rh, P.rid_hi.data(), 4ull * n_in, ctx->stream));
+    T.end(th);
+    fl::HsArgs a{};
+    a.contigs = C.at<const fl::ContigDev>(P.s_cd); a.assign = C.at<const int32_t>(P.s_as); a.assign_base = C.at<const uint64_t>(P.s_ab);
+    a.grp_base = C.at<const uint64_t>(s_gb2); a.in_contig = C.at<const uint32_t>(s_ic); a.in_range = C.at<const uint32_t>(s_ir);
+    a.rid_lo = C.at<const uint32_t>(s_rl); a.rid_hi = C.at<const uint32_t>(s_rh); a.new_off = C.at<uint64_t>(s_no); a.kept_off = C.at<uint64_t>(s_ko);
+    a.counts = C.at<uint64_t>(s_cnt); a.n_contigs = n_contigs; a.n_in = n_in; a.split = ctx->knobs.s2_assign_only ? 0 : 1;
+    const uint32_t grid_in = items_grid(ctx, n_in, 4);
+    int tk = T.begin(K_SEL);
+    hipLaunchKernelGGL(fl::hs_count_kernel, dim3(grid_in), dim3(256), 0, ctx->stream, a);
+    launch_offset_scan(ctx, a.new_off, C.at<uint64_t>(s_ti), n_in);
+    launch_offset_scan(ctx, a.kept_off, C.at<uint64_t>(s_ti), n_in);
+    hipLaunchKernelGGL(fl::hs_contig_counts_kernel, dim3(items_grid(ctx, n_contigs, 256)), dim3(256), 0, ctx->stream, a);
+    T.end(tk);
+    HIPCHK(hipGetLastError());
+    std::vector<uint64_t> counts(2ull * n_contigs);
+    int td = T.begin(K_D2H);
+    HIPCHK(hipMemcpyAsync(counts.data(), a.counts, 16ull * n_contigs, hipMemcpyDeviceToHost, ctx->stream));      // the call's one copy back: two words per contig
+    T.end(td);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    uint64_t NG = 0, NR = 0;
+    for (uint32_t ci = 0; ci < n_contigs; ++ci) { hs->c_groups[ci] = counts[2 * ci]; hs->c_reads[ci] = counts[2 * ci + 1]; NG += counts[2 * ci]; NR += counts[2 * ci + 1]; }
+    if (NG < n_in || NR > P.n_assign) return fail(FLORIA_E_DEVICE, "reassign_batch_resident: the device's group counts are inconsistent");
+    if (NG >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "reassign_batch_resident: 2^32 and more haplosets in one call");
+    hs->n_groups = NG; hs->n_reads = NR;
+    bool all_pos = true;
+    std::vector<fl::SpanContig> sc(n_contigs);
+    for (uint32_t i = 0; i < n_contigs; ++i) {
+        const floria_hip_contig* k = contigs[i];
+        if (!k->seq_pos) all_pos = false;
+        sc[i] = fl::SpanContig{k->dev.read_off, k->dev.cell_snp, k->seq_pos, k->n_reads, (uint32_t)k->n_cells};
+    }
+    Carve H;                                           // the handle's own buffer
+    const Seg h_cd = H.seg(sizeof(fl::ContigDev) * n_contigs), h_sc = H.seg(sizeof(fl::SpanContig) * n_contigs), h_gc = H.seg(4 * NG), h_go = H.seg(8 * (NG + 1)),
+              h_gr = H.seg(4 * NR + 4), h_rg = H.seg(8 * NG), h_lo = H.seg(4 * NG), h_len = H.seg(4 * NG);
+    rc = H.place(hs->buf); if (rc) return rc;
+    Carve S;                                           // the slot tables between the kernels
+    const uint32_t tiles_out = (uint32_t)((NG + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE);
+    const Seg s_sa = S.seg(4 * NG), s_sb = S.seg(4 * NG), s_sr = S.seg(8 * NG), s_sd = S.seg(4 * NG), s_to = S.seg(8ull * tiles_out + 8);
+    rc = S.place(ctx->hs_tmp); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(H.at(h_cd), C.at(P.s_cd), sizeof(fl::ContigDev) * n_contigs, hipMemcpyDeviceToDevice, ctx->stream));
+    if (all_pos) HIPCHK(H.up(h_sc, sc.data(), sizeof(fl::SpanContig) * n_contigs, ctx->stream));
+    hs->d_cd = H.at<const fl::ContigDev>(h_cd); hs->d_sc = all_pos ? H.at<const fl::SpanContig>(h_sc) : nullptr;
+    hs->d_gc = H.at<const uint32_t>(h_gc); hs->d_go = H.at<const uint64_t>(h_go); hs->d_gr = H.at<const uint32_t>(h_gr); hs->d_rg = H.at<const uint32_t>(h_rg);
+    hs->d_lo = H.at<uint32_t>(h_lo); hs->d_len = H.at<uint32_t>(h_len);
+    a.slot_a = S.at<uint32_t>(s_sa); a.slot_b = S.at<uint32_t>(s_sb); a.slot_range = S.at<uint32_t>(s_sr); a.slot_dst = S.at<uint32_t>(s_sd);
+    a.grp_contig = H.at<uint32_t>(h_gc); a.grp_off = H.at<uint64_t>(h_go); a.grp_read = H.at<uint32_t>(h_gr); a.range = H.at<uint32_t>(h_rg);
+    a.n_out = NG; a.n_reads_out = NR;
+    tk = T.begin(K_SEL);
+    hipLaunchKernelGGL(fl::hs_slots_kernel, dim3(grid_in), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(fl::hs_rank_kernel, dim3(items_grid(ctx, NG, 256)), dim3(256), 0, ctx->stream, a);
+    launch_offset_scan(ctx, a.grp_off, S.at<uint64_t>(s_to), (uint32_t)NG);
+    hipLaunchKernelGGL(fl::hs_fill_kernel, dim3(grid_in), dim3(256), 0, ctx->stream, a);
+    T.end(tk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    T.publish(ctx->timing);
+    *out = hs.release();
+    return 0;
+}
+
+void floria_hip_haplosets_free(floria_hip_haplosets* hs) {
+    if (!hs) return;
+    (void)hipSetDevice(hs->ctx->device);
+    delete hs;
+}
+
+int floria_hip_haplosets_download(const floria_hip_haplosets* hs, floria_groups*** out) {
+    if (!hs || !out) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = hs_headers(hs)) return rc;
+    const uint32_t n_contigs = (uint32_t)hs->contigs.size();
+    std::vector<uint32_t> reads(hs->n_reads + 1);
+    if (hs->n_reads) {
+        HIPCHK(hipSetDevice(hs->ctx->device));
+        HIPCHK(hipMemcpyAsync(reads.data(), hs->d_gr, 4 * hs->n_reads, hipMemcpyDeviceToHost, hs->ctx->stream));
+        HIPCHK(hipStreamSynchronize(hs->ctx->stream));
+    }
+    floria_groups** arr = (floria_groups**)calloc(std::max(1u, n_contigs), sizeof(floria_groups*));
+    if (!arr) return fail(FLORIA_E_NOMEM, "calloc");
+    uint64_t g0 = 0;
+    for (uint32_t ci = 0; ci < n_contigs; ++ci) {
+        const uint64_t ng = hs->c_groups[ci], r0 = hs->h_off[g0], tot = hs->h_off[g0 + ng] - r0;
+        floria_groups* G = (floria_groups*)calloc(1, sizeof(floria_groups));
+        if (G) { G->grp_off = (uint64_t*)calloc(ng + 1, 8); G->range = (uint32_t*)calloc(2 * ng + 2, 4); G->grp_read = (uint32_t*)malloc(4 * (tot + 1)); }
+        arr[ci] = G;
+        if (!G || !G->grp_off || !G->range || !G->grp_read) { floria_hip_groups_array_free(arr, n_contigs); return fail(FLORIA_E_NOMEM, "calloc"); }
+        G->n_groups = (uint32_t)ng;
+        for (uint64_t k = 0; k <= ng; ++k) G->grp_off[k] = hs->h_off[g0 + k] - r0;
+        std::copy(hs->h_range.begin() + 2 * g0, hs->h_range.begin() + 2 * (g0 + ng), G->range);
+        std::copy(reads.begin() + r0, reads.begin() + r0 + tot, G->grp_read);
+        g0 += ng;
+    }
+    *out = arr;
+    return 0;
+}
+
+int floria_hip_haploset_stats_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs, double* out4) {
+    if (int rc = hs_check(ctx, contigs, n_contigs, hs, "haploset_stats_resident")) return rc;
+    if (hs->n_groups && !out4) return fail(FLORIA_E_INVALID, "null argument");
+    if (hs->n_groups == 0) return 0;
+    if (int rc = hs_headers(hs)) return rc;
+    return stats_core(ctx, hs->A, hs->h_range.data(), (uint32_t)hs->n_groups, nullptr, hs_dev(hs, false), out4);
+}
+
+int floria_hip_haploset_alleles_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs,
+                                         const uint64_t* pos_off, uint32_t* counts) {
+    if (int rc = hs_check(ctx, contigs, n_contigs, hs, "haploset_alleles_resident")) return rc;
+    if (hs->n_groups && !pos_off) return fail(FLORIA_E_INVALID, "null argument");
+    if (hs->n_groups == 0) return 0;
+    if (int rc = hs_headers(hs)) return rc;
+    return alleles_core(ctx, hs->h_range.data(), (uint32_t)hs->n_groups, pos_off, nullptr, hs_dev(hs, false), counts);
+}
+
+int floria_hip_read_spans_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs,
+                                   uint32_t* left, uint32_t* right) {
+    if (int rc = hs_check(ctx, contigs, n_contigs, hs, "read_spans_resident")) return rc;
+    for (uint32_t i = 0; i < n_contigs; ++i) if (!contigs[i]->seq_pos) return fail(FLORIA_E_INVALID, "the contig carries no seq_pos");
+    if (hs->n_groups == 0 || hs->n_reads == 0) return 0;
+    if (!left || !right) return fail(FLORIA_E_INVALID, "null argument");
+    return spans_core(ctx, n_contigs, hs->n_reads, (uint32_t)hs->n_groups, nullptr, hs_dev(hs, true), left, right);
+}
+
+int floria_hip_hapq_batch_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* chs,
+                                   const uint64_t* const* snp_to_genome_pos, const uint32_t* n_snps, uint64_t block_length,
+                                   uint8_t* hapq, double* rel_err, double* avg_err) {
+    if (int rc = hs_check(ctx, contigs, n_contigs, chs, "hapq_batch_resident")) return rc;
+    if ((n_contigs && !avg_err) || (chs->n_groups && (!hapq || !rel_err))) return fail(FLORIA_E_INVALID, "null argument");
+    if (block_length == 0) return fail(FLORIA_E_INVALID, "block_length must be positive");
+    for (uint32_t c = 0; c < n_contigs; ++c) avg_err[c] = std::numeric_limits<double>::quiet_NaN();
+    if (chs->n_groups == 0) return 0;
+    floria_hip_haplosets* hs = const_cast<floria_hip_haplosets*>(chs);
+    const uint32_t n_groups = (uint32_t)hs->n_groups;
+    if (int rc = hs_headers(hs)) return rc;
+    std::vector<double> st(4ull * n_groups);
+    if (int rc = stats_core(ctx, hs->A, hs->h_range.data(), n_groups, nullptr, hs_dev(hs, false), st.data())) return rc;
+    if (!hs->have_span) {                              // min first / max last of every haploset's reads, once per handle: 8 B per group come back
+        hs->h_lo.assign(n_groups, 0); hs->h_len.assign(n_groups, 0);
+        hipLaunchKernelGGL(fl::hs_span_kernel, dim3(items_grid(ctx, n_groups, 4)), dim3(256), 0, ctx->stream, hs->d_cd, n_contigs, hs->d_gc, hs->d_go, hs->d_gr, n_groups, hs->d_lo, hs->d_len);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hs->h_lo.data(), hs->d_lo, 4ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(hs->h_len.data(), hs->d_len, 4ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        hs->have_span = true;
+    }
+    return hapq_core(ctx, contigs, n_contigs, hs->h_gc, hs->h_off.data(), hs->h_range.data(), n_groups, st, hs->h_lo, hs->h_len, snp_to_genome_pos, n_snps, block_length,
+                     nullptr, hs_dev(hs, false), hapq, rel_err, avg_err);
+}
 
 }  // extern "C"

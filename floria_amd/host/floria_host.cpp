@@ -347,6 +347,7 @@ Batch::Batch(Session& s, std::vector<ContigWork>& work, bool with_set_orders) : 
     for (size_t i = 0; i < work.size(); ++i) handles_[i] = work[i].handle.get();
 }
 Batch::~Batch() {
+    if (haplosets_) floria_hip_haplosets_free(haplosets_);
     for (size_t i = 0; i < handles_.size(); ++i) if (handles_[i] && owned_[i]) floria_hip_contig_free(handles_[i]);
     if (pinned_) floria_hip_host_free(pinned_);
 }
@@ -403,6 +404,12 @@ void Batch::process_reads_for_final_parts(const Options& o) {
     if (o.reassign_short) throw Error(FLORIA_E_UNSUPPORTED, "--reassign-short (hidden flag) is not supported");
     const GroupCsr g = groups_of(work_, false);
     floria_groups** out = nullptr;
+    if (o.haplosets_resident) {                                                // the result stays on the device for stats_and_hapq; the writers' read lists come back once
+        if (haplosets_) { floria_hip_haplosets_free(haplosets_); haplosets_ = nullptr; }
+        check(floria_hip_reassign_batch_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), g.gc.data(), g.off.data(), g.reads.data(), g.rng.data(),
+                                                 (uint32_t)g.gc.size(), nullptr, nullptr, o.epsilon, &haplosets_));
+        check(floria_hip_haplosets_download(haplosets_, &out));
+    } else
     check(floria_hip_reassign_batch(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), g.gc.data(), g.off.data(), g.reads.data(), g.rng.data(), (uint32_t)g.gc.size(),
                                     nullptr, nullptr, o.epsilon, &out));
     for (size_t i = 0; i < work_.size(); ++i) {
@@ -418,17 +425,25 @@ void Batch::process_reads_for_final_parts(const Options& o) {
 }
 
 void Batch::stats_and_hapq(const Options& o) {
-    const GroupCsr g = groups_of(work_, true);
-    const uint32_t ng = (uint32_t)g.gc.size();
+    const bool by_handle = haplosets_ != nullptr;                              // the final haplosets are the handle's, in its order: no list goes up again
+    const GroupCsr g = by_handle ? GroupCsr{} : groups_of(work_, true);
+    uint32_t ng = (uint32_t)g.gc.size();
+    if (by_handle) { ng = 0; for (const ContigWork& w : work_) ng += (uint32_t)w.final_parts.size(); haplosets_by_handle += ng; }
     std::vector<double> st(4 * (size_t)ng + 4, 0.0), rel(ng + 1, 0.0), avg(work_.size() + 1, 0.0);
     std::vector<uint8_t> hq(ng + 1, 0);
     std::vector<std::vector<uint64_t>> pos(work_.size());
     std::vector<const uint64_t*> pp(work_.size());
     std::vector<uint32_t> ns(work_.size());
     for (size_t i = 0; i < work_.size(); ++i) { pos[i].assign(work_[i].snp_to_genome_pos->begin(), work_[i].snp_to_genome_pos->end()); pp[i] = pos[i].data(); ns[i] = (uint32_t)pos[i].size(); }
+    if (by_handle) {
+        check(floria_hip_haploset_stats_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), haplosets_, st.data()));
+        check(floria_hip_hapq_batch_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), haplosets_, pp.data(), ns.data(), (uint64_t)o.block_length, hq.data(),
+                                             rel.data(), avg.data()));
+    } else {
     if (ng) check(floria_hip_haploset_stats(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), g.gc.data(), g.off.data(), g.reads.data(), g.rng.data(), ng, st.data()));
     check(floria_hip_hapq_batch(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), g.gc.data(), g.off.data(), g.reads.data(), g.rng.data(), ng, pp.data(), ns.data(),
                                 (uint64_t)o.block_length, hq.data(), rel.data(), avg.data()));
+    }
     size_t k = 0;
     for (size_t i = 0; i < work_.size(); ++i) {
         ContigWork& w = work_[i];
@@ -442,6 +457,7 @@ void Batch::stats_and_hapq(const Options& o) {
     std::vector<size_t> rix;
     for (size_t i = 0; i < work_.size(); ++i) if (work_[i].handle) { rix.push_back(i); rh.push_back(handles_[i]); }
     if (rh.empty()) return;
+    const bool rh_by_handle = by_handle && rh.size() == work_.size();          // the handle answers for ITS contigs: all of the batch (a batch that mixes routes uploads)
     GroupCsr r;
     std::vector<uint64_t> pos_off{0};
     for (size_t c = 0; c < rix.size(); ++c) {
@@ -460,11 +476,15 @@ void Batch::stats_and_hapq(const Options& o) {
     const uint32_t nr = (uint32_t)r.gc.size();
     if (!nr) return;
     std::vector<uint32_t> counts(4 * pos_off.back() + 4, 0);
+    if (rh_by_handle) check(floria_hip_haploset_alleles_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), haplosets_, pos_off.data(), counts.data()));
+    else
     check(floria_hip_haploset_alleles(s_.ctx(), rh.data(), (uint32_t)rh.size(), r.gc.data(), r.off.data(), r.reads.data(), r.rng.data(), nr, pos_off.data(), counts.data()));
     bytes_back += 16 * pos_off.back();
     std::vector<uint32_t> left, right;
     if (o.output_reads) {                                                      // write_reads' two lookups per (haploset, read)
         left.assign(r.reads.size() + 1, FLORIA_SPAN_NONE); right.assign(r.reads.size() + 1, FLORIA_SPAN_NONE);
+        if (rh_by_handle) check(floria_hip_read_spans_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), haplosets_, left.data(), right.data()));
+        else
         check(floria_hip_read_spans(s_.ctx(), rh.data(), (uint32_t)rh.size(), r.gc.data(), r.off.data(), r.reads.data(), r.rng.data(), nr, left.data(), right.data()));
         bytes_back += 8 * r.reads.size();
     }

@@ -69,6 +69,7 @@ struct Options {
     floria_realign_walk walk = {8, 8, 0, 0};
     bool pileup_device = false;         // --pileup host | device: frag_from_record's CIGAR walk on the host (default) or by floria_hip_pileup_records, one call per ingest round
     bool pileup_fused = false;          // --pileup fused: pileup_device, and the calls are realigned by the same device call (floria_hip_pileup_records_realign) instead of by realign()
+    bool haplosets_resident = false;    // --haplosets resident: S2 by floria_hip_reassign_batch_resident, one download, and the handle to the four consumers (Batch)
     bool pileup_resident = false;       // --pileup resident: the walk (and the realignment) by floria_hip_pileup_records_resident, the fragments assembled on the device from a plan made of
                                         // headers (floria_hip_assemble_contigs_opt): the host holds header-only Frags and a handle per contig, no cell comes back
 };
@@ -493,6 +494,7 @@ public:
     // field 7 where the contig carries a set order; valid once generate_hap_graphs has run (every contig then has a handle, whichever route made it)
     std::string dump_handles() const;
     uint64_t bytes_back = 0;                                           // bytes of the allele tables and trim lookups received
+    uint64_t haplosets_by_handle = 0;                                  // --haplosets resident: final haplosets whose statistics were computed from the handle
 private:
     Session& s_;
     std::vector<ContigWork>& work_;
@@ -500,6 +502,7 @@ private:
     std::vector<size_t> host_ix_;                                      // the contigs without a handle of their own: marshalled here, piles_[j] is contig host_ix_[j]
     std::vector<floria_pileup_packed> piles_;
     std::vector<floria_hip_contig*> handles_;                          // per contig: the ContigWork's own handle, or the one uploaded here (owned_)
+    floria_hip_haplosets* haplosets_ = nullptr;                        // --haplosets resident: S2's result on the device, from process_reads_for_final_parts to the destructor
     std::vector<char> owned_;
 };
 // utils_frags::remove_monomorphic_allele (utils_frags.rs:713-772, --ignore-monomorphic): SNPs where one allele carries (almost) all of the

@@ -24,6 +24,10 @@
 // the round's plans into resident contigs, --ignore-monomorphic is one floria_hip_drop_monomorphic call on them; the batch phases on the handles, the writers take their
 // allele tables from floria_hip_haploset_alleles and --output-reads' trims from floria_hip_read_spans.  A contig the device cannot number (see --pileup device) keeps the host
 // walk and is uploaded beside the others.  One device only, no --dump-frags (the qualities are folded into weights on the device).  Same files.
+// --haplosets host | resident: where the haplosets live between S2 and the writers, on any --pileup route.  host [default]: floria_hip_reassign_batch returns the group
+// lists and COV / ERR, HAPQ, the allele tables and the read trims take them up again.  resident: floria_hip_reassign_batch_resident splits and sorts on the device and
+// keeps the haplosets there as a handle; the lists come back once (floria_hip_haplosets_download) for the writers and the four calls take the handle (the allele tables and
+// trims of a batch that mixes contigs with and without a handle of their own still go by lists).  Same files.
 // For tests: --dump-plan FILE (with --ingest-only, any route: the fragment plan per contig), --dump-handles FILE (any route: the resident arrays of every contig of every batch).
 // --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
 // RULE max | sum, TIE right | down): one member of the family of fixed-block walks (block 8) that scripts/probes/block_walk.c defines.  The reference's block-aligner is
@@ -75,6 +79,9 @@ void usage() {
           "                    round; fused: that device call also re-aligns the calls (instead of the host loop that queues windows for the device); resident: the calls\n"
           "                    never come back - fragments are planned from the records' headers and assembled, filtered (--ignore-monomorphic) and phased on the device,\n"
           "                    the writers ask it for allele tables and read trims (one device only; no --dump-frags).  Same files\n"
+          "  --haplosets host|resident   where the haplosets live between S2 and the writers: host [default] = S2 returns the group lists and the four calls behind it\n"
+          "                    (COV / ERR, HAPQ, allele tables, read trims) take them up again; resident = S2 splits and sorts on the device and keeps the haplosets there\n"
+          "                    (floria_hip_reassign_batch_resident), the lists come back once for the writers and the four calls take the handle.  Any --pileup route.  Same files\n"
           "  --realign exact | block:STEP,RULE,TIE   how that re-alignment scores a window: exact [default] = the exact affine-gap alignment; block:... = a walk of a fixed\n"
           "                 8 x 8 block over the alignment matrix, shifted by STEP = 1 | 2 | 4 | 8 cells towards the larger border by RULE = max | sum, ties going\n"
           "                 TIE = right | down (e.g. block:8,max,right).  floria's block-aligner is a heuristic of this kind; which member is unknown, so one must be named\n"
@@ -229,6 +236,11 @@ int main(int argc, char** argv) {
                     throw Error(FLORIA_E_INVALID, "--pileup takes host or device (or fused: device, and the calls re-aligned there; or resident: the calls stay on the device), not '" + v + "'");
                 o.pileup_device = v == "device" || v == "fused"; o.pileup_fused = v == "fused"; o.pileup_resident = v == "resident";
             }
+            else if (a == "--haplosets") {
+                const std::string v = val();
+                if (v != "host" && v != "resident") throw Error(FLORIA_E_INVALID, "--haplosets takes host or resident, not '" + v + "'");
+                o.haplosets_resident = v == "resident";
+            }
             else if (a == "--dump-plan") dump_plan = val();            // (tests, with --ingest-only) the fragment plan of every contig: needs no GPU under --pileup host
             else if (a == "--dump-handles") dump_handles = val();      // (tests) the resident arrays of every contig of every batch, whichever route made the handle
             else if (a == "--ingest-only") ingest_only = true;          // (tests) stop after ingest: needs no GPU
@@ -377,6 +389,7 @@ int main(int argc, char** argv) {
         const bool resident_keep_seq_pos = o.pileup_resident && (o.output_reads || !dump_seq_pos.empty());
         size_t n_resident_merged = 0, n_resident_contigs = 0;
         double t_resident_assemble = 0., t_resident_filter = 0., t_resident_assemble_ev = 0., t_resident_filter_ev = 0.;
+        std::atomic<uint64_t> n_haplosets_by_handle{0};                          // --haplosets resident
         uint64_t resident_bytes_back = 0, resident_removed_snps = 0, resident_dropped_reads = 0;
         // ---- which contigs (floria.rs:229-262) -------------------------------------------------------------------------------------
         bool warn_first_length = true;
@@ -607,6 +620,7 @@ int main(int argc, char** argv) {
                 tm[2] += now_s() - t1; t1 = now_s();
                 batch.stats_and_hapq(o);
                 tm[3] += now_s() - t1;
+                n_haplosets_by_handle += batch.haplosets_by_handle;
                 if (batch.bytes_back) resident_bytes_back += batch.bytes_back;    // (resident contigs exist with one device only: no other thread is here then)
             };
             double tm[4] = {0., 0., 0., 0.};
@@ -665,6 +679,9 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "Arithmetic: the set orders of %zu fragments merged from several alignments were derived on the device (floria_hip_assemble_contigs_opt), every resident contig "
                                 "phased in the reference's running sums\n", n_resident_merged);
         }
+        if (o.haplosets_resident)
+            fprintf(stderr, "Haplosets: %llu split, sorted and kept on the device behind S2 (floria_hip_reassign_batch_resident); one download for the writers, COV / ERR, HAPQ, "
+                            "allele tables and read trims by handle\n", (unsigned long long)n_haplosets_by_handle.load());
         fprintf(stderr, "Batches %zu; ingest %.3fs, phasing (upload + S1 + graph) %.3fs, LP + paths %.3fs, S2 %.3fs, COV/ERR/HAPQ %.3fs, writers %.3fs\n", n_batches, t_ingest, t_s1,
                 t_stitch, t_s2, t_stats, t_write);
         if (reference_arith && n_batches_orders)

@@ -32,6 +32,8 @@ SYMBOLS = [
     "floria_hip_pileup_records_resident", "floria_hip_record_summary_free", "floria_hip_assemble_contigs", "floria_hip_assemble_contigs_ordered", "floria_hip_haploset_alleles",
     "floria_hip_assemble_contigs_opt", "floria_hip_read_spans",
     "floria_hip_drop_monomorphic", "floria_hip_mono_result_free", "floria_hip_mono_timing",
+    "floria_hip_reassign_batch_resident", "floria_hip_haplosets_free", "floria_hip_haplosets_download", "floria_hip_haploset_stats_resident", "floria_hip_hapq_batch_resident",
+    "floria_hip_haploset_alleles_resident", "floria_hip_read_spans_resident",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -94,6 +96,15 @@ def load():
         L.floria_hip_mono_result_free.argtypes = [C.POINTER(capi.CMonoResult)]
         L.floria_hip_mono_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.floria_hip_haploset_alleles.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u32p, C.c_uint32, capi.u64p, capi.u32p]
+        L.floria_hip_reassign_batch_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u32p, C.c_uint32, capi.u32p, capi.u64p, C.c_double,
+                                                         C.POINTER(C.c_void_p)]
+        L.floria_hip_haplosets_free.restype = None
+        L.floria_hip_haplosets_free.argtypes = [C.c_void_p]
+        L.floria_hip_haplosets_download.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.POINTER(capi.CGroups)))]
+        L.floria_hip_haploset_stats_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, capi.f64p]
+        L.floria_hip_hapq_batch_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, capi.u32p, C.c_uint64, capi.u8p, capi.f64p, capi.f64p]
+        L.floria_hip_haploset_alleles_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, capi.u64p, capi.u32p]
+        L.floria_hip_read_spans_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, capi.u32p, capi.u32p]
         _LIB = L
     return _LIB
 
@@ -299,6 +310,50 @@ class RecordSummary:
             pass
 
 
+class Haplosets:
+    """floria_hip_haplosets: the result of one FloriaHip.reassign_batch_resident call, resident on the device.  download() -> what reassign_batch returns (a list of
+    _capi.Groups in contig order, fetched once and kept); the four consumers take the handle as haplosets= (with the contigs of the S2 call) and upload no group."""
+
+    def __init__(self, ctx, handle, n_contigs):
+        self.ctx, self._h, self.n_contigs, self._groups = ctx, handle, n_contigs, None
+
+    def download(self):
+        if self._groups is None:
+            out = C.POINTER(C.POINTER(capi.CGroups))()
+            _check(load().floria_hip_haplosets_download(self._h, C.byref(out)))
+            self._groups = [capi.Groups(out[i].contents) for i in range(self.n_contigs)]
+            load().floria_hip_groups_array_free(out, C.c_uint32(self.n_contigs))
+        return self._groups
+
+    @property
+    def n_groups(self):
+        return sum(g.n_groups for g in self.download())
+
+    @property
+    def n_entries(self):
+        return sum(len(g.grp_read) for g in self.download())
+
+    def ranges(self):
+        """uint32 [n_groups, 2]: the ranges of all contigs' groups in the handle's order."""
+        return np.concatenate([g.range.reshape(-1, 2) for g in self.download()] + [np.zeros((0, 2), np.uint32)])
+
+    def free(self):
+        if self._h is not None:
+            load().floria_hip_haplosets_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _contig_array(contigs):
+    n = len(contigs)
+    return contigs._arr if isinstance(contigs, ContigBatch) else (C.c_void_p * max(n, 1))(*[c._h for c in contigs])
+
+
 def c_pileups(pileups):
     """ctypes array of floria_pileup for a list of Pileups (keep the Pileups alive while it is in use)."""
     return (capi.CPileup * len(pileups))(*[p.as_c() for p in pileups])
@@ -430,8 +485,13 @@ class FloriaHip:
         load().floria_hip_hap_graph_free(out)
         return g
 
-    def haploset_stats(self, contigs, grp_contig, groups, ranges):
-        """get_errors_cov_from_frags (utils_frags.rs:596-655) per haploset -> float64 [n_groups, 4] = cov, err, total_err, total_cov."""
+    def haploset_stats(self, contigs, grp_contig=None, groups=None, ranges=None, haplosets=None):
+        """get_errors_cov_from_frags (utils_frags.rs:596-655) per haploset -> float64 [n_groups, 4] = cov, err, total_err, total_cov.
+        haplosets= a Haplosets handle made from `contigs`: its groups, nothing uploaded."""
+        if haplosets is not None:
+            out = np.zeros((haplosets.n_groups, 4), np.float64)
+            _check(load().floria_hip_haploset_stats_resident(self._h, _contig_array(contigs), C.c_uint32(len(contigs)), haplosets._h, capi.ptr(out, C.c_double)))
+            return out
         arr = (C.c_void_p * len(contigs))(*[c._h for c in contigs])
         gc = np.ascontiguousarray(grp_contig, np.uint32)
         off = np.zeros(len(groups) + 1, np.uint64)
@@ -561,9 +621,17 @@ class FloriaHip:
         _check(load().floria_hip_mono_timing(self._h, ms))
         return dict(zip(("clear_ms", "count_ms", "decide_ms", "filter_count_ms", "filter_fill_ms", "order_ms"), [float(x) for x in ms]))
 
-    def haploset_alleles(self, contigs, grp_contig, groups, ranges):
+    def haploset_alleles(self, contigs, grp_contig=None, groups=None, ranges=None, haplosets=None):
         """floria_hip_haploset_alleles: per haploset (read-id list + inclusive SNP range, as haploset_stats takes them) the number of its reads calling each allele
         at every SNP of its range -> (pos_off uint64 [n_groups + 1], counts uint32 [pos_off[-1], 4]): row pos_off[g] + (p - lo_g) is SNP p of group g."""
+        if haplosets is not None:                    # the handle's groups; pos_off from the ranges of its download
+            rg = haplosets.ranges().astype(np.int64)
+            pos_off = np.zeros(len(rg) + 1, np.uint64)
+            pos_off[1:] = np.cumsum(np.maximum(0, rg[:, 1] - rg[:, 0] + 1))
+            counts = np.zeros((int(pos_off[-1]), 4), np.uint32)
+            _check(load().floria_hip_haploset_alleles_resident(self._h, _contig_array(contigs), C.c_uint32(len(contigs)), haplosets._h, capi.ptr(pos_off, C.c_uint64),
+                                                               capi.ptr(counts, C.c_uint32)))
+            return pos_off, counts
         arr = (C.c_void_p * len(contigs))(*[c._h for c in contigs])
         gc = np.ascontiguousarray(grp_contig, np.uint32)
         off = np.zeros(len(groups) + 1, np.uint64)
@@ -578,12 +646,17 @@ class FloriaHip:
                                                   capi.ptr(rng, C.c_uint32), C.c_uint32(len(groups)), capi.ptr(pos_off, C.c_uint64), capi.ptr(counts, C.c_uint32)))
         return pos_off, counts
 
-    def read_spans(self, contigs, grp_contig, groups, ranges):
+    def read_spans(self, contigs, grp_contig=None, groups=None, ranges=None, haplosets=None):
         """floria_hip_read_spans: per haploset (read-id list + inclusive SNP range, as haploset_alleles takes them; or groups = (grp_off, grp_read) arrays) and read the SEQ_POS word of the read's first
         cell with snp >= lo and of its last cell with snp <= hi -> (left uint32 [sum of the group sizes], right uint32 [same]); capi.FLORIA_SPAN_NONE where the
         read has no such cell.  Every contig must carry positions (assemble_contigs(keep_seq_pos=True), or drop_monomorphic of such contigs)."""
         n = len(contigs)
         arr = contigs._arr if isinstance(contigs, ContigBatch) else (C.c_void_p * max(n, 1))(*[c._h for c in contigs])
+        if haplosets is not None:
+            ne = haplosets.n_entries
+            left = np.zeros(ne, np.uint32); right = np.zeros(ne, np.uint32)
+            _check(load().floria_hip_read_spans_resident(self._h, arr, C.c_uint32(n), haplosets._h, capi.ptr(left, C.c_uint32), capi.ptr(right, C.c_uint32)))
+            return left, right
         gc = np.ascontiguousarray(grp_contig, np.uint32)
         if isinstance(groups, tuple) and len(groups) == 2 and isinstance(groups[0], np.ndarray):      # (grp_off uint64 [n_groups + 1], grp_read uint32) as the C entry takes them
             off, reads = np.ascontiguousarray(groups[0], np.uint64), np.ascontiguousarray(groups[1], np.uint32)
@@ -650,8 +723,18 @@ class FloriaHip:
         del keep
         return res if refs is None else (res, counts)
 
-    def hapq_batch(self, contigs, grp_contig, groups, ranges, snp_positions, block_length):
-        """get_hapq for the haplosets of many contigs in one call -> (hapq uint8 [n], rel_err float64 [n], avg_err float64 [n_contigs])."""
+    def hapq_batch(self, contigs, grp_contig=None, groups=None, ranges=None, snp_positions=None, block_length=None, haplosets=None):
+        """get_hapq for the haplosets of many contigs in one call -> (hapq uint8 [n], rel_err float64 [n], avg_err float64 [n_contigs]).
+        haplosets= a Haplosets handle made from `contigs`: its groups, nothing uploaded."""
+        if haplosets is not None:
+            pos = [np.ascontiguousarray(p, np.uint64) for p in snp_positions]
+            pp = (C.POINTER(C.c_uint64) * max(1, len(pos)))(*[capi.ptr(p, C.c_uint64) for p in pos])
+            ns = np.ascontiguousarray([len(p) for p in pos], np.uint32)
+            ng = haplosets.n_groups
+            hq = np.zeros(ng, np.uint8); rel = np.zeros(ng, np.float64); avg = np.zeros(len(contigs), np.float64)
+            _check(load().floria_hip_hapq_batch_resident(self._h, _contig_array(contigs), C.c_uint32(len(contigs)), haplosets._h, pp, capi.ptr(ns, C.c_uint32),
+                                                         C.c_uint64(int(block_length)), capi.ptr(hq, C.c_uint8), capi.ptr(rel, C.c_double), capi.ptr(avg, C.c_double)))
+            return hq, rel, avg
         arr = (C.c_void_p * len(contigs))(*[c._h for c in contigs])
         gc = np.ascontiguousarray(grp_contig, np.uint32)
         off = np.zeros(len(groups) + 1, np.uint64)
@@ -670,9 +753,13 @@ class FloriaHip:
         return hq, rel, avg
 
     # S2 --------------------------------------------------------------------------------------------
-    def reassign_batch(self, contigs, grp_contig, groups, ranges, epsilon, read_orders=None):
+    def reassign_batch_resident(self, contigs, grp_contig, groups, ranges, epsilon, read_orders=None):
+        """reassign_batch whose result stays on the device -> Haplosets (download() gives reassign_batch's list)."""
+        return self.reassign_batch(contigs, grp_contig, groups, ranges, epsilon, read_orders, _resident=True)
+
+    def reassign_batch(self, contigs, grp_contig, groups, ranges, epsilon, read_orders=None, _resident=False):
         """process_reads_for_final_parts for many resident contigs in one launch -> list of _capi.Groups (contig order)."""
-        arr = (C.c_void_p * len(contigs))(*[c._h for c in contigs])
+        arr = _contig_array(contigs)
         gc = np.ascontiguousarray(grp_contig, np.uint32)
         off = np.zeros(len(groups) + 1, np.uint64)
         off[1:] = np.cumsum([len(g) for g in groups])
@@ -686,6 +773,12 @@ class FloriaHip:
             oo[1:] = np.cumsum([len(o) for o in read_orders])
             ordv = np.ascontiguousarray(np.concatenate([np.asarray(o, np.uint32) for o in read_orders]) if len(read_orders) else np.zeros(0, np.uint32), np.uint32)
             po, poo = capi.ptr(ordv, C.c_uint32), capi.ptr(oo, C.c_uint64)
+        if _resident:
+            h = C.c_void_p()
+            _check(load().floria_hip_reassign_batch_resident(self._h, arr, C.c_uint32(len(contigs)), capi.ptr(gc, C.c_uint32), capi.ptr(off, C.c_uint64),
+                                                             capi.ptr(reads, C.c_uint32), capi.ptr(rng, C.c_uint32), C.c_uint32(len(groups)), po, poo,
+                                                             C.c_double(epsilon), C.byref(h)))
+            return Haplosets(self, h, len(contigs))
         _check(load().floria_hip_reassign_batch(self._h, arr, C.c_uint32(len(contigs)), capi.ptr(gc, C.c_uint32), capi.ptr(off, C.c_uint64),
                                                 capi.ptr(reads, C.c_uint32), capi.ptr(rng, C.c_uint32), C.c_uint32(len(groups)), po, poo,
                                                 C.c_double(epsilon), C.byref(out)))

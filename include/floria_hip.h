@@ -572,6 +572,45 @@ int  floria_hip_read_spans(floria_hip_ctx* ctx, const floria_hip_contig* const* 
                            const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
                            const uint32_t* grp_range, uint32_t n_groups, uint32_t* left /* [grp_off[n_groups]] */, uint32_t* right /* same */);
 
+/* ---- S2 whose result stays on the device: haplosets as a handle ------------------------------------------------------------------------------------------------------
+ * floria_hip_reassign_batch_resident is floria_hip_reassign_batch — the same arguments, the same validation and refusals with the same messages, the same host
+ * prologue, the same re-insertion kernels with the same path choice in both arithmetics — but what follows the kernel (the groups from the per-read assignment,
+ * separate_broken_haplogroups, sort_parts) runs on the device (csrc/haploset_kernel.h) and the result is a floria_hip_haplosets handle: for the n_contigs contigs
+ * of the call, back to back in contig order, the group tables the consumer kernels read (grp_contig, grp_off, grp_read, range).  Group order and contents are those
+ * floria_hip_reassign_batch returns, under "s2_assign_only" = 1 too; nothing depends on the order in which anything lands on the device.  One copy comes back during
+ * the call: two words per contig (its groups, its reads).
+ * RESIDENCY.  The handle lives in a buffer of its own and remembers the context and the contig handles it was made from (they must outlive it).  Creating, using
+ * or freeing it ends no other residency beyond what the call it replaces ends (the S2 call itself works in the buffer of the last phase_blocks* batch, as
+ * floria_hip_reassign_batch does), and no later call overwrites it: it answers the same after any number of S1 / S2 calls.
+ * floria_hip_haplosets_download returns exactly what floria_hip_reassign_batch returns for the same inputs (floria_hip_groups_array_free); nothing goes back up.
+ * The consumers by handle take (ctx, contigs, n_contigs, hs, ...) and otherwise the arguments of their siblings, run the siblings' kernels on the handle's arrays
+ * — no group list is uploaded, no host loop touches a read — and return, bit for bit, what the sibling returns for the downloaded groups concatenated in contig
+ * order (grp_contig[g] = the contig, grp_off rebased).  Their host parts read a header-sized mirror of the handle (grp_off and range, 16 B per group, fetched once
+ * per handle; floria_hip_hapq_batch_resident also the SNP span of every group's reads, 8 B per group, computed by one launch).  pos_off of the alleles call is the
+ * caller's, from the ranges of the download.
+ * Buffers: floria_hip_haploset_stats_resident, floria_hip_haploset_alleles_resident and floria_hip_hapq_batch_resident work in the buffer their siblings use and
+ * end the residency of the last phase_blocks* batch (floria_hip_hap_graph) as they do; floria_hip_read_spans_resident, floria_hip_haplosets_download and
+ * floria_hip_haplosets_free end none.
+ * Refused before any launch, FLORIA_E_INVALID each: a null argument; a handle of another context; a `contigs` array that is not the handle's (its count or any
+ * pointer); for the spans call a contig without positions ("the contig carries no seq_pos").  floria_hip_last_timing after the S2 call: reassign_ms = the
+ * re-insertion kernels, select_ms = the epilogue's kernels, h2d_ms, d2h_ms, total_ms. */
+typedef struct floria_hip_haplosets floria_hip_haplosets;
+int  floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                                        const uint32_t* grp_contig, const uint64_t* grp_off, const uint32_t* grp_read,
+                                        const uint32_t* grp_range, uint32_t n_groups,
+                                        const uint32_t* read_order, const uint64_t* order_off,
+                                        double epsilon, floria_hip_haplosets** out);
+void floria_hip_haplosets_free(floria_hip_haplosets* hs);
+int  floria_hip_haplosets_download(const floria_hip_haplosets* hs, floria_groups*** out /* [n_contigs of the S2 call] */);
+int  floria_hip_haploset_stats_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs, double* out4);
+int  floria_hip_hapq_batch_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs,
+                                    const uint64_t* const* snp_to_genome_pos, const uint32_t* n_snps, uint64_t block_length,
+                                    uint8_t* hapq, double* rel_err, double* avg_err);
+int  floria_hip_haploset_alleles_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs,
+                                          const uint64_t* pos_off, uint32_t* counts);
+int  floria_hip_read_spans_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs,
+                                    uint32_t* left, uint32_t* right);
+
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
 /* Self-test of a hardware assumption: the beam kernel screens the pruning test (global_clustering.rs:98) with an f32 evaluation of stable_binom_cdf_p_rev
@@ -614,7 +653,7 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
  * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
- * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic — uses at most N workgroups, and the one-thread order kernel at most N threads,
+ * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic, the epilogue of floria_hip_reassign_batch_resident — uses at most N workgroups, and the one-thread order kernel at most N threads,
  * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "hw_queues" (tests: override the number of
  * concurrently running streams floria_hip_create measured — 6 on an MI355X whose host set GPU_MAX_HW_QUEUES=12 before HIP initialised, 4 or fewer
  * with the runtime's default; below 5 the launch plans stay within two job groups and do not speculate). */
