@@ -19,6 +19,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -39,6 +40,23 @@ struct Error : std::runtime_error {
     int code;
     Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
+
+// --pileup host | device | fused | resident: where the CIGAR walk that turns alignment records into SNP calls runs
+//   Host      frag_from_record on the host threads (default)
+//   Device    floria_hip_pileup_records, one call per ingest round (RecordPileup)
+//   Fused     Device, and the calls are realigned by the same device call (floria_hip_pileup_records_realign) instead of by realign()
+//   Resident  the walk (and the realignment) by floria_hip_pileup_records_resident, the fragments assembled on the device from a plan made of headers
+//             (floria_hip_assemble_contigs_opt): the host holds header-only Frags and a handle per contig, no cell comes back (ResidentPileup)
+enum class PileupRoute { Host, Device, Fused, Resident };
+inline const char* route_name(PileupRoute r) { return r == PileupRoute::Host ? "host" : r == PileupRoute::Device ? "device" : r == PileupRoute::Fused ? "fused" : "resident"; }
+// the round's CIGAR walks are one device call
+inline bool walk_on_device(PileupRoute r) { return r != PileupRoute::Host; }
+// --ingest-only needs no device, unless the walk runs there
+inline bool needs_session(PileupRoute r, bool ingest_only) { return !ingest_only || walk_on_device(r); }
+// the calls are realigned by the device call that walked them (the host loop that queues windows then sees only the contigs that kept the host walk)
+inline bool realigned_behind_walk(PileupRoute r, bool no_realign) { return !no_realign && (r == PileupRoute::Fused || r == PileupRoute::Resident); }
+// --pileup fused --no-realign is --pileup device
+inline PileupRoute effective_route(PileupRoute r, bool no_realign) { return r == PileupRoute::Fused && no_realign ? PileupRoute::Device : r; }
 
 // The hot-path fields of `Options` (types_structs.rs:20-51) with the CLI defaults (parse_cmd_line.rs)
 struct Options {
@@ -67,11 +85,8 @@ struct Options {
     // fixed-block walk family (floria_hip_realign_walk on the device, walk_affine_score on the host)
     bool realign_walk = false;
     floria_realign_walk walk = {8, 8, 0, 0};
-    bool pileup_device = false;         // --pileup host | device: frag_from_record's CIGAR walk on the host (default) or by floria_hip_pileup_records, one call per ingest round
-    bool pileup_fused = false;          // --pileup fused: pileup_device, and the calls are realigned by the same device call (floria_hip_pileup_records_realign) instead of by realign()
+    PileupRoute pileup = PileupRoute::Host;   // --pileup
     bool haplosets_resident = false;    // --haplosets resident: S2 by floria_hip_reassign_batch_resident, one download, and the handle to the four consumers (Batch)
-    bool pileup_resident = false;       // --pileup resident: the walk (and the realignment) by floria_hip_pileup_records_resident, the fragments assembled on the device from a plan made of
-                                        // headers (floria_hip_assemble_contigs_opt): the host holds header-only Frags and a handle per contig, no cell comes back
 };
 // "exact" | "block:STEP,RULE,TIE" (STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down) -> options.realign_walk / options.walk; anything else throws with the grammar
 void parse_realign_spec(const std::string& spec, Options& options);
@@ -306,11 +321,29 @@ struct RealignQueue {
     size_t size() const { return dst.size(); }
     void append(RealignQueue&& other);
 };
-// --pileup device: the CIGAR walks of one ingest round in ONE floria_hip_pileup_records call.  Every record of the given contigs that passes alignment_passed_check is
-// sent as offsets into the segment's inflated buffer (the stretch of bam.raw that holds those records travels as it is); a ContigIngest given the result fills its Frags
-// from the records' cells instead of walking their CIGARs.  A contig whose SNP counters are not rank + 1 in position order (a VCF that repeats a position) or that has a
-// site with more than FLORIA_MAX_ALLELES alleles is not sent: its records keep the host walk (host_contigs names them).
-class RecordPileup {
+// The CIGAR walks of one ingest round in ONE device call, whichever route makes it (--pileup device / fused: RecordPileup, resident: ResidentPileup).  Every record of
+// the given contigs that passes alignment_passed_check is sent as offsets into the segment's inflated buffer (the stretch of bam.raw that holds those records travels
+// as it is).  A contig whose SNP counters are not rank + 1 in position order (a VCF that repeats a position) or that has a site with more than FLORIA_MAX_ALLELES
+// alleles is not sent: its records keep the host walk (host_contigs names them).
+struct RecordSelection;                                      // what floria_hip_pileup_records* takes (ingest.cpp)
+class RoundWalk {
+public:
+    size_t records_sent = 0, blob_bytes = 0;
+    double kernel_ms = 0., h2d_ms = 0., d2h_ms = 0.;         // floria_hip_last_timing of the call
+    std::vector<std::string> host_contigs;
+    floria_realign_counts counts = {};                       // of a realigning call
+protected:
+    RoundWalk() = default;
+    // selects the round's records (ref_seqs: with the contigs' reference sequences) and, where there are any, makes the route's one device call (`call` throws when
+    // it fails) and keeps its event times and the records' places in it.  Called by the route's constructor.
+    void walk(Session& s, const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string* contigs, size_t n_contigs,
+              const std::map<std::string, std::string>* ref_seqs, const std::function<void(const RecordSelection&)>& call);
+    std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
+    std::vector<int32_t> table_of_;                          // contig of the list -> contig of the call's SNP table, -1
+    std::vector<uint64_t> snp_count_;                        // per table contig
+};
+// --pileup device: floria_hip_pileup_records.  A ContigIngest given the result fills its Frags from the records' cells instead of walking their CIGARs.
+class RecordPileup : public RoundWalk {
 public:
     // ref_seqs (--pileup fused): the reference sequences by contig name; the call is then floria_hip_pileup_records_realign with options.realign_walk / walk, the cells come
     // back realigned (a contig that is not in the map travels with an empty sequence: its cells stay as walked) and `realigned` tells ContigIngest to leave them alone
@@ -321,14 +354,9 @@ public:
     RecordPileup& operator=(const RecordPileup&) = delete;
     struct Cells { const uint32_t* snp; const uint8_t* allele; const uint8_t* qual; const uint32_t* seq_pos; size_t n; int64_t ref_end; };
     bool cells(uint32_t record_index, Cells& out) const;     // false: the record was not sent
-    size_t records_sent = 0, blob_bytes = 0;
-    double kernel_ms = 0., h2d_ms = 0., d2h_ms = 0.;         // floria_hip_last_timing of the call
-    std::vector<std::string> host_contigs;
     bool realigned = false;
-    floria_realign_counts counts = {};                       // of the realigning call
 private:
     floria_record_cells* cells_ = nullptr;
-    std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
 };
 struct ContigPlan;
 class ContigIngest {
@@ -340,8 +368,9 @@ public:
     ~ContigIngest();
     ContigIngest(ContigIngest&&) noexcept;
     ContigIngest& operator=(ContigIngest&&) noexcept;
-    std::pair<std::vector<Frag>, std::vector<Frag>> finish();              // combine_frags (:491-659) -> (frags with SNPs, frags without)
-    ContigPlan plan() const;                                      // the fragment plan of the records held (before finish()): --dump-plan under the routes that walk into Frags
+    // combine_frags (:491-659) -> (frags with SNPs in Frag::cmp order, frags without): plan() decides who is merged onto whom, the Frags are merged in its order
+    std::pair<std::vector<Frag>, std::vector<Frag>> finish();
+    ContigPlan plan() const;                                      // the fragment plan of the records held (before finish()): also --dump-plan under the routes that walk into Frags
 private:
     struct Impl;
     std::unique_ptr<Impl> p_;
@@ -401,7 +430,7 @@ struct HeaderContig {
 // The walks of one ingest round in ONE floria_hip_pileup_records_resident call (RecordPileup's record selection and host_contigs rule; with ref_seqs the calls are
 // realigned there, options.realign_walk / walk honoured), then per contig a plan from the summary, one floria_hip_assemble_contigs_opt call for the round and, with
 // --ignore-monomorphic, one floria_hip_drop_monomorphic call.  assemble() must run before the context's next floria_hip_pileup_records* call (include/floria_hip.h, RESIDENCY).
-class ResidentPileup {
+class ResidentPileup : public RoundWalk {
 public:
     ResidentPileup(Session& s, const BamFile& bam, const VcfProfile& vcf_profile, const Options& options, const std::string* contigs, size_t n_contigs,
                    const std::map<std::string, std::string>* ref_seqs = nullptr);
@@ -412,14 +441,10 @@ public:
     HeaderContig plan(size_t contig_index) const;                                          // thread-safe: reads the summary
     // planned[i] (may be null where !on_table(i)) for every contig of the constructor's list; fills planned[i]->handle and re-maps the Frags through the filter
     void assemble(std::vector<HeaderContig*>& planned, bool derive_set_order, bool keep_seq_pos, bool ignore_monomorphic, double epsilon);
-    size_t records_sent = 0, blob_bytes = 0;
-    double kernel_ms = 0., h2d_ms = 0., d2h_ms = 0.;         // floria_hip_last_timing of the pileup call
     double assemble_s = 0., filter_s = 0.;                   // wall seconds of the assemble and the filter call
     double assemble_ms = 0., filter_ms = 0.;                 // their device-event totals
     uint64_t bytes_back = 0;                                 // what the host received: the summary's arrays, the filter's three words per read, its mask and map
     uint64_t removed_snps = 0, dropped_reads = 0;            // --ignore-monomorphic
-    std::vector<std::string> host_contigs;
-    floria_realign_counts counts = {};
 private:
     Session& s_;
     const BamFile& bam_;
@@ -427,9 +452,6 @@ private:
     const Options& o_;
     const std::string* contigs_;
     floria_record_summary* summary_ = nullptr;
-    std::vector<int32_t> table_of_;                          // contig of the list -> contig of the SNP table, -1
-    std::vector<uint64_t> snp_count_;                        // per table contig
-    std::vector<uint32_t> slot_;                             // record index of the segment -> position in the call + 1 (0: not sent)
 };
 std::pair<size_t, double> l_epsilon_auto_detect(const BamFile& bam);                   // :749-826
 // The same fed segment by segment (complete targets in header order, as BamStream::next yields them): done() once 1000 columns have been sampled,

@@ -894,6 +894,7 @@ struct ContigIngest::Impl {
     std::vector<std::vector<Tagged>> buckets;                                  // read name -> its passing alignments, in record order
     const std::map<SnpPosition, GnPosition>* snp_to_gn = nullptr;
     int64_t supp_aln_dist_cutoff = 0;
+    size_t n_records = 0;                                                      // of the contig, passing or not: the Frags' counter_ids lie below it
 };
 ContigIngest::~ContigIngest() = default;
 ContigIngest::ContigIngest(ContigIngest&&) noexcept = default;
@@ -927,6 +928,7 @@ ContigIngest::ContigIngest(const BamFile& bam, const VcfProfile& vp, const Optio
         if (ref_seq && !(on_device && device_cells->realigned)) realign(*ref_seq, fr, rec.seq, snp_to_gn, pos_allele_map, queue, o.realign_walk ? &o.walk : nullptr);             // :416-423
         buckets[ins.first->second].push_back({rec.flags, std::move(fr), rec_ix});
     }
+    p_->n_records = count;
 }
 
 // ---- --pileup device ------------------------------------------------------------------------------------------------------------------------
@@ -938,7 +940,6 @@ bool RecordPileup::cells(uint32_t rec_ix, Cells& out) const {
     out = {cells_->snp + b, cells_->allele + b, cells_->qual + b, cells_->seq_pos + b, (size_t)(e - b), cells_->ref_end[s - 1]};
     return true;
 }
-namespace {
 // The records of a round that go to the device, as floria_hip_pileup_records* takes them (shared by --pileup device / fused / resident): every record of the given
 // contigs that passes alignment_passed_check, as offsets into the stretch of the segment's inflated buffer that holds them; the SNP table of those contigs; with
 // ref_seqs their reference sequences back to back.  A contig the device's numbering (rank + 1) would not match, or with a site of more than FLORIA_MAX_ALLELES
@@ -1015,101 +1016,39 @@ struct RecordSelection {
     RecordSelection(const RecordSelection&) = delete;
     RecordSelection& operator=(const RecordSelection&) = delete;
 };
-}  // namespace
 
-RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
-                           const std::map<std::string, std::string>* ref_seqs) {
+void RoundWalk::walk(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
+                     const std::map<std::string, std::string>* ref_seqs, const std::function<void(const RecordSelection&)>& call) {
     RecordSelection sel(bam, vp, o, contigs, n_contigs, ref_seqs);
     host_contigs = sel.host_contigs;
+    table_of_ = sel.table_of;
+    for (size_t c = 0; c + 1 < sel.snp_off.size(); ++c) snp_count_.push_back(sel.snp_off[c + 1] - sel.snp_off[c]);
     const size_t n = sel.n();
     records_sent = n;
     if (n == 0) return;
     blob_bytes = sel.blob_bytes;
-    if (ref_seqs) {
-        if (const int rc = floria_hip_pileup_records_realign(session.ctx(), &sel.A, &sel.S, &sel.F, o.realign_walk ? &o.walk : nullptr, &cells_, &counts))
-            throw Error(rc, std::string("floria_hip_pileup_records_realign: ") + floria_hip_last_error());
-        realigned = true;
-    } else if (const int rc = floria_hip_pileup_records(session.ctx(), &sel.A, &sel.S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
+    call(sel);
     floria_timing tm;
     if (floria_hip_last_timing(session.ctx(), &tm) == 0) { kernel_ms = tm.pileup_ms; h2d_ms = tm.h2d_ms; d2h_ms = tm.d2h_ms; }
     slot_.assign(bam.records.size(), 0);
     for (size_t i = 0; i < n; ++i) slot_[sel.rec_of[i]] = (uint32_t)i + 1;
 }
 
-std::pair<std::vector<Frag>, std::vector<Frag>> ContigIngest::finish() {
-    std::vector<std::vector<Tagged>>& buckets = p_->buckets;
-    if (buckets.empty()) return {};
-    const std::map<SnpPosition, GnPosition>& snp_to_gn = *p_->snp_to_gn;
-    struct { int64_t supp_aln_dist_cutoff; } o{p_->supp_aln_dist_cutoff};
-    // combine_frags (:491-659)
-    std::vector<Frag> ref_frags;
-    for (auto& frags : buckets) {
-        if (frags.size() == 2 && frags[0].frag.is_paired && frags[1].frag.is_paired) {
-            std::sort(frags.begin(), frags.end(), [](const Tagged& a, const Tagged& b) { return a.flags != b.flags ? a.flags < b.flags : a.frag < b.frag; });
-            Tagged &first = frags[0], &second = frags[1];
-            Frag *ff, *sf;
-            if ((first.flags & F_PAIRED1) == F_PAIRED1) { ff = &first.frag; sf = &second.frag; }
-            else if ((first.flags & F_PAIRED2) == F_PAIRED2) { ff = &second.frag; sf = &first.frag; }
-            else continue;
-            if (!sf->seq_dict.empty()) {                                                   // first_frag.positions.extend(sec_frag.positions) (:541): remember who brought what
-                ff->merged_positions = true;
-                ff->position_segments.emplace_back(); ff->position_segments.emplace_back();
-                for (const auto& kv : ff->seq_dict) ff->position_segments[0].push_back(kv.first);
-                for (const auto& kv : sf->seq_dict) ff->position_segments[1].push_back(kv.first);
-            }
-            for (auto& kv : sf->seq_dict) ff->seq_dict[kv.first] = kv.second;              // extend: the mate's call overwrites
-            for (auto& kv : sf->qual_dict) ff->qual_dict[kv.first] = kv.second;
-            ff->first_position = std::min(ff->first_position, sf->first_position);
-            ff->last_position = std::max(ff->last_position, sf->last_position);
-            ff->first_pos_base = std::min(ff->first_pos_base, sf->first_pos_base);
-            ff->last_pos_base = std::min(ff->last_pos_base, sf->last_pos_base);           // (min, as in the reference, :547)
-            ff->seq_len[1] = sf->seq_len[0];
-            ff->seq_string[1] = std::move(sf->seq_string[0]); ff->qual_string[1] = std::move(sf->qual_string[0]);   // :551-554
-            for (auto& kv : sf->snp_pos_to_seq_pos) ff->snp_pos_to_seq_pos[kv.first] = {1, kv.second.second};
-            ref_frags.push_back(std::move(*ff));
-        } else if (frags.size() == 1 && (frags[0].flags & F_SUPP) == 0) {
-            ref_frags.push_back(std::move(frags[0].frag));
-        } else {
-            std::vector<std::pair<SnpPosition, SnpPosition>> supp_intervals;
-            for (auto& t : frags) if (!t.frag.seq_dict.empty()) supp_intervals.push_back({t.frag.first_position, t.frag.last_position});
-            std::sort(supp_intervals.begin(), supp_intervals.end());
-            bool take_primary_only = false;
-            for (size_t i = 0; i + 1 < supp_intervals.size(); ++i)
-                if ((int64_t)snp_to_gn.at(supp_intervals[i + 1].first) - (int64_t)snp_to_gn.at(supp_intervals[i].second) > o.supp_aln_dist_cutoff) { take_primary_only = true; break; }
-            int primary = -1;
-            for (size_t i = 0; i < frags.size(); ++i) if ((frags[i].flags & F_SUPP) != F_SUPP) primary = (int)i;   // the LAST primary wins (:606-614)
-            if (primary < 0) continue;
-            if (take_primary_only) { ref_frags.push_back(std::move(frags[primary].frag)); continue; }
-            Frag pf = std::move(frags[primary].frag);
-            for (size_t i = 0; i < frags.size(); ++i) {
-                if ((int)i == primary) continue;
-                Frag& fr = frags[i].frag;
-                if (!fr.seq_dict.empty()) {                                                  // :639
-                    pf.merged_positions = true;
-                    if (pf.position_segments.empty()) { pf.position_segments.emplace_back(); for (const auto& kv : pf.seq_dict) pf.position_segments[0].push_back(kv.first); }
-                    pf.position_segments.emplace_back();
-                    for (const auto& kv : fr.seq_dict) pf.position_segments.back().push_back(kv.first);
-                }
-                for (auto& kv : fr.seq_dict) pf.seq_dict[kv.first] = kv.second;
-                for (auto& kv : fr.qual_dict) pf.qual_dict[kv.first] = kv.second;
-                pf.first_position = std::min(pf.first_position, fr.first_position);
-                pf.last_position = std::max(pf.last_position, fr.last_position);
-                pf.first_pos_base = std::min(pf.first_pos_base, fr.first_pos_base);
-                pf.last_pos_base = std::min(pf.last_pos_base, fr.last_pos_base);
-                for (auto& kv : fr.snp_pos_to_seq_pos) pf.snp_pos_to_seq_pos[kv.first] = kv.second;
-            }
-            ref_frags.push_back(std::move(pf));
-        }
-    }
-    std::pair<std::vector<Frag>, std::vector<Frag>> out;
-    for (Frag& f : ref_frags) (f.seq_dict.empty() ? out.second : out.first).push_back(std::move(f));
-    buckets.clear();
-    return out;
+RecordPileup::RecordPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
+                           const std::map<std::string, std::string>* ref_seqs) {
+    walk(session, bam, vp, o, contigs, n_contigs, ref_seqs, [&](const RecordSelection& sel) {
+        if (ref_seqs) {
+            if (const int rc = floria_hip_pileup_records_realign(session.ctx(), &sel.A, &sel.S, &sel.F, o.realign_walk ? &o.walk : nullptr, &cells_, &counts))
+                throw Error(rc, std::string("floria_hip_pileup_records_realign: ") + floria_hip_last_error());
+            realigned = true;
+        } else if (const int rc = floria_hip_pileup_records(session.ctx(), &sel.A, &sel.S, &cells_)) throw Error(rc, std::string("floria_hip_pileup_records: ") + floria_hip_last_error());
+    });
 }
 
-// ---- --pileup resident: combine_frags on headers -----------------------------------------------------------------------------------------------
-// The decisions of finish() above restated on (flags, counter_id, first, last) alone.  A record without cells has first = UINT32_MAX and last = 0, what its Frag
-// has in the host route, so the sort of a pair, the intervals of a supplementary group and the merged ends come out as they do there.
+// ---- combine_frags on headers (every route) ------------------------------------------------------------------------------------------------------
+// The decisions of combine_frags (:491-659) on (flags, counter_id, first, last) alone: ContigIngest::finish() merges its Frags by this plan, --pileup resident hands
+// it to the device.  A record without cells has first = UINT32_MAX and last = 0, what its Frag has, so the sort of a pair, the intervals of a supplementary group and
+// the merged ends come out as they do on the Frags themselves.
 ContigPlan plan_contig(std::vector<std::vector<PlanRecord>>& groups, const std::map<SnpPosition, GnPosition>& snp_to_gn, int64_t supp_aln_dist_cutoff) {
     const auto frag_less = [](SnpPosition af, SnpPosition al, size_t ac, SnpPosition bf, SnpPosition bl, size_t bc) {      // Frag::cmp
         if (af != bf) return af < bf;
@@ -1182,26 +1121,59 @@ ContigPlan ContigIngest::plan() const {
     return plan_contig(groups, *p_->snp_to_gn, p_->supp_aln_dist_cutoff);
 }
 
+namespace {
+// first_frag.positions.extend(..) and what goes with it (:539-562 for a mate, :633-650 for a supplementary piece): `fr` is merged onto `base`
+void extend_frag(Frag& base, Frag& fr, bool mate) {
+    if (!fr.seq_dict.empty()) {                                                        // positions.extend (:541, :639): remember who brought what
+        base.merged_positions = true;
+        if (base.position_segments.empty()) { base.position_segments.emplace_back(); for (const auto& kv : base.seq_dict) base.position_segments[0].push_back(kv.first); }
+        base.position_segments.emplace_back();
+        for (const auto& kv : fr.seq_dict) base.position_segments.back().push_back(kv.first);
+    }
+    for (auto& kv : fr.seq_dict) base.seq_dict[kv.first] = kv.second;                  // extend: the later part's call overwrites
+    for (auto& kv : fr.qual_dict) base.qual_dict[kv.first] = kv.second;
+    base.first_position = std::min(base.first_position, fr.first_position);
+    base.last_position = std::max(base.last_position, fr.last_position);
+    base.first_pos_base = std::min(base.first_pos_base, fr.first_pos_base);
+    base.last_pos_base = std::min(base.last_pos_base, fr.last_pos_base);               // (min, as in the reference, :547)
+    if (mate) {
+        base.seq_len[1] = fr.seq_len[0];
+        base.seq_string[1] = std::move(fr.seq_string[0]); base.qual_string[1] = std::move(fr.qual_string[0]);   // :551-554
+        for (auto& kv : fr.snp_pos_to_seq_pos) base.snp_pos_to_seq_pos[kv.first] = {1, kv.second.second};
+    } else
+        for (auto& kv : fr.snp_pos_to_seq_pos) base.snp_pos_to_seq_pos[kv.first] = kv.second;
+}
+}  // namespace
+
+std::pair<std::vector<Frag>, std::vector<Frag>> ContigIngest::finish() {
+    std::vector<std::vector<Tagged>>& buckets = p_->buckets;
+    if (buckets.empty()) return {};
+    const ContigPlan pl = plan();
+    std::vector<Frag*> by_counter(p_->n_records, nullptr);                             // a part is named by its counter_id: the record's place among the contig's
+    for (auto& frags : buckets) for (Tagged& t : frags) by_counter[t.frag.counter_id] = &t.frag;
+    const auto merged = [&](const PlannedFrag& pf) -> Frag& {
+        Frag& base = *by_counter[pf.parts[0].counter_id];
+        for (size_t k = 1; k < pf.parts.size(); ++k) extend_frag(base, *by_counter[pf.parts[k].counter_id], pf.mate[k] != 0);
+        return base;
+    };
+    std::pair<std::vector<Frag>, std::vector<Frag>> out;
+    out.first.reserve(pl.frags.size()); out.second.reserve(pl.snpless.size());
+    for (const PlannedFrag& pf : pl.frags) out.first.push_back(std::move(merged(pf)));
+    for (const PlannedFrag& pf : pl.snpless) out.second.push_back(std::move(merged(pf)));
+    buckets.clear();
+    return out;
+}
+
 ResidentPileup::~ResidentPileup() { floria_hip_record_summary_free(summary_); }
 ResidentPileup::ResidentPileup(Session& session, const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string* contigs, size_t n_contigs,
                                const std::map<std::string, std::string>* ref_seqs)
     : s_(session), bam_(bam), vp_(vp), o_(o), contigs_(contigs) {
-    RecordSelection sel(bam, vp, o, contigs, n_contigs, ref_seqs);
-    host_contigs = sel.host_contigs;
-    table_of_ = sel.table_of;
-    for (size_t c = 0; c + 1 < sel.snp_off.size(); ++c) snp_count_.push_back(sel.snp_off[c + 1] - sel.snp_off[c]);
-    const size_t n = sel.n();
-    records_sent = n;
-    if (n == 0) return;
-    blob_bytes = sel.blob_bytes;
-    if (const int rc = floria_hip_pileup_records_resident(session.ctx(), &sel.A, &sel.S, ref_seqs ? &sel.F : nullptr, o.realign_walk ? &o.walk : nullptr, &summary_))
-        throw Error(rc, std::string("floria_hip_pileup_records_resident: ") + floria_hip_last_error());
-    counts = summary_->counts;
-    floria_timing tm;
-    if (floria_hip_last_timing(session.ctx(), &tm) == 0) { kernel_ms = tm.pileup_ms; h2d_ms = tm.h2d_ms; d2h_ms = tm.d2h_ms; }
-    bytes_back += (uint64_t)n * 24 + 8;                                        // cell_off, first_snp, last_snp, ref_end
-    slot_.assign(bam.records.size(), 0);
-    for (size_t i = 0; i < n; ++i) slot_[sel.rec_of[i]] = (uint32_t)i + 1;
+    walk(session, bam, vp, o, contigs, n_contigs, ref_seqs, [&](const RecordSelection& sel) {
+        if (const int rc = floria_hip_pileup_records_resident(session.ctx(), &sel.A, &sel.S, ref_seqs ? &sel.F : nullptr, o.realign_walk ? &o.walk : nullptr, &summary_))
+            throw Error(rc, std::string("floria_hip_pileup_records_resident: ") + floria_hip_last_error());
+        counts = summary_->counts;
+        bytes_back += (uint64_t)sel.n() * 24 + 8;                              // cell_off, first_snp, last_snp, ref_end
+    });
 }
 
 HeaderContig ResidentPileup::plan(size_t ci) const {

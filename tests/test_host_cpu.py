@@ -484,6 +484,73 @@ def test_hand_built_alignments_flags_cigar_ops_and_supplementary_merging(floria_
     assert [(c[0], c[1]) for c in e["cells"]] == [(1, 1), (2, 1), (61, 1), (62, 1)] and e["span"] == (900, 1600)
 
 
+def test_hand_built_merges_a_cell_less_base_a_cell_less_piece_and_two_primaries(floria_hip, tmp_path):
+    """combine_frags cases the hand-built set above lacks (it has: primary + one supplementary piece within and beyond the cutoff, supplementary only, a
+    low-MAPQ supplementary, a snpless read), the --dump-frags records written out by hand from file_reader.rs:491-659:
+      a  a proper pair whose flag-64 mate covers no SNP and whose flag-128 mate covers two: the flag-64 mate is the base whatever the record order (:519-533), its
+         position set is empty before `extend` (:541), the mate's calls are entered as mate 1 (:556-562), last_pos_base is the MIN of the two ends (:547)
+      b  a primary and two supplementary pieces, the first of them (in record order) without a SNP: merged in record order behind the primary (:617-650); with a
+         cutoff below the gap between the pieces that have SNPs, the primary alone (:585-605)
+      c  a name with two primaries: the LAST one is the base (:606-614), the other is merged onto it and its call overwrites the base's at the SNP both cover
+    A merged fragment carries an #ORDER line (the replay of what its position set went through), a fragment of one alignment does not."""
+    from oracle import oracle as _orc
+    rng = np.random.default_rng(8)
+    clen = 3000
+    ref = synth_bam.BASES[rng.integers(0, 4, size=clen)].copy()
+    snp_pos = 1000 + 40 * np.arange(10)                                       # SNP i+1 at 0-based position snp_pos[i]: 1000, 1040 .. 1360
+    nxt = {65: 67, 67: 71, 71: 84, 84: 65}
+    alt = np.array([nxt[int(ref[q])] for q in snp_pos], np.uint8)
+    prefix = str(tmp_path / "m")
+    with open(prefix + ".fa", "w") as f:
+        f.write(">c\n" + bytes(ref).decode() + "\n")
+    with open(prefix + ".vcf", "w") as f:
+        f.write("##fileformat=VCFv4.2\n##contig=<ID=c,length=%d>\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\ts\n" % clen)
+        for i, q in enumerate(snp_pos):
+            f.write(f"c\t{q + 1}\t.\t{chr(ref[q])}\t{chr(alt[i])}\t50\tPASS\t.\tGT\t0/1\n")
+    recs = []
+
+    def add(name, pos, flag, alts):                                           # 100 aligned bases from pos, ALT at the SNPs (1-based) in `alts`, REF elsewhere
+        s = ref[pos:pos + 100].copy()
+        for i in alts:
+            s[snp_pos[i - 1] - pos] = alt[i - 1]
+        recs.append((pos, synth_bam.bam_record(0, pos, name, flag, 60, [("M", 100)], bytes(s), np.full(100, 30, np.uint8))))
+    add("a_pair", 1290, 147, [9])                                             # second mate: SNPs 9 (ALT, read offset 30) and 10 (REF, offset 70); first in the file
+    add("a_pair", 1370, 99, [])                                               # first mate: behind the last SNP
+    add("b_supp", 500, 2048, [])                                              # before the first SNP
+    add("b_supp", 1000, 0, [1, 2, 3])
+    add("b_supp", 1190, 2048, [6, 7, 8])
+    add("c_two", 1000, 0, [1, 2, 3])
+    add("c_two", 1070, 0, [4, 5])                                             # SNP 3 (REF here), 4, 5
+    recs.sort(key=lambda t: t[0])
+    synth_bam.write_bam(prefix + ".bam", [("c", clen)], [r for _, r in recs])
+
+    def order(*segs):
+        return "#ORDER\t" + "\t".join(str(x) for x in _orc.positions_order([np.asarray(s, np.uint32) for s in segs]).tolist())
+
+    def cells(calls):
+        return "\t".join(f"{s}:{a}:30" for s, a in calls)
+
+    def run(extra):
+        r = subprocess.run([floria_hip, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-o", str(tmp_path / "unused"), "-e", "0.03", "-l", "10000", "--ingest-only",
+                            "--no-realign", "--snp-count-filter", "5", "--dump-frags", prefix + ".frags", "--dump-seq-pos", prefix + ".sp", *extra], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        return open(prefix + ".frags").read().split("\n"), open(prefix + ".sp").read().split("\n")
+    a_pair = ["a_pair\t9\t10\t1290\t1390\t1\t" + cells([(9, 1), (10, 0)]), order([], [9, 10])]
+    c_two = ["c_two\t1\t5\t1000\t1100\t0\t" + cells([(1, 1), (2, 1), (3, 1), (4, 1), (5, 1)]), order([3, 4, 5], [1, 2, 3])]
+    frags, seq_pos = run(())
+    assert frags == ["#CONTIG\tc\t3\t0",
+                     "b_supp\t1\t8\t500\t600\t0\t" + cells([(1, 1), (2, 1), (3, 1), (6, 1), (7, 1), (8, 1)]), order([1, 2, 3], [6, 7, 8])] + c_two + a_pair + [""]
+    assert seq_pos == ["#CONTIG\tc\t3",
+                       "b_supp\t1:0:0\t2:0:40\t3:0:80\t6:0:10\t7:0:50\t8:0:90",
+                       "c_two\t1:0:0\t2:0:40\t3:0:80\t4:0:50\t5:0:90",
+                       "a_pair\t9:1:30\t10:1:70", ""]
+    # the pieces of b that have SNPs are 1200 - 1080 = 120 bases apart: beyond a cutoff of 100 the primary stands alone, a fragment of one alignment
+    # (and sorts behind c: Frag::cmp puts the larger last SNP first)
+    frags, seq_pos = run(("--supp-aln-dist-cutoff", "100"))
+    assert frags == ["#CONTIG\tc\t3\t0"] + c_two + ["b_supp\t1\t3\t1000\t1100\t0\t" + cells([(1, 1), (2, 1), (3, 1)])] + a_pair + [""]
+    assert seq_pos[2] == "b_supp\t1:0:0\t2:0:40\t3:0:80"
+
+
 def test_flatmap_behaves_like_std_map():
     # the Frag maps are sorted vectors with std::map's interface (floria_host.hpp: FlatMap): random operations against std::map
     cpp = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp")
