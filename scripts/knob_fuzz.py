@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """(GPU) the canonical S1 path under random launch knobs (kernel choice, insert path, stage plans, workgroup sizes, grid sizes) on random pileups against the
-oracle: every knob combination must give the oracle's bits.   usage: scripts/knob_fuzz.py [first seed = 0] [count = 300]"""
+oracle: every knob combination must give the oracle's bits; one pileup in four is moved by up to 300 000 SNPs along its contig first.   usage: scripts/knob_fuzz.py [first seed = 0] [count = 300]"""
 import sys
 sys.path.insert(0, ".")
 import numpy as np
 from floria_amd import lib
 from oracle import oracle
 from tests.helpers import random_pileup
+from tests.wide_cases import shifted
 
 oracle.build()
 ctx = lib.FloriaHip(0)
@@ -36,13 +37,16 @@ for seed in range(s0, s0 + cnt):
     knobs = {k: (v[int(rng.integers(0, len(v)))]) for k, v in KNOBS.items()}
     for k, v in knobs.items():
         ctx.set_option(k, v)
+    mv = np.random.default_rng([990000 + seed, 1])          # a generator of its own: the pileups and knobs of earlier seeds stay as they were
+    off = int(mv.integers(0, 300001)) if mv.random() < 0.25 else 0
+    pile, s, e = shifted(pile, off), s + off, e + off
     ro = oracle.phase_blocks(pile, s, e, oracle.make_params(eps, P, B, sens, stop), threads=4)
     rg = ctx.phase_blocks(pile, s, e, lib.make_params(eps, P, B, sens, stop))
     same = (np.array_equal(ro.best_ploidy, rg.best_ploidy) and np.array_equal(ro.part, rg.part) and np.array_equal(ro.mec.view(np.uint64), rg.mec.view(np.uint64))
             and np.array_equal(ro.ploidies_tried, rg.ploidies_tried) and (ro.min_prune_margin == rg.min_prune_margin or abs(ro.min_prune_margin - rg.min_prune_margin) <= 1e-11))
     if not same:
         bad += 1
-        print(f"MISMATCH seed {seed} margins {ro.min_prune_margin!r} / {rg.min_prune_margin!r} eps {eps} P {P} B {B} sens {sens} stop {stop} alleles {alleles} knobs {knobs}: best {ro.best_ploidy} / {rg.best_ploidy}")
+        print(f"MISMATCH seed {seed} margins {ro.min_prune_margin!r} / {rg.min_prune_margin!r} eps {eps} P {P} B {B} sens {sens} stop {stop} alleles {alleles} moved by {off} knobs {knobs}: best {ro.best_ploidy} / {rg.best_ploidy}")
 for k, v in DEFAULT.items():
     ctx.set_option(k, v)
 print(f"seeds {s0}..{s0 + cnt - 1} under random launch knobs: {bad} mismatches")
