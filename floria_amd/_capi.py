@@ -140,8 +140,9 @@ class BlockResult:
         self.ploidies_tried = np_from(c.ploidies_tried, nb, np.uint32)
         self.read_off = np_from(c.read_off, nb + 1, np.uint64)
         tot = int(self.read_off[nb]) if nb else 0
-        self.read_id = np_from(c.read_id, tot, np.uint32)
-        self.part = np_from(c.part, tot, np.uint8)
+        self.has_lists = bool(c.read_id) or tot == 0          # "s1_no_lists": read_id and part are NULL, the lists stayed on the device
+        self.read_id = np_from(c.read_id, tot if c.read_id else 0, np.uint32)
+        self.part = np_from(c.part, tot if c.part else 0, np.uint8)
         self.mec = np_from(c.mec, nb * mp, np.float64).reshape(nb, mp)
         self.min_prune_margin = float(c.min_prune_margin)
         self.batch_token = int(c.batch_token)

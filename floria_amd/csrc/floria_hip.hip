@@ -51,6 +51,7 @@
 #include "mono_kernel.h"
 #include "span_kernel.h"
 #include "haploset_kernel.h"
+#include "path_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -200,6 +201,7 @@ struct Knobs {
     uint32_t arith_replay = 0;    // (tests) reference arithmetic: replay every position map insertion by insertion (the home-bucket rule of optimize_kernel.h off)
     uint32_t arith_hbm = 0;       // (tests) reference arithmetic: position-map tables and first-insertion keys in HBM scratch even where they fit into LDS
     uint32_t opt_block_order = 0; // (A/B, tests) optimise: the build / distance passes visit the reads in block order instead of longest first
+    uint32_t s1_no_lists = 0;     // floria_hip_phase_*: the read-id lists and partition bytes stay on the device (read_id / part of the result are NULL): for a host that joins paths there (floria_hip_join_paths)
     uint32_t s2_assign_only = 0;  // S2 returns the haplogroups as re-inserted (input order): separate_broken_haplogroups and sort_parts are left to a host that iterates its own sets
     uint32_t arith = 0;           // 1 = the reference's own running f64 sums in its own orders (arith_kernel.h; slower kernels), 0 = the canonical (Q24, #eps) form
     int32_t  tail_overlap = 0;    // one ploidy per stage: the LAST ploidy's beam launch runs beside the optimise launch of the ploidy below, every job waiting for its block's
@@ -254,6 +256,7 @@ struct floria_hip_ctx {
     const uint32_t* last_best = nullptr;
     uint32_t last_nall = 2;
     std::vector<uint32_t> last_bc, last_start, last_end;
+    std::vector<const floria_hip_contig*> last_contigs;      // the handles that batch was phased from (floria_hip_join_paths refuses any other array)
     DevBuf graph_buf, graph_hist, graph_sort;
     // uploads
     DevBuf up_tmp;                            // raw allele / qual bytes + the flatten kernel's tables (transient per upload)
@@ -272,7 +275,8 @@ struct floria_hip_ctx {
     double mono_ms[6] = {};                   // the last floria_hip_drop_monomorphic call's device time by kind (floria_hip_mono_timing)
     DevBuf mono_buf;                          // floria_hip_drop_monomorphic: the per-SNP tables, the per-read survivor words and the call's small tables
     DevBuf span_buf;                          // floria_hip_read_spans: the groups, the contig table and the two result arrays (a buffer of its own: no residency ends)
-    DevBuf hs_tmp;                            // floria_hip_reassign_batch_resident: the slot tables between its kernels (the handle has a buffer of its own)
+    DevBuf hs_tmp;                            // floria_hip_reassign_batch_resident: the slot tables between its kernels (the handle has a buffer of its own); floria_hip_join_paths: its path tables
+    DevBuf join_bits;                         // floria_hip_join_paths: the paths' bitmaps
     uint32_t stage_threads = 8;
 };
 
@@ -1005,7 +1009,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -1074,6 +1078,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "fx_tags") { if (value != 0 && (value < (int64_t)fl::FX_TAGS_MIN || value > (int64_t)fl::FX_TAGS_MAX || (value & (value - 1)))) return fail(FLORIA_E_INVALID, "fx_tags: 0 | a power of two in 128..1024"); K.fx_tags = (uint32_t)value; }
     else if (k == "arith_ow6") K.arith_ow6 = value != 0;
     else if (k == "s2_assign_only") K.s2_assign_only = value != 0;
+    else if (k == "s1_no_lists") K.s1_no_lists = value != 0;
     else if (k == "arith") { if (value < 0 || value > 1) return fail(FLORIA_E_INVALID, "arith: 0 canonical | 1 the reference's running sums"); K.arith = (uint32_t)value; }
     else if (k == "hw_queues") ctx->hw_queues = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 64));      // (tests: pretend the probe found this many)
     else if (k == "upload_chunks") K.upload_chunks = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, floria_hip_ctx::MAX_GROUPS));
@@ -1893,7 +1898,7 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     if (prm->beam < 1) return fail(FLORIA_E_INVALID, "beam (max_number_solns) must be >= 1");
     if (!(prm->epsilon > 0.0 && prm->epsilon < 1.0)) return fail(FLORIA_E_INVALID, "epsilon must be in (0,1)");
     ctx->timing = floria_timing{};
-    ctx->batch_token = 0;
+    ctx->batch_token = 0; ctx->last_contigs.clear();
     const uint32_t P = prm->max_ploidy;
 
     // ---- block read lists: find_reads_in_interval on the device (blocks_kernel.h) -------------------------------
@@ -2032,11 +2037,12 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     R->best_ploidy = (uint32_t*)calloc(n_blocks + 1, 4);
     R->ploidies_tried = (uint32_t*)calloc(n_blocks + 1, 4);
     R->read_off = (uint64_t*)calloc(n_blocks + 1, 8);
-    R->read_id = (uint32_t*)g_big.get(4 * (tot + 1));
-    R->part = (uint8_t*)g_big.get(tot + 1);
+    const bool lists = !ctx->knobs.s1_no_lists;       // "s1_no_lists": the lists stay where floria_hip_hap_graph and floria_hip_join_paths read them
+    R->read_id = lists ? (uint32_t*)g_big.get(4 * (tot + 1)) : nullptr;
+    R->part = lists ? (uint8_t*)g_big.get(tot + 1) : nullptr;
     R->mec = (double*)calloc((size_t)n_blocks * P + 1, 8);
     struct ResultGuard { floria_hip_ctx* c; floria_block_result* r; ~ResultGuard() { if (r) { sync_all(c); floria_hip_block_result_free(r); } } } guard{ctx, R};   // every early return below
-    if (!R->best_ploidy || !R->ploidies_tried || !R->read_off || !R->read_id || !R->part || !R->mec) { return fail(FLORIA_E_NOMEM, "malloc"); }
+    if (!R->best_ploidy || !R->ploidies_tried || !R->read_off || (lists && (!R->read_id || !R->part)) || !R->mec) { return fail(FLORIA_E_NOMEM, "malloc"); }
     bool p1_shortcut = false;
     const PhaseShape shape{bs, any_q0, (uint32_t)jobs.size(), tot, n_max, span_max};
     const PhaseBufs bufs{C.at<const uint32_t>(s_jobs), C.at<uint8_t>(s_planes), C.at<uint8_t>(s_bpart), C.at<double>(s_mec), C.at<double>(s_na), C.at<uint32_t>(s_it),
@@ -2047,7 +2053,7 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     if (rc) { sync_all(ctx); return rc; }
     TR.mark("every launch queued");
     int t_rids = -1;
-    if (n_blocks && tot) {              // everything is queued: the copy (pageable destination, the host may block here) overlaps the kernels
+    if (n_blocks && tot && lists) {     // everything is queued: the copy (pageable destination, the host may block here) overlaps the kernels
         HIPCHK(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_rids, 0));
         t_rids = T.begin(K_D2H, ctx->copy_stream);
         hipError_t ce = hipMemcpyAsync(R->read_id, C.at(s_rids), 4ull * tot, hipMemcpyDeviceToHost, ctx->copy_stream);
@@ -2071,7 +2077,7 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
         e = hipMemcpyAsync(R->best_ploidy, C.at(s_best), 4ull * n_blocks, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(R->ploidies_tried, C.at(s_tried), 4ull * n_blocks, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(R->mec, C.at(s_mec), 8ull * n_blocks * P, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && tot) e = hipMemcpyAsync(R->part, C.at(s_out), tot, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && tot && lists) e = hipMemcpyAsync(R->part, C.at(s_out), tot, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(diag, C.at(s_diag), 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&steps, C.at(s_steps), 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -2189,7 +2195,9 @@ int floria_hip_phase_blocks_batch(floria_hip_ctx* ctx, const floria_hip_contig* 
         SC.nall = std::max(SC.nall, contigs[i]->n_alleles);
         SC.any_q0 = SC.any_q0 || contigs[i]->has_q0;
     }
-    return s1_core(ctx, SC, blk_contig, blk_start, blk_end, n_blocks, prm, out);
+    const int rc = s1_core(ctx, SC, blk_contig, blk_start, blk_end, n_blocks, prm, out);
+    if (!rc) ctx->last_contigs.assign(contigs, contigs + n_contigs);
+    return rc;
 }
 
 // S1 straight from host pileups: floria_hip_contig_upload_batch + floria_hip_phase_blocks_batch as ONE pipelined call.  The
@@ -2294,6 +2302,7 @@ static int phase_pileups_impl(floria_hip_ctx* ctx, const floria_pileup* pileups,
         // 0|111|2 106.7, 0|11|22 107.7, 00|11|2 108.0, 000|11 108.9, 00|111 108.9, 0|1111 109.3, a group per chunk 109.6, one group 109.4
         if (pk) { SC.chunk_groups = 3; SC.ends_apart = true; }
         if (int rc = s1_core(ctx, SC, blk_contig, blk_start, blk_end, n_blocks, prm, &R)) return rc;
+        ctx->last_contigs.assign(handles.begin(), handles.end());
         const floria_timing tm = ctx->timing;
         HIPCHK_AS("upload status: ", hipMemcpy(UP.ust.data(), UP.T + UP.t_st, sizeof(fl::UploadStatus) * n_contigs, hipMemcpyDeviceToHost));
         if (int rc = UP.commit()) return rc;
@@ -3463,6 +3472,13 @@ struct floria_hip_haplosets {
 
 namespace {
 
+int hs_headers(const floria_hip_haplosets* chs);
+int hs_spans(floria_hip_ctx* ctx, const floria_hip_haplosets* chs);
+struct S2Plan;
+int s2_resident_core(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, S2Plan& P, const std::vector<uint64_t>& gb,
+                     const std::vector<uint32_t>& in_contig, const std::vector<uint32_t>& in_range, const uint32_t* read_order, const uint64_t* order_off, double epsilon,
+                     floria_hip_haplosets** out);
+
 // S2 up to the re-insertion kernels, shared by floria_hip_reassign_batch and floria_hip_reassign_batch_resident: validation, the host prologue (read -> candidate
 // groups, the `multi` list, p0 / p1), the call's segments in the context's scratch, the uploads and the launch with its path choice.  `assign` stays on the device.
 struct S2Plan {
@@ -3473,6 +3489,8 @@ struct S2Plan {
     std::vector<uint32_t> rid_lo, rid_hi;                          // per group, contig-major as gpos0_all: the id window [lo, hi) of its input list (haploset_kernel.h)
     std::vector<fl::ContigDev> cdev;
     uint64_t hist_cells = 0, n_assign = 0;
+    uint64_t n_ro = 0, n_r2g = 0, n_mu = 0;                        // entries of r2g_off / r2g / multi the call's segments hold
+    const floria_hip_haplosets* src = nullptr;                     // non-null: the input groups are this handle's, and the per-read tables are built on the device (dev_tables)
     Seg s_cd{}, s_rob{}, s_rb{}, s_gb{}, s_ab{}, s_ro{}, s_r2g{}, s_ho{}, s_p0{}, s_hist{}, s_as{}, s_q{}, s_ord{}, s_oo{}, s_mu{}, s_mo{}, s_ls{};
 
     int prologue(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const uint32_t* grp_contig, const uint64_t* grp_off,
@@ -3550,16 +3568,81 @@ struct S2Plan {
         n_assign += N;
     }
     multi_off_all.push_back(multi_all.size());
+    n_ro = r2g_off_all.size(); n_r2g = r2g_all.size(); n_mu = multi_all.size();
     return 0;
+    }
+
+    // The second way to fill the tables: the input groups are a handle's (floria_hip_reassign_haplosets_resident).  The host part reads header-sized data only — per
+    // group its size and the SNP span of its reads (the handle's mirrors: hs_headers, hs_spans) — and sizes the segments; the per-read tables (read -> groups, `multi`)
+    // are built on the device inside run() (dev_tables).  Reads are visited in ascending id.  No first / last comes to the host (no host_meta).
+    int prologue_handle(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* in) {
+        HIPCHK(hipSetDevice(ctx->device));
+        ctx->timing = floria_timing{};
+        if (int rc = hs_headers(in)) return rc;
+        if (int rc = hs_spans(ctx, in)) return rc;
+        ctx->batch_token = 0;                      // misc is about to be overwritten
+        src = in;
+        r2g_off_base.assign(n_contigs, 0); r2g_base.assign(n_contigs, 0); grp_base.assign(n_contigs, 0); assign_base.assign(n_contigs, 0);
+        cdev.assign(n_contigs, fl::ContigDev{});
+        for (uint32_t i = 0; i < n_contigs; ++i) A = std::max(A, contigs[i]->n_alleles);
+        uint64_t g = 0;
+        for (uint32_t ci = 0; ci < n_contigs; ++ci) {
+            cdev[ci] = contigs[ci]->dev;
+            grp_base[ci] = g; assign_base[ci] = n_assign; r2g_off_base[ci] = n_assign + ci;      // (haploset_kernel.h: n_reads + 1 slots per contig, r2g_base stays 0)
+            for (uint64_t k = 0; k < in->c_groups[ci]; ++k, ++g) {
+                hist_off_all.push_back(hist_cells);
+                gpos0_all.push_back(in->h_lo[g]);
+                hist_cells += (uint64_t)in->h_len[g] * A;
+            }
+            n_assign += contigs[ci]->n_reads;
+        }
+        n_ro = n_assign + n_contigs; n_r2g = in->n_reads; n_mu = in->n_reads / 2;      // (a read with a choice sits in two groups at the least)
+        if (n_ro >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "reassign_haplosets_resident: 2^32 and more reads in one call");
+        return 0;
+    }
+
+    // ... and its device part, into the segments run() would upload: read -> groups offsets and lists, `multi` and its offsets (haploset_kernel.h).  The per-contig
+    // `multi` counts come back for the path choice: one word per contig.
+    int dev_tables(floria_hip_ctx* ctx, uint32_t n_contigs, const Carve& C, EventTimer& T) {
+        const uint32_t n_groups = (uint32_t)src->n_groups;
+        Carve S;
+        const uint32_t tiles = (uint32_t)((n_ro + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE);
+        const Seg s_mf = S.seg(8ull * n_ro + 8), s_ti = S.seg(8ull * tiles + 8);
+        if (int rc = S.place(ctx->hs_tmp)) return rc;
+        fl::HpArgs a{};
+        a.contigs = C.at<const fl::ContigDev>(s_cd); a.grp_contig = src->d_gc; a.grp_off = src->d_go; a.grp_read = src->d_gr;
+        a.grp_base = C.at<const uint64_t>(s_gb); a.ro_base = C.at<const uint64_t>(s_rob); a.ro = C.at<uint64_t>(s_ro); a.mf = S.at<uint64_t>(s_mf);
+        a.cursor = C.at<uint32_t>(s_as); a.r2g = C.at<uint32_t>(s_r2g); a.multi = C.at<uint32_t>(s_mu); a.multi_off = C.at<uint64_t>(s_mo);
+        a.n_slots = n_ro; a.n_entries = n_r2g; a.n_multi_cap = n_mu; a.n_groups = n_groups; a.n_contigs = n_contigs;
+        HIPCHK(hipMemsetAsync(a.ro, 0, 8ull * n_ro + 8, ctx->stream));
+        HIPCHK(hipMemsetAsync(a.cursor, 0, 4ull * n_assign + 4, ctx->stream));
+        const uint32_t grid_g = items_grid(ctx, n_groups, 4), grid_s = items_grid(ctx, n_ro, 256);
+        int tk = T.begin(K_SEL);
+        hipLaunchKernelGGL(fl::hp_groups_kernel<false>, dim3(grid_g), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(fl::hp_flag_kernel, dim3(grid_s), dim3(256), 0, ctx->stream, a);
+        launch_offset_scan(ctx, a.ro, S.at<uint64_t>(s_ti), (uint32_t)n_ro);
+        launch_offset_scan(ctx, a.mf, S.at<uint64_t>(s_ti), (uint32_t)n_ro);
+        hipLaunchKernelGGL(fl::hp_groups_kernel<true>, dim3(grid_g), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(fl::hp_sort_kernel, dim3(grid_s), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL(fl::hp_multi_off_kernel, dim3(items_grid(ctx, n_contigs + 1, 256)), dim3(256), 0, ctx->stream, a);
+        T.end(tk);
+        HIPCHK(hipGetLastError());
+        multi_off_all.assign(n_contigs + 1, 0);
+        int td = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(multi_off_all.data(), a.multi_off, 8ull * (n_contigs + 1), hipMemcpyDeviceToHost, ctx->stream));
+        T.end(td);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (multi_off_all.back() > n_mu) return fail(FLORIA_E_DEVICE, "reassign_haplosets_resident: the device's read tables are inconsistent");
+        return 0;
     }
 
     // the call's segments, first in the caller's Carve (it may add its own behind them before it places the Carve in ctx->misc)
     void carve(Carve& C, uint32_t n_contigs, const uint32_t* read_order, const uint64_t* order_off) {
         s_cd = C.seg(sizeof(fl::ContigDev) * n_contigs); s_rob = C.seg(8ull * n_contigs); s_rb = C.seg(8ull * n_contigs); s_gb = C.seg(8ull * n_contigs);
-        s_ab = C.seg(8ull * n_contigs); s_ro = C.seg(8ull * r2g_off_all.size() + 8); s_r2g = C.seg(4ull * r2g_all.size() + 4);
+        s_ab = C.seg(8ull * n_contigs); s_ro = C.seg(8ull * n_ro + 8); s_r2g = C.seg(4ull * n_r2g + 4);
         s_ho = C.seg(8ull * hist_off_all.size() + 8); s_p0 = C.seg(4ull * gpos0_all.size() + 4); s_hist = C.seg(8ull * hist_cells + 8);
         s_as = C.seg(4ull * n_assign + 4); s_q = C.seg(16); s_ord = C.seg(read_order ? 4ull * order_off[n_contigs] + 4 : 4);
-        s_oo = C.seg(8ull * (n_contigs + 1)); s_mu = C.seg(4ull * multi_all.size() + 4); s_mo = C.seg(8ull * (n_contigs + 1)); s_ls = C.seg(4ull * n_contigs + 4);
+        s_oo = C.seg(8ull * (n_contigs + 1)); s_mu = C.seg(4ull * n_mu + 4); s_mo = C.seg(8ull * (n_contigs + 1)); s_ls = C.seg(4ull * n_contigs + 4);
     }
 
     // uploads + the re-insertion launches, timed into T (K_H2D, K_REASSIGN); the caller goes on in the same stream
@@ -3570,13 +3653,14 @@ struct S2Plan {
         HIPCHK(C.up(s_cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream));
         HIPCHK(C.up(s_rob, r2g_off_base.data(), 8ull * n_contigs, ctx->stream)); HIPCHK(C.up(s_rb, r2g_base.data(), 8ull * n_contigs, ctx->stream));
         HIPCHK(C.up(s_gb, grp_base.data(), 8ull * n_contigs, ctx->stream)); HIPCHK(C.up(s_ab, assign_base.data(), 8ull * n_contigs, ctx->stream));
-        HIPCHK(C.up(s_ro, r2g_off_all.data(), 8ull * r2g_off_all.size(), ctx->stream)); HIPCHK(C.up(s_r2g, r2g_all.data(), 4ull * r2g_all.size(), ctx->stream));
+        if (!src) { HIPCHK(C.up(s_ro, r2g_off_all.data(), 8ull * r2g_off_all.size(), ctx->stream)); HIPCHK(C.up(s_r2g, r2g_all.data(), 4ull * r2g_all.size(), ctx->stream)); }
         HIPCHK(C.up(s_ho, hist_off_all.data(), 8ull * hist_off_all.size(), ctx->stream)); HIPCHK(C.up(s_p0, gpos0_all.data(), 4ull * gpos0_all.size(), ctx->stream));
+        if (src) { T.end(th); rc = dev_tables(ctx, n_contigs, C, T); if (rc) return rc; th = T.begin(K_H2D); }      // (its cursors lie in `assign`: before the memset below)
         HIPCHK(hipMemsetAsync(C.at(s_hist), 0, s_hist.bytes, ctx->stream));
         HIPCHK(hipMemsetAsync(C.at(s_q), 0, 16, ctx->stream));
         HIPCHK(hipMemsetAsync(C.at(s_as), 0xff, s_as.bytes, ctx->stream));            // -1 = not assigned
         if (read_order) { HIPCHK(C.up(s_ord, read_order, 4ull * order_off[n_contigs], ctx->stream)); HIPCHK(C.up(s_oo, order_off, 8ull * (n_contigs + 1), ctx->stream)); }
-        HIPCHK(C.up(s_mu, multi_all.data(), 4ull * multi_all.size(), ctx->stream)); HIPCHK(C.up(s_mo, multi_off_all.data(), 8ull * (n_contigs + 1), ctx->stream));
+        if (!src) { HIPCHK(C.up(s_mu, multi_all.data(), 4ull * multi_all.size(), ctx->stream)); HIPCHK(C.up(s_mo, multi_off_all.data(), 8ull * (n_contigs + 1), ctx->stream)); }
         T.end(th);
         fl::ReassignArgs a{};
         a.contigs = C.at<const fl::ContigDev>(s_cd); a.n_contigs = n_contigs;
@@ -3620,7 +3704,7 @@ struct S2Plan {
             if (A == 2) hipLaunchKernelGGL(fl::reassign_chain_kernel<2>, dim3(grid), dim3(64), 0, ctx->stream, a);
             else hipLaunchKernelGGL(fl::reassign_chain_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
         }
-        ctx->timing.jobs = multi_all.size();                        // reads that had a choice (the sequential part of S2)
+        ctx->timing.jobs = multi_off_all.back();                      // reads that had a choice (the sequential part of S2)
         T.end(tk);
         HIPCHK(hipGetLastError());
         return 0;
@@ -3771,6 +3855,24 @@ int hs_headers(const floria_hip_haplosets* chs) {
     return 0;
 }
 
+// min first / max last of every haploset's reads (get_hapq; the histogram windows of an S2 call that takes the handle as its input), once per handle: 8 B per group come back
+int hs_spans(floria_hip_ctx* ctx, const floria_hip_haplosets* chs) {
+    floria_hip_haplosets* hs = const_cast<floria_hip_haplosets*>(chs);
+    if (hs->have_span) return 0;
+    const uint32_t n_groups = (uint32_t)hs->n_groups;
+    hs->h_lo.assign(n_groups, 0); hs->h_len.assign(n_groups, 0);
+    if (n_groups) {
+        HIPCHK(hipSetDevice(ctx->device));
+        hipLaunchKernelGGL(fl::hs_span_kernel, dim3(items_grid(ctx, n_groups, 4)), dim3(256), 0, ctx->stream, hs->d_cd, (uint32_t)hs->contigs.size(), hs->d_gc, hs->d_go, hs->d_gr, n_groups, hs->d_lo, hs->d_len);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hs->h_lo.data(), hs->d_lo, 4ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(hs->h_len.data(), hs->d_len, 4ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    hs->have_span = true;
+    return 0;
+}
+
 // what every call that takes a handle refuses before anything else
 int hs_check(const floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs, const char* who) {
     if (!ctx || !hs || (n_contigs && !contigs)) return fail(FLORIA_E_INVALID, "null argument");
@@ -3785,6 +3887,27 @@ int hs_check(const floria_hip_ctx* ctx, const floria_hip_contig* const* contigs,
 
 DevGroups hs_dev(const floria_hip_haplosets* hs, bool span) { return DevGroups{span ? (const void*)hs->d_sc : (const void*)hs->d_cd, hs->d_gc, hs->d_go, hs->d_gr, hs->d_rg}; }
 
+// a handle's buffer for NG groups and NR reads: carved, placed, its pointers set and its span table uploaded (`sc` must live until the stream has run); the contig
+// table (cd) and the group arrays are the caller's to fill
+struct HsSegs { Seg cd{}, sc{}, gc{}, go{}, gr{}, rg{}, lo{}, len{}; };
+int hs_place(floria_hip_haplosets* hs, const floria_hip_contig* const* contigs, uint32_t n_contigs, uint64_t NG, uint64_t NR, Carve& H, HsSegs& S, std::vector<fl::SpanContig>& sc) {
+    bool all_pos = true;
+    sc.resize(n_contigs);
+    for (uint32_t i = 0; i < n_contigs; ++i) {
+        const floria_hip_contig* k = contigs[i];
+        if (!k->seq_pos) all_pos = false;
+        sc[i] = fl::SpanContig{k->dev.read_off, k->dev.cell_snp, k->seq_pos, k->n_reads, (uint32_t)k->n_cells};
+    }
+    S.cd = H.seg(sizeof(fl::ContigDev) * n_contigs); S.sc = H.seg(sizeof(fl::SpanContig) * n_contigs); S.gc = H.seg(4 * NG); S.go = H.seg(8 * (NG + 1));
+    S.gr = H.seg(4 * NR + 4); S.rg = H.seg(8 * NG); S.lo = H.seg(4 * NG); S.len = H.seg(4 * NG);
+    if (int rc = H.place(hs->buf)) return rc;
+    if (all_pos) HIPCHK(H.up(S.sc, sc.data(), sizeof(fl::SpanContig) * n_contigs, hs->ctx->stream));
+    hs->d_cd = H.at<const fl::ContigDev>(S.cd); hs->d_sc = all_pos ? H.at<const fl::SpanContig>(S.sc) : nullptr;
+    hs->d_gc = H.at<const uint32_t>(S.gc); hs->d_go = H.at<const uint64_t>(S.go); hs->d_gr = H.at<const uint32_t>(S.gr); hs->d_rg = H.at<const uint32_t>(S.rg);
+    hs->d_lo = H.at<uint32_t>(S.lo); hs->d_len = H.at<uint32_t>(S.len);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3798,11 +3921,6 @@ int floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_con
     *out = nullptr;
     S2Plan P;
     if (int rc = P.prologue(ctx, contigs, n_contigs, grp_contig, grp_off, grp_read, n_groups, read_order, order_off)) return rc;
-    std::unique_ptr<floria_hip_haplosets> hs(new (std::nothrow) floria_hip_haplosets);
-    if (!hs) return fail(FLORIA_E_NOMEM, "new");
-    hs->ctx = ctx; hs->contigs.assign(contigs, contigs + n_contigs); hs->A = P.A;
-    hs->c_groups.assign(n_contigs, 0); hs->c_reads.assign(n_contigs, 0);
-    if (n_groups == 0) { *out = hs.release(); return 0; }
     // the input groups contig-major, as the prologue numbers them
     const uint32_t n_in = n_groups;
     std::vector<uint64_t> gb(n_contigs + 1, 0);
@@ -3814,6 +3932,37 @@ int floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_con
             in_contig[k] = ci; in_range[2 * k] = grp_range[2 * g]; in_range[2 * k + 1] = grp_range[2 * g + 1];
         }
     }
+    return s2_resident_core(ctx, contigs, n_contigs, P, gb, in_contig, in_range, read_order, order_off, epsilon, out);
+}
+
+int floria_hip_reassign_haplosets_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* in, double epsilon,
+                                           floria_hip_haplosets** out) {
+    if (!out) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = hs_check(ctx, contigs, n_contigs, in, "reassign_haplosets_resident")) return rc;
+    if (in->n_groups >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "reassign_haplosets_resident: 2^32 and more haplosets in one call");
+    S2Plan P;
+    if (int rc = P.prologue_handle(ctx, contigs, n_contigs, in)) return rc;
+    std::vector<uint64_t> gb(n_contigs + 1, 0);
+    for (uint32_t ci = 0; ci < n_contigs; ++ci) gb[ci + 1] = gb[ci] + in->c_groups[ci];
+    return s2_resident_core(ctx, contigs, n_contigs, P, gb, in->h_gc, in->h_range, nullptr, nullptr, epsilon, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// S2 behind its prologue, for both entries: the re-insertion (S2Plan::run) and the epilogue on the device.  The input groups are numbered contig-major (gb: the first
+// group of every contig; in_contig, in_range per group); their id windows are the plan's (from the lists) or computed from the plan's source handle.
+int s2_resident_core(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, S2Plan& P, const std::vector<uint64_t>& gb,
+                     const std::vector<uint32_t>& in_contig, const std::vector<uint32_t>& in_range, const uint32_t* read_order, const uint64_t* order_off, double epsilon,
+                     floria_hip_haplosets** out) {
+    const uint32_t n_in = (uint32_t)in_contig.size(), n_groups = n_in;
+    std::unique_ptr<floria_hip_haplosets> hs(new (std::nothrow) floria_hip_haplosets);
+    if (!hs) return fail(FLORIA_E_NOMEM, "new");
+    hs->ctx = ctx; hs->contigs.assign(contigs, contigs + n_contigs); hs->A = P.A;
+    hs->c_groups.assign(n_contigs, 0); hs->c_reads.assign(n_contigs, 0);
+    if (n_groups == 0) { *out = hs.release(); return 0; }
     Carve C;
     P.carve(C, n_contigs, read_order, order_off);
     const uint32_t tiles_in = (n_in + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
@@ -3827,9 +3976,10 @@ int floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_con
     }
     int th = T.begin(K_H2D);
     HIPCHK(C.up(s_gb2, gb.data(), 8ull * (n_contigs + 1), ctx->stream)); HIPCHK(C.up(s_ic, in_contig.data(), 4ull * n_in, ctx->stream));
-    HIPCHK(C.up(s_ir, in_range.data(), 8ull * n_in, ctx->stream)); HIPCHK(C.up(s_rl, P.rid_lo.data(), 4ull * n_in, ctx->stream));
-    HIPCHK(C.up(s_rh, P.rid_hi.data(), 4ull * n_in, ctx->stream));
+    HIPCHK(C.up(s_ir, in_range.data(), 8ull * n_in, ctx->stream));
+    if (!P.src) { HIPCHK(C.up(s_rl, P.rid_lo.data(), 4ull * n_in, ctx->stream)); HIPCHK(C.up(s_rh, P.rid_hi.data(), 4ull * n_in, ctx->stream)); }
     T.end(th);
+    if (P.src) hipLaunchKernelGGL(fl::hp_rid_kernel, dim3(items_grid(ctx, n_in, 256)), dim3(256), 0, ctx->stream, P.src->d_go, P.src->d_gr, n_in, P.src->n_reads, C.at<uint32_t>(s_rl), C.at<uint32_t>(s_rh));
     fl::HsArgs a{};
     a.contigs = C.at<const fl::ContigDev>(P.s_cd); a.assign = C.at<const int32_t>(P.s_as); a.assign_base = C.at<const uint64_t>(P.s_ab);
     a.grp_base = C.at<const uint64_t>(s_gb2); a.in_contig = C.at<const uint32_t>(s_ic); a.in_range = C.at<const uint32_t>(s_ir);
@@ -3853,28 +4003,16 @@ int floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_con
     if (NG < n_in || NR > P.n_assign) return fail(FLORIA_E_DEVICE, "reassign_batch_resident: the device's group counts are inconsistent");
     if (NG >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "reassign_batch_resident: 2^32 and more haplosets in one call");
     hs->n_groups = NG; hs->n_reads = NR;
-    bool all_pos = true;
-    std::vector<fl::SpanContig> sc(n_contigs);
-    for (uint32_t i = 0; i < n_contigs; ++i) {
-        const floria_hip_contig* k = contigs[i];
-        if (!k->seq_pos) all_pos = false;
-        sc[i] = fl::SpanContig{k->dev.read_off, k->dev.cell_snp, k->seq_pos, k->n_reads, (uint32_t)k->n_cells};
-    }
     Carve H;                                           // the handle's own buffer
-    const Seg h_cd = H.seg(sizeof(fl::ContigDev) * n_contigs), h_sc = H.seg(sizeof(fl::SpanContig) * n_contigs), h_gc = H.seg(4 * NG), h_go = H.seg(8 * (NG + 1)),
-              h_gr = H.seg(4 * NR + 4), h_rg = H.seg(8 * NG), h_lo = H.seg(4 * NG), h_len = H.seg(4 * NG);
-    rc = H.place(hs->buf); if (rc) return rc;
+    HsSegs hseg; std::vector<fl::SpanContig> sc;
+    rc = hs_place(hs.get(), contigs, n_contigs, NG, NR, H, hseg, sc); if (rc) return rc;
     Carve S;                                           // the slot tables between the kernels
     const uint32_t tiles_out = (uint32_t)((NG + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE);
     const Seg s_sa = S.seg(4 * NG), s_sb = S.seg(4 * NG), s_sr = S.seg(8 * NG), s_sd = S.seg(4 * NG), s_to = S.seg(8ull * tiles_out + 8);
     rc = S.place(ctx->hs_tmp); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(H.at(h_cd), C.at(P.s_cd), sizeof(fl::ContigDev) * n_contigs, hipMemcpyDeviceToDevice, ctx->stream));
-    if (all_pos) HIPCHK(H.up(h_sc, sc.data(), sizeof(fl::SpanContig) * n_contigs, ctx->stream));
-    hs->d_cd = H.at<const fl::ContigDev>(h_cd); hs->d_sc = all_pos ? H.at<const fl::SpanContig>(h_sc) : nullptr;
-    hs->d_gc = H.at<const uint32_t>(h_gc); hs->d_go = H.at<const uint64_t>(h_go); hs->d_gr = H.at<const uint32_t>(h_gr); hs->d_rg = H.at<const uint32_t>(h_rg);
-    hs->d_lo = H.at<uint32_t>(h_lo); hs->d_len = H.at<uint32_t>(h_len);
+    HIPCHK(hipMemcpyAsync(H.at(hseg.cd), C.at(P.s_cd), sizeof(fl::ContigDev) * n_contigs, hipMemcpyDeviceToDevice, ctx->stream));
     a.slot_a = S.at<uint32_t>(s_sa); a.slot_b = S.at<uint32_t>(s_sb); a.slot_range = S.at<uint32_t>(s_sr); a.slot_dst = S.at<uint32_t>(s_sd);
-    a.grp_contig = H.at<uint32_t>(h_gc); a.grp_off = H.at<uint64_t>(h_go); a.grp_read = H.at<uint32_t>(h_gr); a.range = H.at<uint32_t>(h_rg);
+    a.grp_contig = H.at<uint32_t>(hseg.gc); a.grp_off = H.at<uint64_t>(hseg.go); a.grp_read = H.at<uint32_t>(hseg.gr); a.range = H.at<uint32_t>(hseg.rg);
     a.n_out = NG; a.n_reads_out = NR;
     tk = T.begin(K_SEL);
     hipLaunchKernelGGL(fl::hs_slots_kernel, dim3(grid_in), dim3(256), 0, ctx->stream, a);
@@ -3888,6 +4026,10 @@ int floria_hip_reassign_batch_resident(floria_hip_ctx* ctx, const floria_hip_con
     *out = hs.release();
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
 
 void floria_hip_haplosets_free(floria_hip_haplosets* hs) {
     if (!hs) return;
@@ -3964,17 +4106,127 @@ int floria_hip_hapq_batch_resident(floria_hip_ctx* ctx, const floria_hip_contig*
     if (int rc = hs_headers(hs)) return rc;
     std::vector<double> st(4ull * n_groups);
     if (int rc = stats_core(ctx, hs->A, hs->h_range.data(), n_groups, nullptr, hs_dev(hs, false), st.data())) return rc;
-    if (!hs->have_span) {                              // min first / max last of every haploset's reads, once per handle: 8 B per group come back
-        hs->h_lo.assign(n_groups, 0); hs->h_len.assign(n_groups, 0);
-        hipLaunchKernelGGL(fl::hs_span_kernel, dim3(items_grid(ctx, n_groups, 4)), dim3(256), 0, ctx->stream, hs->d_cd, n_contigs, hs->d_gc, hs->d_go, hs->d_gr, n_groups, hs->d_lo, hs->d_len);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hs->h_lo.data(), hs->d_lo, 4ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(hs->h_len.data(), hs->d_len, 4ull * n_groups, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        hs->have_span = true;
-    }
+    if (int rc = hs_spans(ctx, hs)) return rc;
     return hapq_core(ctx, contigs, n_contigs, hs->h_gc, hs->h_off.data(), hs->h_range.data(), n_groups, st, hs->h_lo, hs->h_len, snp_to_genome_pos, n_snps, block_length,
                      nullptr, hs_dev(hs, false), hapq, rel_err, avg_err);
+}
+
+// ---- hap-graph paths -> haplosets on the resident S1 batch (path_kernel.h) -----------------------------------------------------------------------------------------
+int floria_hip_join_paths(floria_hip_ctx* ctx, const floria_block_result* res, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                          const uint32_t* path_contig, const uint64_t* node_off, const uint32_t* node_block, const uint8_t* node_part,
+                          const uint32_t* path_range, uint32_t n_paths, floria_hip_haplosets** out) {
+    if (!ctx) return fail(FLORIA_E_INVALID, "join_paths: null argument (ctx)");
+    if (!res) return fail(FLORIA_E_INVALID, "join_paths: null argument (res)");
+    if (!out) return fail(FLORIA_E_INVALID, "join_paths: null argument (out)");
+    *out = nullptr;
+    if (n_contigs && !contigs) return fail(FLORIA_E_INVALID, "join_paths: null argument (contigs)");
+    if (!node_off) return fail(FLORIA_E_INVALID, "join_paths: null argument (node_off)");
+    if (n_paths && !path_contig) return fail(FLORIA_E_INVALID, "join_paths: null argument (path_contig)");
+    if (n_paths && !path_range) return fail(FLORIA_E_INVALID, "join_paths: null argument (path_range)");
+    if (!ctx->batch_token || res->batch_token != ctx->batch_token) return fail(FLORIA_E_INVALID, "the batch is no longer resident: call floria_hip_hap_graph directly after phase_blocks");
+    const uint32_t nb = (uint32_t)ctx->last_bc.size();
+    if (res->n_blocks != nb || (nb && !res->best_ploidy)) return fail(FLORIA_E_INVALID, "join_paths: res is not the result of the resident batch");
+    for (uint32_t i = 0; i < n_contigs; ++i) {
+        if (!contigs[i]) return fail(FLORIA_E_INVALID, "join_paths: null argument (contigs[" + std::to_string(i) + "])");
+        if (contigs[i]->ctx != ctx) return fail(FLORIA_E_INVALID, "join_paths: contig " + std::to_string(i) + " belongs to another context");
+    }
+    if (n_contigs != ctx->last_contigs.size()) return fail(FLORIA_E_INVALID, "join_paths: contigs: " + std::to_string(n_contigs) + " given, the S1 call had " + std::to_string(ctx->last_contigs.size()));
+    for (uint32_t i = 0; i < n_contigs; ++i)
+        if (contigs[i] != ctx->last_contigs[i]) return fail(FLORIA_E_INVALID, "join_paths: contigs[" + std::to_string(i) + "] is not the S1 call's");
+    if (node_off[0] != 0) return fail(FLORIA_E_INVALID, "join_paths: node_off does not start at 0");
+    for (uint32_t p = 0; p < n_paths; ++p) {
+        if (path_contig[p] >= n_contigs) return fail(FLORIA_E_INVALID, "join_paths: path_contig[" + std::to_string(p) + "] out of range");
+        if (p && path_contig[p] < path_contig[p - 1]) return fail(FLORIA_E_INVALID, "join_paths: path_contig descends at path " + std::to_string(p));
+        if (node_off[p + 1] < node_off[p]) return fail(FLORIA_E_INVALID, "join_paths: node_off descends at path " + std::to_string(p));
+    }
+    const uint64_t n_nodes = node_off[n_paths];
+    if (n_nodes >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "join_paths: 2^32 and more nodes in one call");
+    if (n_nodes && !node_block) return fail(FLORIA_E_INVALID, "join_paths: null argument (node_block)");
+    if (n_nodes && !node_part) return fail(FLORIA_E_INVALID, "join_paths: null argument (node_part)");
+    std::vector<uint32_t> node_path(n_nodes);
+    for (uint32_t p = 0; p < n_paths; ++p)
+        for (uint64_t n = node_off[p]; n < node_off[p + 1]; ++n) {
+            const uint32_t b = node_block[n];
+            if (b >= nb) return fail(FLORIA_E_INVALID, "join_paths: node_block[" + std::to_string(n) + "] out of range");
+            if (node_part[n] >= res->best_ploidy[b]) return fail(FLORIA_E_INVALID, "join_paths: node_part[" + std::to_string(n) + "] is not below the best ploidy of block " + std::to_string(b));
+            if (ctx->last_bc[b] != path_contig[p]) return fail(FLORIA_E_INVALID, "join_paths: node_block[" + std::to_string(n) + "] belongs to another contig than path " + std::to_string(p));
+            node_path[n] = p;
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->timing = floria_timing{};
+    std::unique_ptr<floria_hip_haplosets> hs(new (std::nothrow) floria_hip_haplosets);
+    if (!hs) return fail(FLORIA_E_NOMEM, "new");
+    hs->ctx = ctx; hs->contigs.assign(contigs, contigs + n_contigs);
+    hs->c_groups.assign(n_contigs, 0); hs->c_reads.assign(n_contigs, 0);
+    std::vector<fl::ContigDev> cdev(n_contigs);
+    for (uint32_t i = 0; i < n_contigs; ++i) { hs->A = std::max(hs->A, contigs[i]->n_alleles); cdev[i] = contigs[i]->dev; }
+    if (n_paths == 0) { *out = hs.release(); return 0; }
+    std::vector<uint64_t> pb(n_contigs + 1, 0);
+    for (uint32_t p = 0; p < n_paths; ++p) pb[path_contig[p] + 1]++;
+    for (uint32_t ci = 0; ci < n_contigs; ++ci) pb[ci + 1] += pb[ci];
+    Carve C;                                           // the path tables (the S1 batch lies in misc / misc0 and stays)
+    const uint32_t tiles = (n_paths + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+    const Seg s_no = C.seg(8ull * (n_paths + 1)), s_nb = C.seg(4 * n_nodes + 4), s_np = C.seg(n_nodes + 4), s_npa = C.seg(4 * n_nodes + 4), s_pb = C.seg(8ull * (n_contigs + 1)),
+              s_wl = C.seg(4ull * n_paths), s_wo = C.seg(8ull * (n_paths + 1)), s_go = C.seg(8ull * (n_paths + 1)), s_ti = C.seg(8ull * tiles + 8), s_cnt = C.seg(16ull * n_contigs);
+    int rc = C.place(ctx->hs_tmp); if (rc) return rc;
+    EventTimer T(ctx->stream);
+    int th = T.begin(K_H2D);
+    HIPCHK(C.up(s_no, node_off, 8ull * (n_paths + 1), ctx->stream)); HIPCHK(C.up(s_nb, node_block, 4 * n_nodes, ctx->stream)); HIPCHK(C.up(s_np, node_part, n_nodes, ctx->stream));
+    HIPCHK(C.up(s_npa, node_path.data(), 4 * n_nodes, ctx->stream)); HIPCHK(C.up(s_pb, pb.data(), 8ull * (n_contigs + 1), ctx->stream));
+    T.end(th);
+    fl::PathArgs a{};
+    a.bs = ctx->last_bs; a.part = ctx->last_part;
+    a.node_off = C.at<const uint64_t>(s_no); a.node_block = C.at<const uint32_t>(s_nb); a.node_part = C.at<const uint8_t>(s_np); a.node_path = C.at<const uint32_t>(s_npa);
+    a.path_base = C.at<const uint64_t>(s_pb); a.win_lo = C.at<uint32_t>(s_wl); a.word_off = C.at<uint64_t>(s_wo); a.grp_off = C.at<uint64_t>(s_go); a.counts = C.at<uint64_t>(s_cnt);
+    a.n_nodes = n_nodes; a.n_paths = n_paths; a.n_contigs = n_contigs;
+    const uint32_t grid_p = items_grid(ctx, n_paths, 4);
+    int tk = T.begin(K_SEL);
+    hipLaunchKernelGGL(fl::path_window_kernel, dim3(grid_p), dim3(256), 0, ctx->stream, a);
+    launch_offset_scan(ctx, a.word_off, C.at<uint64_t>(s_ti), n_paths);
+    T.end(tk);
+    HIPCHK(hipGetLastError());
+    uint64_t n_words = 0;                              // the bitmap's size: 8 B come back before it can be placed
+    int td = T.begin(K_D2H);
+    HIPCHK(hipMemcpyAsync(&n_words, a.word_off + n_paths, 8, hipMemcpyDeviceToHost, ctx->stream));
+    T.end(td);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (n_words > ((uint64_t)n_paths << 26)) return fail(FLORIA_E_DEVICE, "join_paths: the device's window sizes are inconsistent");
+    rc = ctx->join_bits.ensure(8 * n_words + 8); if (rc) return rc;
+    a.bitmap = ctx->join_bits.as<uint64_t>(); a.n_words = n_words;
+    HIPCHK(hipMemsetAsync(a.bitmap, 0, 8 * n_words + 8, ctx->stream));
+    tk = T.begin(K_SEL);
+    if (n_nodes) hipLaunchKernelGGL(fl::path_mark_kernel, dim3(items_grid(ctx, n_nodes, 4)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(fl::path_count_kernel, dim3(grid_p), dim3(256), 0, ctx->stream, a);
+    launch_offset_scan(ctx, a.grp_off, C.at<uint64_t>(s_ti), n_paths);
+    hipLaunchKernelGGL(fl::path_contig_counts_kernel, dim3(items_grid(ctx, n_contigs, 256)), dim3(256), 0, ctx->stream, a);
+    T.end(tk);
+    HIPCHK(hipGetLastError());
+    std::vector<uint64_t> counts(2ull * n_contigs);
+    td = T.begin(K_D2H);
+    HIPCHK(hipMemcpyAsync(counts.data(), a.counts, 16ull * n_contigs, hipMemcpyDeviceToHost, ctx->stream));      // two words per contig, as in S2's epilogue
+    T.end(td);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    uint64_t NG = 0, NR = 0;
+    for (uint32_t ci = 0; ci < n_contigs; ++ci) { hs->c_groups[ci] = counts[2 * ci]; hs->c_reads[ci] = counts[2 * ci + 1]; NG += counts[2 * ci]; NR += counts[2 * ci + 1]; }
+    if (NG != n_paths || NR > 64 * n_words) return fail(FLORIA_E_DEVICE, "join_paths: the device's group counts are inconsistent");
+    hs->n_groups = NG; hs->n_reads = NR;
+    Carve H;
+    HsSegs hseg; std::vector<fl::SpanContig> sc;
+    rc = hs_place(hs.get(), contigs, n_contigs, NG, NR, H, hseg, sc); if (rc) return rc;
+    th = T.begin(K_H2D);
+    HIPCHK(H.up(hseg.cd, cdev.data(), sizeof(fl::ContigDev) * n_contigs, ctx->stream)); HIPCHK(H.up(hseg.gc, path_contig, 4ull * n_paths, ctx->stream));
+    HIPCHK(H.up(hseg.rg, path_range, 8ull * n_paths, ctx->stream));
+    T.end(th);
+    HIPCHK(hipMemcpyAsync(H.at(hseg.go), a.grp_off, 8ull * (n_paths + 1), hipMemcpyDeviceToDevice, ctx->stream));
+    a.grp_read = H.at<uint32_t>(hseg.gr); a.n_reads_out = NR;
+    tk = T.begin(K_SEL);
+    hipLaunchKernelGGL(fl::path_fill_kernel, dim3(grid_p), dim3(256), 0, ctx->stream, a);
+    T.end(tk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    T.publish(ctx->timing);
+    *out = hs.release();
+    return 0;
 }
 
 }  // extern "C"

@@ -193,4 +193,83 @@ __global__ __launch_bounds__(256) void hs_span_kernel(const ContigDev* contigs, 
     }
 }
 
+// ---- S2's input tables from a handle (floria_hip_reassign_haplosets_resident): what S2Plan::prologue builds on the host from group lists, built here from the
+// handle's grp_contig / grp_off / grp_read.  Reads are numbered over all contigs: slot x = ro_base[ci] + r with ro_base[ci] = (reads of the contigs before ci) + ci, so
+// every contig owns n_reads + 1 consecutive slots and the last one counts nothing: ONE exclusive scan over all slots then holds, for every contig, the n_reads + 1
+// offsets of its read -> groups lists (absolute into r2g: the kernels' r2g_base is 0).
+//   COUNT   a wavefront per group: ro[slot of the read] += 1 (integer atomicAdd: a count does not depend on the order);
+//   FLAG    mf[x] = the read has a choice (count > 1); both arrays are then scanned (pileup_scan_*);
+//   PLACE   a wavefront per group: the group's local id goes to its reads' lists at a cursor taken by atomicAdd, so a list holds the right SET in some order;
+//   SORT    a thread per read: insertion sort of its list (a read has a handful of candidates) — ascending local group id, as the host's counting sort leaves it,
+//           whatever order PLACE wrote in; the same thread writes the read into `multi` at the rank the scan of FLAG gave it: ascending visiting index;
+//   RID     (hp_rid_kernel) a thread per group: the id window [first entry, last entry + 1) of its ascending list.
+struct HpArgs {
+    const ContigDev* contigs;
+    const uint32_t*  grp_contig;    // the handle's arrays
+    const uint64_t*  grp_off;
+    const uint32_t*  grp_read;
+    const uint64_t*  grp_base;      // [n_contigs] first group of contig ci
+    const uint64_t*  ro_base;       // [n_contigs] first slot of contig ci
+    uint64_t*        ro;            // [n_slots + 1] COUNT, then scanned in place
+    uint64_t*        mf;            // [n_slots + 1] FLAG, then scanned in place
+    uint32_t*        cursor;        // [n_slots - n_contigs] one per read, zeroed
+    uint32_t*        r2g;           // [n_entries]
+    uint32_t*        multi;         // [n_multi_cap]
+    uint64_t*        multi_off;     // [n_contigs + 1]
+    uint64_t         n_slots, n_entries, n_multi_cap;
+    uint32_t         n_groups, n_contigs;
+};
+
+template <bool PLACE> __global__ __launch_bounds__(256) void hp_groups_kernel(HpArgs g) {
+    const uint32_t lane = threadIdx.x & 63, nw = gridDim.x * 4;
+    for (uint64_t k = blockIdx.x * 4 + (threadIdx.x >> 6); k < g.n_groups; k += nw) {
+        const uint32_t ci = g.grp_contig[k];
+        if (ci >= g.n_contigs) continue;
+        const uint32_t N = g.contigs[ci].n_reads, lg = (uint32_t)(k - g.grp_base[ci]);
+        const uint64_t base = g.ro_base[ci], i1 = g.grp_off[k + 1] < g.n_entries ? g.grp_off[k + 1] : g.n_entries;
+        for (uint64_t i = g.grp_off[k] + lane; i < i1; i += 64) {
+            const uint32_t r = g.grp_read[i];
+            if (r >= N || base + r >= g.n_slots) continue;
+            if (!PLACE) atomicAdd((unsigned long long*)&g.ro[base + r], 1ull);
+            else {
+                const uint64_t at = g.ro[base + r] + atomicAdd(&g.cursor[base - ci + r], 1u);      // (base - ci: the contig's first read among all reads)
+                if (at < g.ro[base + r + 1] && at < g.n_entries) g.r2g[at] = lg;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void hp_flag_kernel(HpArgs g) {
+    for (uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x; x < g.n_slots; x += (uint64_t)gridDim.x * 256) g.mf[x] = g.ro[x] > 1 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void hp_sort_kernel(HpArgs g) {
+    for (uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x; x < g.n_slots; x += (uint64_t)gridDim.x * 256) {
+        const uint64_t a = g.ro[x], b = g.ro[x + 1] < g.n_entries ? g.ro[x + 1] : g.n_entries;
+        for (uint64_t i = a + 1; i < b; ++i) {
+            const uint32_t v = g.r2g[i];
+            uint64_t j = i;
+            for (; j > a && g.r2g[j - 1] > v; --j) g.r2g[j] = g.r2g[j - 1];
+            g.r2g[j] = v;
+        }
+        if (g.mf[x + 1] > g.mf[x] && g.mf[x] < g.n_multi_cap) {
+            uint32_t lo = 0, hi = g.n_contigs;                  // the slot's contig: the last ci with ro_base[ci] <= x
+            while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (g.ro_base[mid] <= x) lo = mid; else hi = mid; }
+            g.multi[g.mf[x]] = (uint32_t)(x - g.ro_base[lo]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void hp_multi_off_kernel(HpArgs g) {
+    for (uint64_t ci = (uint64_t)blockIdx.x * 256 + threadIdx.x; ci <= g.n_contigs; ci += (uint64_t)gridDim.x * 256) g.multi_off[ci] = ci < g.n_contigs ? g.mf[g.ro_base[ci]] : g.mf[g.n_slots];
+}
+
+__global__ __launch_bounds__(256) void hp_rid_kernel(const uint64_t* grp_off, const uint32_t* grp_read, uint32_t n_groups, uint64_t n_entries, uint32_t* rid_lo, uint32_t* rid_hi) {
+    for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < n_groups; k += (uint64_t)gridDim.x * 256) {
+        const uint64_t a = grp_off[k], b = grp_off[k + 1] < n_entries ? grp_off[k + 1] : n_entries;
+        rid_lo[k] = b > a ? grp_read[a] : 0;
+        rid_hi[k] = b > a ? grp_read[b - 1] + 1 : 0;
+    }
+}
+
 }  // namespace fl

@@ -38,6 +38,10 @@ void usage() {
           "  --haplosets host|resident   where the haplosets live between S2 and the writers: host [default] = S2 returns the group lists and the four calls behind it\n"
           "                    (COV / ERR, HAPQ, allele tables, read trims) take them up again; resident = S2 splits and sorts on the device and keeps the haplosets there\n"
           "                    (floria_hip_reassign_batch_resident), the lists come back once for the writers and the four calls take the handle.  Any --pileup route.  Same files\n"
+          "  --paths host|resident   where the reads of a hap-graph path are united: host [default] = S1 returns every block's read list, the nodes hold their reads and the\n"
+          "                    path peeling unites them; resident = the peeling returns node lists, floria_hip_join_paths unites the reads on the S1 batch that is still on the\n"
+          "                    device and S2 takes that handle (floria_hip_reassign_haplosets_resident): no read list comes down (unless --debug) or goes up.  Implies\n"
+          "                    --haplosets resident.  Any --pileup route.  Same files\n"
           "  --realign exact | block:STEP,RULE,TIE   how that re-alignment scores a window: exact [default] = the exact affine-gap alignment; block:... = a walk of a fixed\n"
           "                 8 x 8 block over the alignment matrix, shifted by STEP = 1 | 2 | 4 | 8 cells towards the larger border by RULE = max | sum, ties going\n"
           "                 TIE = right | down (e.g. block:8,max,right).  floria's block-aligner is a heuristic of this kind; which member is unknown, so one must be named\n"
@@ -148,6 +152,12 @@ Cli parse_args(int argc, char** argv) {
             if (v != "host" && v != "resident") throw Error(FLORIA_E_INVALID, "--haplosets takes host or resident, not '" + v + "'");
             o.haplosets_resident = v == "resident";
         }
+        else if (a == "--paths") {
+            const std::string v = val();
+            if (v != "host" && v != "resident") throw Error(FLORIA_E_INVALID, "--paths takes host or resident, not '" + v + "'");
+            o.paths_resident = v == "resident";
+        }
+        else if (a == "--stitch-paths") cli.stitch_paths = true;      // (tests, with --stitch-graph) also one Q line per path: its nodes
         else if (a == "--dump-plan") cli.dump_plan = val();            // (tests, with --ingest-only) the fragment plan of every contig: needs no GPU under --pileup host
         else if (a == "--dump-handles") cli.dump_handles = val();      // (tests) the resident arrays of every contig of every batch, whichever route made the handle
         else if (a == "--ingest-only") cli.ingest_only = true;          // (tests) stop after ingest: needs no GPU
@@ -161,6 +171,7 @@ Cli parse_args(int argc, char** argv) {
             throw Error(FLORIA_E_UNSUPPORTED, "option " + a + " of floria is not supported by floria-hip");
         else throw Error(FLORIA_E_INVALID, "unknown option " + a);
     }
+    if (o.paths_resident) { o.haplosets_resident = true; o.paths_keep_lists = cli.debug; }
     return cli;
 }
 
@@ -211,12 +222,19 @@ void stitch_graph_tool(const Cli& cli) {
     for (const EdgeIn& e : edges) { hg[e.c][e.r].out_edges.push_back({e.r2, e.w}); hg[e.c + 1][e.r2].in_edges.push_back({e.r, e.w}); }
     LpInfo li;
     const FlowUpVec fl = solve_lp_graph(hg, cli.lp_tie, &li);
-    auto paths = get_disjoint_paths_rewrite(hg, fl, cli.o);
+    const std::vector<PeeledPath> peeled = peel_disjoint_paths(hg, fl, cli.o);
+    auto paths = unite_paths(hg, peeled);
     printf("U\t%lld\t%zu\n", (long long)li.cost, li.movable_edges);
     for (const FlowUpdate& f : fl) printf("F\t%zu\t%zu\t%zu\t%.17g\n", f.n1.first, f.n1.second, f.n2.second, f.flow);
     for (size_t k = 0; k < paths.first.size(); ++k) {
         printf("P\t%u\t%u", paths.second[k].first, paths.second[k].second);
         for (const Frag* f : paths.first[k]) printf("\t%zu", f->counter_id);
+        printf("\n");
+    }
+    if (cli.stitch_paths)                                              // path k's range and its nodes (column:row), sink first
+    for (const PeeledPath& p : peeled) {
+        printf("Q\t%u\t%u", p.ends.first, p.ends.second);
+        for (const auto& cr : p.nodes) printf("\t%zu:%zu", cr.first, cr.second);
         printf("\n");
     }
 }

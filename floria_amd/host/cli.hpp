@@ -15,6 +15,7 @@ struct Cli {
     uint64_t batch_cells = 256ull << 20; // --batch-cells (1.5 GB of pinned staging)
     bool ingest_only = false, no_realign = false, have_realign = false;
     std::string stitch_graph;
+    bool stitch_paths = false;
     LpTie lp_tie = LpTie::First;         // --lp-tie first|last: which optimal vertex of the stitching LP is used where the optimum is not unique (stitch.cpp)
     bool lp_report = false;              // --lp-report (implied by --debug): count the edges whose flow differs in another optimal solution of the stitching LP
     bool debug = false;                  // --debug / --trace: per contig, debug_graph.txt (hap graph, LP flows, joined paths) next to the outputs
@@ -31,7 +32,7 @@ struct Cli {
 Cli parse_args(int argc, char** argv);
 // the refusals that need more than one option, before anything is read
 void validate(const Cli& cli);
-// (tests) --stitch-graph FILE: N / E lines of a hap graph -> U / F / P lines on stdout
+// (tests) --stitch-graph FILE: N / E lines of a hap graph -> U / F / P lines on stdout; with --stitch-paths also Q lines: every path's nodes
 void stitch_graph_tool(const Cli& cli);
 
 }  // namespace floria

@@ -58,7 +58,8 @@ std::vector<std::pair<SnpPosition, SnpPosition>> get_range_with_lengths(const st
 
 namespace {
 // process_chunks (graph_processing.rs:306-323) + update_hap_graph's edge lists (:22-100) for the blocks [b0, b1) of one contig out of a batch
-// result: columns = blocks that returned Some, in block order; ids run over the contig's nodes; edges with weight >= MIN_SHARED_READS_UNAMBIG (:51)
+// result: columns = blocks that returned Some, in block order; ids run over the contig's nodes; edges with weight >= MIN_SHARED_READS_UNAMBIG (:51).
+// A result without read lists ("s1_no_lists": --paths resident) leaves every frag_set empty: the reads of a path are then united on the device.
 std::vector<std::vector<HapNode>> build_columns(const floria_block_result* res, const floria_hap_graph* hg, uint32_t b0, uint32_t b1, const std::vector<Frag>& all_frags,
                                                 const std::vector<std::pair<SnpPosition, SnpPosition>>& iter_vec) {
     std::vector<std::vector<HapNode>> cols;
@@ -68,9 +69,10 @@ std::vector<std::vector<HapNode>> build_columns(const floria_block_result* res, 
         const uint32_t p = res->best_ploidy[b];
         if (p == 0) continue;
         std::vector<HapNode> col(p);
+        if (res->read_id && res->part)
         for (uint64_t i = res->read_off[b]; i < res->read_off[b + 1]; ++i) col[res->part[i]].frag_set.push_back(&all_frags[res->read_id[i]]);
         for (uint32_t k = 0; k < p; ++k) {
-            col[k].row = k; col[k].column = cols.size(); col[k].id = id_counter++;
+            col[k].row = k; col[k].column = cols.size(); col[k].id = id_counter++; col[k].block = b;
             col[k].snp_endpoints = iter_vec[b - b0];
             col[k].cov = hg->node_cov[hg->node_off[b] + k];
         }
@@ -348,6 +350,7 @@ Batch::Batch(Session& s, std::vector<ContigWork>& work, bool with_set_orders) : 
 }
 Batch::~Batch() {
     if (haplosets_) floria_hip_haplosets_free(haplosets_);
+    if (res_) floria_hip_block_result_free(res_);
     for (size_t i = 0; i < handles_.size(); ++i) if (handles_[i] && owned_[i]) floria_hip_contig_free(handles_[i]);
     if (pinned_) floria_hip_host_free(pinned_);
 }
@@ -363,6 +366,9 @@ void Batch::generate_hap_graphs(const Options& o) {
     b0.push_back((uint32_t)bs.size());
     floria_params prm{o.epsilon, (uint32_t)o.max_ploidy, (uint32_t)o.max_number_solns, o.ploidy_sensitivity, o.stopping_heuristic ? 1 : 0};
     floria_block_result* res = nullptr;
+    // --paths resident: the read lists stay on the device (the join reads them there); the option is the call's alone
+    struct NoLists { floria_hip_ctx* c; bool on; NoLists(floria_hip_ctx* x, bool o) : c(x), on(o) { if (on) check(floria_hip_set_option(c, "s1_no_lists", 1)); }
+                     ~NoLists() { if (on) (void)floria_hip_set_option(c, "s1_no_lists", 0); } } no_lists(s_.ctx(), o.paths_resident && !o.paths_keep_lists);
     if (host_ix_.size() == work_.size()) {                                     // no contig came with a handle: upload + S1 as one pipelined call
         check(floria_hip_phase_pileups_batch_packed(s_.ctx(), piles_.data(), (uint32_t)piles_.size(), bc.data(), bs.data(), be.data(), (uint32_t)bs.size(), &prm, &res, handles_.data()));
         owned_.assign(work_.size(), 1);
@@ -380,7 +386,8 @@ void Batch::generate_hap_graphs(const Options& o) {
     if (rc) { floria_hip_block_result_free(res); check(rc); }
     for (size_t i = 0; i < work_.size(); ++i) work_[i].hap_graph = build_columns(res, hg, b0[i], b0[i + 1], work_[i].all_frags, work_[i].iter_vec);
     floria_hip_hap_graph_free(hg);
-    floria_hip_block_result_free(res);
+    if (o.paths_resident) { if (res_) floria_hip_block_result_free(res_); res_ = res; }      // (the join needs its token and ploidies)
+    else floria_hip_block_result_free(res);
 }
 
 namespace {
@@ -402,8 +409,28 @@ GroupCsr groups_of(const std::vector<ContigWork>& work, bool final_parts) {
 
 void Batch::process_reads_for_final_parts(const Options& o) {
     if (o.reassign_short) throw Error(FLORIA_E_UNSUPPORTED, "--reassign-short (hidden flag) is not supported");
-    const GroupCsr g = groups_of(work_, false);
     floria_groups** out = nullptr;
+    if (o.paths_resident) {                                                    // the paths as node lists: one join and one S2 call, no read id goes up
+        if (!res_) throw Error(FLORIA_E_INVALID, "--paths resident: no S1 batch to join the paths on");
+        std::vector<uint32_t> pc, nb, rng;
+        std::vector<uint8_t> np;
+        std::vector<uint64_t> no{0};
+        for (size_t i = 0; i < work_.size(); ++i)
+            for (const PeeledPath& p : work_[i].path_nodes) {
+                for (const auto& cr : p.nodes) { nb.push_back(work_[i].hap_graph[cr.first][cr.second].block); np.push_back((uint8_t)cr.second); }
+                pc.push_back((uint32_t)i); no.push_back(nb.size()); rng.push_back(p.ends.first); rng.push_back(p.ends.second);
+            }
+        floria_hip_haplosets* joined = nullptr;
+        check(floria_hip_join_paths(s_.ctx(), res_, handles_.data(), (uint32_t)handles_.size(), pc.data(), no.data(), nb.data(), np.data(), rng.data(), (uint32_t)pc.size(), &joined));
+        floria_hip_block_result_free(res_); res_ = nullptr;
+        if (haplosets_) { floria_hip_haplosets_free(haplosets_); haplosets_ = nullptr; }
+        const int rc = floria_hip_reassign_haplosets_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), joined, o.epsilon, &haplosets_);
+        floria_hip_haplosets_free(joined);
+        check(rc);
+        check(floria_hip_haplosets_download(haplosets_, &out));
+        paths_joined += pc.size();
+    } else {
+    const GroupCsr g = groups_of(work_, false);
     if (o.haplosets_resident) {                                                // the result stays on the device for stats_and_hapq; the writers' read lists come back once
         if (haplosets_) { floria_hip_haplosets_free(haplosets_); haplosets_ = nullptr; }
         check(floria_hip_reassign_batch_resident(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), g.gc.data(), g.off.data(), g.reads.data(), g.rng.data(),
@@ -412,6 +439,7 @@ void Batch::process_reads_for_final_parts(const Options& o) {
     } else
     check(floria_hip_reassign_batch(s_.ctx(), handles_.data(), (uint32_t)handles_.size(), g.gc.data(), g.off.data(), g.reads.data(), g.rng.data(), (uint32_t)g.gc.size(),
                                     nullptr, nullptr, o.epsilon, &out));
+    }
     for (size_t i = 0; i < work_.size(); ++i) {
         ContigWork& w = work_[i];
         const floria_groups* G = out[i];

@@ -87,6 +87,9 @@ struct Options {
     floria_realign_walk walk = {8, 8, 0, 0};
     PileupRoute pileup = PileupRoute::Host;   // --pileup
     bool haplosets_resident = false;    // --haplosets resident: S2 by floria_hip_reassign_batch_resident, one download, and the handle to the four consumers (Batch)
+    // --paths resident: the path peeling returns node lists, the reads of a path are united on the device (floria_hip_join_paths) and S2 takes that handle
+    // (floria_hip_reassign_haplosets_resident); S1 then returns no read list ("s1_no_lists") unless paths_keep_lists (--debug prints the nodes' reads)
+    bool paths_resident = false, paths_keep_lists = false;
 };
 // "exact" | "block:STEP,RULE,TIE" (STEP 1 | 2 | 4 | 8, RULE max | sum, TIE right | down) -> options.realign_walk / options.walk; anything else throws with the grammar
 void parse_realign_spec(const std::string& spec, Options& options);
@@ -175,6 +178,7 @@ struct HapNode {
     size_t column = SIZE_MAX, row = SIZE_MAX, id = SIZE_MAX;
     double cov = 0.0;
     std::pair<SnpPosition, SnpPosition> snp_endpoints;
+    uint32_t block = 0;                                                  // the block of the S1 call the column was made from (its index in that call)
 };
 
 // One context + the contig currently resident in HBM.
@@ -222,6 +226,12 @@ typedef std::vector<FlowUpdate> FlowUpVec;
 enum class LpTie { First, Last };
 struct LpInfo { int64_t cost = 0; size_t movable_edges = 0; };
 FlowUpVec solve_lp_graph(const std::vector<std::vector<HapNode>>& hap_graph, LpTie tie = LpTie::First, LpInfo* info = nullptr);
+// get_disjoint_paths_rewrite in two halves.  The peeling decides from node coordinates, block ranges and flows alone: per path its nodes (column, row), in the order the
+// trace-back visits them (sink first), and the SNP range they span.  The union concatenates the frag_sets of a path's nodes, sorts by counter_id and drops repeats.
+struct PeeledPath { std::vector<std::pair<size_t, size_t>> nodes; std::pair<SnpPosition, SnpPosition> ends; };
+std::vector<PeeledPath> peel_disjoint_paths(std::vector<std::vector<HapNode>>& hap_graph, const FlowUpVec& flow_update_vec, const Options& options);
+std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPosition, SnpPosition>>> unite_paths(const std::vector<std::vector<HapNode>>& hap_graph,
+                                                                                                                 const std::vector<PeeledPath>& paths);
 std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPosition, SnpPosition>>> get_disjoint_paths_rewrite(
     std::vector<std::vector<HapNode>>& hap_graph, const FlowUpVec& flow_update_vec, const Options& options);
 std::vector<const Frag*> get_frags_in_snpless_gaps(const std::vector<std::pair<SnpPosition, SnpPosition>>& path_parts, const std::vector<GnPosition>& snp_to_gn_pos,
@@ -488,6 +498,7 @@ struct ContigWork {
     FlowUpVec flows;                                                   // solve_lp_graph
     std::vector<std::vector<const Frag*>> path_parts, final_parts;     // get_disjoint_paths_rewrite / process_reads_for_final_parts
     std::vector<std::pair<SnpPosition, SnpPosition>> path_ranges, final_ranges;
+    std::vector<PeeledPath> path_nodes;                                // --paths resident: peel_disjoint_paths (path_parts then stay empty unless --debug)
     std::vector<const Frag*> snpless;                                  // get_frags_in_snpless_gaps
     std::vector<double> stats;                                         // 4 per final haploset: cov, err, total_err, total_cov
     HapqResult hq;
@@ -509,13 +520,14 @@ public:
     Batch(const Batch&) = delete;
     Batch& operator=(const Batch&) = delete;
     void generate_hap_graphs(const Options& options);                  // upload + S1 + hap graph for every contig (graph_processing.rs:325-372)
-    void process_reads_for_final_parts(const Options& options);        // S2 for every contig, from path_parts / path_ranges
+    void process_reads_for_final_parts(const Options& options);        // S2 for every contig, from path_parts / path_ranges (--paths resident: from path_nodes, joined on the device)
     void stats_and_hapq(const Options& options);                       // get_errors_cov_from_frags + get_hapq for every final haploset; for contigs with a handle also the
                                                                        // writers' allele tables and, with --output-reads, their trim lookups
     // --dump-handles (tests): per contig "#CONTIG name n_reads", "#IDS id ..", then "#FIELD k v .." for floria_hip_contig_download fields 0-6 as uint32 words and
     // field 7 where the contig carries a set order; valid once generate_hap_graphs has run (every contig then has a handle, whichever route made it)
     std::string dump_handles() const;
     uint64_t bytes_back = 0;                                           // bytes of the allele tables and trim lookups received
+    uint64_t paths_joined = 0;                                         // --paths resident: paths united on the device
     uint64_t haplosets_by_handle = 0;                                  // --haplosets resident: final haplosets whose statistics were computed from the handle
 private:
     Session& s_;
@@ -524,6 +536,7 @@ private:
     std::vector<size_t> host_ix_;                                      // the contigs without a handle of their own: marshalled here, piles_[j] is contig host_ix_[j]
     std::vector<floria_pileup_packed> piles_;
     std::vector<floria_hip_contig*> handles_;                          // per contig: the ContigWork's own handle, or the one uploaded here (owned_)
+    floria_block_result* res_ = nullptr;                               // --paths resident: the S1 result (its batch stays resident) from generate_hap_graphs to the join
     floria_hip_haplosets* haplosets_ = nullptr;                        // --haplosets resident: S2's result on the device, from process_reads_for_final_parts to the destructor
     std::vector<char> owned_;
 };

@@ -121,6 +121,7 @@ struct RunStats {
     size_t n_resident_merged = 0, n_resident_contigs = 0;
     double t_resident_assemble = 0., t_resident_filter = 0., t_resident_assemble_ev = 0., t_resident_filter_ev = 0.;
     std::atomic<uint64_t> n_haplosets_by_handle{0};                          // --haplosets resident
+    std::atomic<uint64_t> n_paths_joined{0};                                 // --paths resident
     uint64_t resident_bytes_back = 0, resident_removed_snps = 0, resident_dropped_reads = 0;
     std::atomic<size_t> lp_contigs{0}, lp_not_unique{0}, lp_edges{0}, lp_movable{0};
 
@@ -176,6 +177,10 @@ struct RunStats {
         if (o.haplosets_resident)
             fprintf(stderr, "Haplosets: %llu split, sorted and kept on the device behind S2 (floria_hip_reassign_batch_resident); one download for the writers, COV / ERR, HAPQ, "
                             "allele tables and read trims by handle\n", (unsigned long long)n_haplosets_by_handle.load());
+        if (o.paths_resident)
+            fprintf(stderr, "Paths: --paths resident: %llu hap-graph paths joined into haplosets on the device (floria_hip_join_paths), S2 from that handle "
+                            "(floria_hip_reassign_haplosets_resident); S1 %s\n", (unsigned long long)n_paths_joined.load(),
+                    o.paths_keep_lists ? "returned its read lists (--debug prints them)" : "returned no read list");
         fprintf(stderr, "Batches %zu; ingest %.3fs, phasing (upload + S1 + graph) %.3fs, LP + paths %.3fs, S2 %.3fs, COV/ERR/HAPQ %.3fs, writers %.3fs\n", n_batches, t_ingest, t_s1,
                 t_stitch, t_s2, t_stats, t_write);
         if (reference_arith && n_batches_orders)
@@ -491,8 +496,13 @@ void device_stages(Run& run, RunStats& stats, Session& session, std::vector<Cont
         LpInfo li;
         w.flows = solve_lp_graph(w.hap_graph, cli.lp_tie, cli.lp_report ? &li : nullptr);
         if (cli.lp_report) { ++stats.lp_contigs; stats.lp_not_unique += li.movable_edges != 0; stats.lp_edges += w.flows.size(); stats.lp_movable += li.movable_edges; }
+        if (o.paths_resident) {                                              // the peeling alone: the union runs on the device (Batch::process_reads_for_final_parts)
+            w.path_nodes = peel_disjoint_paths(w.hap_graph, w.flows, o);
+            if (o.paths_keep_lists) { auto paths = unite_paths(w.hap_graph, w.path_nodes); w.path_parts = std::move(paths.first); w.path_ranges = std::move(paths.second); }      // (--debug prints them)
+        } else {
         auto paths = get_disjoint_paths_rewrite(w.hap_graph, w.flows, o);
         w.path_parts = std::move(paths.first); w.path_ranges = std::move(paths.second);
+        }
         if (cli.debug) write_debug_graph(w);
     });
     tm[1] += now_s() - t1; t1 = now_s();
@@ -501,6 +511,7 @@ void device_stages(Run& run, RunStats& stats, Session& session, std::vector<Cont
     batch.stats_and_hapq(o);
     tm[3] += now_s() - t1;
     stats.n_haplosets_by_handle += batch.haplosets_by_handle;
+    stats.n_paths_joined += batch.paths_joined;
     if (batch.bytes_back) stats.resident_bytes_back += batch.bytes_back;    // (resident contigs exist with one device only: no other thread is here then)
 }
 

@@ -235,8 +235,7 @@ FlowUpVec solve_lp_graph(const std::vector<std::vector<HapNode>>& hap_graph, LpT
 }
 
 // graph_processing.rs:462-750 (do_binning, a hidden flag, is not supported)
-std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPosition, SnpPosition>>> get_disjoint_paths_rewrite(
-    std::vector<std::vector<HapNode>>& hap_graph, const FlowUpVec& flow_update_vec, const Options&) {
+std::vector<PeeledPath> peel_disjoint_paths(std::vector<std::vector<HapNode>>& hap_graph, const FlowUpVec& flow_update_vec, const Options&) {
     StableGraph pg;
     for (auto& col : hap_graph) for (auto& n : col) n.out_flows.clear();
     for (const auto& fu : flow_update_vec) {                                        // :474-483
@@ -249,8 +248,7 @@ std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPositi
         for (size_t r = 0; r < hap_graph[c].size(); ++r)
             for (const auto& of : hap_graph[c][r].out_flows) pg.add_edge(index[c][r], index[c + 1][of.first], of.second);
     const size_t num_starting_nodes = pg.nodes.size();
-    std::vector<std::vector<const Frag*>> all_joined_path_parts;
-    std::vector<std::pair<SnpPosition, SnpPosition>> path_parts_snp_endpoints;
+    std::vector<PeeledPath> peeled;
     const double F64_MAX = std::numeric_limits<double>::max();
     while (pg.n_alive > 0) {
         std::vector<TraceBackNode> tb(num_starting_nodes);                           // :505-536 / :557-589
@@ -280,23 +278,42 @@ std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPositi
         double best_score = std::numeric_limits<double>::lowest();                   // f64::MIN
         for (size_t i = 0; i < tb.size(); ++i) if (tb[i].score > best_score && tb[i].is_sink) { best_end = (int)i; best_score = tb[i].score; }
         if (best_end < 0) throw Error(FLORIA_E_INVALID, "get_disjoint_paths_rewrite: no sink (the reference panics here: \"Shouldn't get here\")");
-        std::vector<const Frag*> joined;
-        std::pair<SnpPosition, SnpPosition> ends{std::numeric_limits<SnpPosition>::max(), std::numeric_limits<SnpPosition>::min()};
+        PeeledPath path;
+        std::pair<SnpPosition, SnpPosition>& ends = path.ends;
+        ends = {std::numeric_limits<SnpPosition>::max(), std::numeric_limits<SnpPosition>::min()};
         std::vector<int> best_path;
         for (int cur = best_end; cur >= 0; cur = tb[cur].prev_ind) {                 // :676-705
             const HapNode& hn = hap_graph[pg.nodes[cur].col][pg.nodes[cur].row];
             ends.first = std::min(ends.first, hn.snp_endpoints.first);
             ends.second = std::max(ends.second, hn.snp_endpoints.second);
-            joined.insert(joined.end(), hn.frag_set.begin(), hn.frag_set.end());
+            path.nodes.push_back({pg.nodes[cur].col, pg.nodes[cur].row});
             best_path.push_back(cur);
         }
         for (int n : best_path) pg.remove_node(n);                                   // :714-717
+        peeled.push_back(std::move(path));
+    }
+    return peeled;
+}
+
+// :676-705, the frag_set side: the reads of a path's nodes as one set
+std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPosition, SnpPosition>>> unite_paths(const std::vector<std::vector<HapNode>>& hap_graph,
+                                                                                                                 const std::vector<PeeledPath>& paths) {
+    std::vector<std::vector<const Frag*>> all_joined_path_parts;
+    std::vector<std::pair<SnpPosition, SnpPosition>> path_parts_snp_endpoints;
+    for (const PeeledPath& path : paths) {
+        std::vector<const Frag*> joined;
+        for (const auto& cr : path.nodes) { const HapNode& hn = hap_graph[cr.first][cr.second]; joined.insert(joined.end(), hn.frag_set.begin(), hn.frag_set.end()); }
         std::sort(joined.begin(), joined.end(), [](const Frag* a, const Frag* b) { return a->counter_id < b->counter_id; });   // a set: each read once
         joined.erase(std::unique(joined.begin(), joined.end()), joined.end());
         all_joined_path_parts.push_back(std::move(joined));
-        path_parts_snp_endpoints.push_back(ends);
+        path_parts_snp_endpoints.push_back(path.ends);
     }
     return {std::move(all_joined_path_parts), std::move(path_parts_snp_endpoints)};
+}
+
+std::pair<std::vector<std::vector<const Frag*>>, std::vector<std::pair<SnpPosition, SnpPosition>>> get_disjoint_paths_rewrite(
+    std::vector<std::vector<HapNode>>& hap_graph, const FlowUpVec& flow_update_vec, const Options& options) {
+    return unite_paths(hap_graph, peel_disjoint_paths(hap_graph, flow_update_vec, options));
 }
 
 // part_block_manip.rs:622-675.  rust-lapper's count(start, stop) counts intervals [s, e) with s < stop && e > start.

@@ -33,7 +33,7 @@ SYMBOLS = [
     "floria_hip_assemble_contigs_opt", "floria_hip_read_spans",
     "floria_hip_drop_monomorphic", "floria_hip_mono_result_free", "floria_hip_mono_timing",
     "floria_hip_reassign_batch_resident", "floria_hip_haplosets_free", "floria_hip_haplosets_download", "floria_hip_haploset_stats_resident", "floria_hip_hapq_batch_resident",
-    "floria_hip_haploset_alleles_resident", "floria_hip_read_spans_resident",
+    "floria_hip_haploset_alleles_resident", "floria_hip_read_spans_resident", "floria_hip_join_paths", "floria_hip_reassign_haplosets_resident",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -105,6 +105,9 @@ def load():
         L.floria_hip_hapq_batch_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, capi.u32p, C.c_uint64, capi.u8p, capi.f64p, capi.f64p]
         L.floria_hip_haploset_alleles_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, capi.u64p, capi.u32p]
         L.floria_hip_read_spans_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, capi.u32p, capi.u32p]
+        L.floria_hip_join_paths.argtypes = [C.c_void_p, C.POINTER(capi.CBlockResult), C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u8p, capi.u32p, C.c_uint32,
+                                            C.POINTER(C.c_void_p)]
+        L.floria_hip_reassign_haplosets_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.POINTER(C.c_void_p)]
         _LIB = L
     return _LIB
 
@@ -751,6 +754,45 @@ class FloriaHip:
                                             capi.ptr(reads, C.c_uint32), capi.ptr(rng, C.c_uint32), C.c_uint32(len(groups)), pp, capi.ptr(ns, C.c_uint32),
                                             C.c_uint64(int(block_length)), capi.ptr(hq, C.c_uint8), capi.ptr(rel, C.c_double), capi.ptr(avg, C.c_double)))
         return hq, rel, avg
+
+    # hap-graph paths -> haplosets on the resident S1 batch, and S2 from a handle ------------------------
+    def join_paths(self, res, contigs, path_contig, nodes, ranges):
+        """floria_hip_join_paths: path p of contig path_contig[p] (non-descending) is nodes[p], a sequence of (block, partition) of the S1 batch that produced `res`
+        (still resident: the rule of hap_graph); ranges[p] = (lo, hi) is passed through -> Haplosets whose group p unites the nodes' reads."""
+        off = np.zeros(len(nodes) + 1, np.uint64)
+        off[1:] = np.cumsum([len(n) for n in nodes])
+        flat = np.asarray([bk for n in nodes for bk in n], np.int64).reshape(-1, 2)
+        return self.join_paths_raw(res, contigs, len(contigs), np.asarray(path_contig, np.uint32), off, flat[:, 0].astype(np.uint32), flat[:, 1].astype(np.uint8),
+                                   np.asarray(ranges, np.uint32).reshape(-1), len(nodes))
+
+    def join_paths_raw(self, res, contigs, n_contigs, path_contig, node_off, node_block, node_part, path_range, n_paths, token=None):
+        """The C call with its arrays as given (None = NULL): what the refusal tests need."""
+        def p(a, dt, ct):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dt)
+            return a, capi.ptr(a, ct)
+        keep = [p(path_contig, np.uint32, C.c_uint32), p(node_off, np.uint64, C.c_uint64), p(node_block, np.uint32, C.c_uint32), p(node_part, np.uint8, C.c_uint8),
+                p(path_range, np.uint32, C.c_uint32)]
+        cres = None
+        if res is not None:
+            bp = np.ascontiguousarray(res.best_ploidy, np.uint32)
+            cres = capi.CBlockResult()
+            cres.n_blocks = res.n_blocks; cres.max_ploidy = res.max_ploidy; cres.best_ploidy = capi.ptr(bp, C.c_uint32)
+            cres.batch_token = res.batch_token if token is None else token
+        h = C.c_void_p()
+        _check(load().floria_hip_join_paths(self._h, C.byref(cres) if cres is not None else None, _contig_array(contigs) if contigs is not None else None, C.c_uint32(n_contigs),
+                                            keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1], C.c_uint32(n_paths), C.byref(h)))
+        return Haplosets(self, h, n_contigs)
+
+    def reassign_haplosets_resident(self, contigs, haplosets, epsilon):
+        """floria_hip_reassign_haplosets_resident: S2 whose input groups are a Haplosets handle (join_paths' or an earlier S2 call's) -> Haplosets; download() equals
+        reassign_batch_resident on haplosets.download() with no read order.  `haplosets` is left as it is."""
+        h = C.c_void_p()
+        n = len(contigs) if contigs is not None else haplosets.n_contigs
+        _check(load().floria_hip_reassign_haplosets_resident(self._h, _contig_array(contigs) if contigs is not None else None, C.c_uint32(n),
+                                                             haplosets._h if haplosets is not None else None, C.c_double(epsilon), C.byref(h)))
+        return Haplosets(self, h, n)
 
     # S2 --------------------------------------------------------------------------------------------
     def reassign_batch_resident(self, contigs, grp_contig, groups, ranges, epsilon, read_orders=None):

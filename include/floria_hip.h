@@ -611,6 +611,41 @@ int  floria_hip_haploset_alleles_resident(floria_hip_ctx* ctx, const floria_hip_
 int  floria_hip_read_spans_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs, const floria_hip_haplosets* hs,
                                     uint32_t* left, uint32_t* right);
 
+/* ---- hap-graph paths -> haplosets on the device, and S2 whose input is a handle: no per-read list crosses the link between S1 and S2 ------------------------------
+ * floria_hip_join_paths is the union that ends get_disjoint_paths_rewrite (graph_processing.rs), on the S1 batch `res` that is still resident: path p (of contig
+ * path_contig[p], non-descending) is the list of hap-graph nodes node_off[p] .. node_off[p + 1], node n = partition node_part[n] of block node_block[n] of that batch.
+ * Group p of the result holds, ascending and once each, every read r for which some node (b, k) of the path has r in block b's list with part == k; its range is
+ * path_range[2p], path_range[2p + 1], passed through.  A node may occur in several paths and a read in several groups; a path without nodes is an empty group that
+ * keeps its range.  The result is a complete floria_hip_haplosets — the layout of the S2 handle, a buffer of its own, groups contig-major in path order — that
+ * floria_hip_haplosets_download, the four *_resident consumers and floria_hip_reassign_haplosets_resident take as they take S2's.
+ * RESIDENCY.  The token rule and message of floria_hip_hap_graph; the call may run before or after it, any number of times, and ends no residency (its tables lie in
+ * buffers of their own).  `contigs` must be the array of the S1 call.
+ * Kernels (csrc/path_kernel.h): per path an id window from its nodes' lists, a bitmap over it marked by integer atomicOr, popcount, prefix sums, fill by prefix
+ * popcount: the result does not depend on the order in which anything lands; memory is linear in the sum of the windows.  Two copies come back during the call: the
+ * bitmap's size (8 B) and two words per contig.
+ * Refused before any launch, FLORIA_E_INVALID each, the message naming the argument: a null argument; a stale or foreign token; a contig of another context or an
+ * array that is not the S1 call's; path_contig >= n_contigs or descending; node_off not starting at 0 or descending; node_block >= n_blocks; node_part >=
+ * best_ploidy[block] (which covers every node of an empty block); a node whose block belongs to another contig than its path.
+ *
+ * floria_hip_reassign_haplosets_resident is floria_hip_reassign_batch_resident whose input groups are the handle `in` (from floria_hip_join_paths or from an S2 call;
+ * it is left unchanged and valid): floria_hip_haplosets_download(*out) equals, list for list, what floria_hip_reassign_batch_resident returns for
+ * floria_hip_haplosets_download(in) concatenated in contig order with read_order == NULL — in both arithmetics, under "s2_assign_only" and under "reassign_path" 1
+ * and 2.  Reads are visited in ascending counter_id.  The per-read tables of the prologue (read -> candidate groups, the `multi` list, the id windows) are built on
+ * the device from the handle (csrc/haploset_kernel.h); the host reads header-sized data only: per group its size and the SNP span of its reads, per contig the number
+ * of reads that have a choice.  Re-insertion kernels, path choice and epilogue are those of floria_hip_reassign_batch_resident.  Like it, the call works in the buffer
+ * of the last phase_blocks* batch and ends that batch's residency.  Refused as the *_resident consumers refuse: a null argument, a handle of another context, a
+ * `contigs` array that is not the handle's. */
+int  floria_hip_join_paths(floria_hip_ctx* ctx, const floria_block_result* res,
+                           const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                           const uint32_t* path_contig,   /* [n_paths] index into contigs, non-descending */
+                           const uint64_t* node_off,      /* [n_paths+1] */
+                           const uint32_t* node_block,    /* [node_off[n_paths]] block index of the S1 batch `res` */
+                           const uint8_t*  node_part,     /* same length: partition, < best_ploidy[block] */
+                           const uint32_t* path_range,    /* [2*n_paths] inclusive SNP range, passed through */
+                           uint32_t n_paths, floria_hip_haplosets** out);
+int  floria_hip_reassign_haplosets_resident(floria_hip_ctx* ctx, const floria_hip_contig* const* contigs, uint32_t n_contigs,
+                                            const floria_hip_haplosets* in, double epsilon, floria_hip_haplosets** out);
+
 int  floria_hip_last_timing(const floria_hip_ctx* ctx, floria_timing* out);
 
 /* Self-test of a hardware assumption: the beam kernel screens the pruning test (global_clustering.rs:98) with an f32 evaluation of stable_binom_cdf_p_rev
@@ -644,6 +679,10 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * one).  A Rust host that wants its own sets' order inserts the returned reads into its sets and keeps calling its own two functions: they are integer
  * bookkeeping, a few microseconds per contig.
  *
+ * "s1_no_lists" = 1: floria_hip_phase_* leave the per-(block, read) lists on the device: read_id and part of the result are NULL (floria_hip_block_result_free copes),
+ * every other field, the resident batch and the token are as before.  For a host that needs the lists on the device only (floria_hip_hap_graph,
+ * floria_hip_join_paths): 5 B per (block, read) stay off the link.  Default 0: nothing changes.
+ *
  * Tuning / test knobs; none changes results.  Keys: "groups" (job groups on separate streams, 0 = auto), "speculate" (ploidy stages: -1 auto,
  * 0 one ploidy at a time, 1 all ploidies of a block at once, 2 {1,2,3} then {4..P}), "spec_gate_div" (grid divisor of the gated ploidies of a
  * speculative stage, default 2), "tail_overlap" (one ploidy per stage: the beam launch of the LAST ploidy runs beside the optimise launch of the
@@ -653,7 +692,7 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
  * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
- * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic, the epilogue of floria_hip_reassign_batch_resident — uses at most N workgroups, and the one-thread order kernel at most N threads,
+ * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic, the epilogue of floria_hip_reassign_batch_resident, floria_hip_join_paths, the device prologue of floria_hip_reassign_haplosets_resident — uses at most N workgroups, and the one-thread order kernel at most N threads,
  * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "hw_queues" (tests: override the number of
  * concurrently running streams floria_hip_create measured — 6 on an MI355X whose host set GPU_MAX_HW_QUEUES=12 before HIP initialised, 4 or fewer
  * with the runtime's default; below 5 the launch plans stay within two job groups and do not speculate). */

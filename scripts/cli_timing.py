@@ -8,6 +8,9 @@ median and the spread (min .. max) of the ingest time and of the wall time per r
 (profiles/pileup_device.md, profiles/pileup_fused.md, profiles/pileup_resident.md).
 --haplosets-compare N [--pileup-route host|resident]: only the batched flow on that --pileup route, --haplosets host and resident ALTERNATING, N runs each, then
 the median and the spread (min .. max) of the S2 stage, the COV/ERR/HAPQ stage, their sum and the wall time per setting (profiles/haplosets_resident.md).
+--paths-compare N [--pileup-route host|resident]: only the batched flow on that --pileup route under --haplosets resident, --paths host and resident ALTERNATING,
+N runs each, then the median and the spread of the phasing stage (upload + S1 + graph: where the read lists come down or do not), the LP + paths stage, the S2 stage,
+their sum and the wall time per setting (profiles/paths_resident.md).
 --config K --epsilon X --block-length N: the data set's synth configuration (4 = long reads [default], 3 = paired short reads) and the run's -e / -l, e.g.
 --config 3 --epsilon 0.04 --block-length 500 for the paired set in the reference arithmetic.
 --realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
@@ -40,7 +43,8 @@ def main():
     ap.add_argument("--pileup-compare", type=int, default=0, help="only: the batched flow with --pileup host, device and fused alternating, this many runs each")
     ap.add_argument("--threads-list", default=None, help="with --pileup-compare: comma-separated -t values (default: --threads)")
     ap.add_argument("--haplosets-compare", type=int, default=0, help="only: the batched flow with --haplosets host and resident alternating, this many runs each")
-    ap.add_argument("--pileup-route", default="host", help="with --haplosets-compare: the --pileup route of every run")
+    ap.add_argument("--paths-compare", type=int, default=0, help="only: the batched flow under --haplosets resident with --paths host and resident alternating, this many runs each")
+    ap.add_argument("--pileup-route", default="host", help="with --haplosets-compare / --paths-compare: the --pileup route of every run")
     ap.add_argument("--config", type=int, default=4, help="synth configuration of the contigs (4: long reads, 3: paired short reads)")
     ap.add_argument("--epsilon", default="0.03125", help="-e of every run")
     ap.add_argument("--block-length", default="10000", help="-l of every run")
@@ -70,10 +74,13 @@ def main():
     if a.haplosets_compare:
         runs = tuple((f"--pileup {a.pileup_route}, --haplosets {h}, run {k + 1}", ["-t", str(a.threads), "--pileup", a.pileup_route, "--haplosets", h])
                      for k in range(a.haplosets_compare) for h in ("host", "resident"))
+    if a.paths_compare:
+        runs = tuple((f"--pileup {a.pileup_route}, --paths {h}, run {k + 1}", ["-t", str(a.threads), "--pileup", a.pileup_route, "--haplosets", "resident", "--paths", h])
+                     for k in range(a.paths_compare) for h in ("host", "resident"))
     if a.only:
         runs = tuple(r for r in runs if a.only in r[0])
     stages = {}
-    stats, calls = {}, {}
+    stats, calls, paths = {}, {}, {}
     for label, extra in runs:
         out = os.path.join(tmp, "o_" + label.replace(" ", "_").replace(",", ""))
         t = time.time()
@@ -82,12 +89,16 @@ def main():
         if r.returncode:
             print(r.stderr[-2000:])
             raise SystemExit(1)
-        lines = [ln for ln in r.stderr.splitlines() if ln.startswith(("Batches", "Total time", "Preprocessing:", "[read_bam]", "Realignment:", "Pileup on the device:", "Resident contigs:", "Haplosets:"))]
+        lines = [ln for ln in r.stderr.splitlines() if ln.startswith(("Batches", "Total time", "Preprocessing:", "[read_bam]", "Realignment:", "Pileup on the device:", "Resident contigs:", "Haplosets:", "Paths:"))]
         print(f"[{label}] wall {wall:.2f}s | " + " | ".join(lines), flush=True)
         if a.haplosets_compare:
             m = re.search(r"S2 ([\d.]+)s, COV/ERR/HAPQ ([\d.]+)s", next(ln for ln in lines if ln.startswith("Batches")))
             s2, st = float(m.group(1)), float(m.group(2))
             stages.setdefault(label.rsplit(", run", 1)[0], []).append((s2, st, s2 + st, wall))
+        if a.paths_compare:
+            m = re.search(r"phasing \(upload \+ S1 \+ graph\) ([\d.]+)s, LP \+ paths ([\d.]+)s, S2 ([\d.]+)s", next(ln for ln in lines if ln.startswith("Batches")))
+            ph, lp, s2 = float(m.group(1)), float(m.group(2)), float(m.group(3))
+            paths.setdefault(label.rsplit(", run", 1)[0], []).append((ph, lp, s2, ph + lp + s2, wall))
         if a.pileup_compare:
             ingest = float(next(ln for ln in lines if ln.startswith("Batches")).split("ingest ")[1].split("s")[0])
             stats.setdefault(label.rsplit(", run", 1)[0], []).append((ingest, wall))
@@ -109,6 +120,10 @@ def main():
             print(f"[{key}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs")
     for key, v in stages.items():
         for k, what in enumerate(("S2", "COV/ERR/HAPQ", "S2 + COV/ERR/HAPQ", "wall")):
+            x = sorted(t[k] for t in v)
+            print(f"[{key}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs")
+    for key, v in paths.items():
+        for k, what in enumerate(("phasing", "LP + paths", "S2", "phasing + LP + paths + S2", "wall")):
             x = sorted(t[k] for t in v)
             print(f"[{key}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs")
     for key, v in calls.items():
