@@ -25,6 +25,8 @@ void usage() {
           "  --device N | --devices 0-7 | 0,2,5   GPU(s); contigs of a batch are dealt to them, files do not depend on it\n"
           "  --batch-contigs N [4096]  --batch-cells N [2^28]   contigs taken through the device stages together\n"
           "  --bam-window-mb N [512]   inflated BAM records held in memory at a time\n"
+          "  an index beside the BAM (X.bam.bai, then X.bai) is used when present: only the contigs to be phased (-G, --snp-count-filter) are read, each from its indexed offset\n"
+          "  --no-index        ignore the index: stream the whole file in order, as when there is none\n"
           "  --arith auto|reference|canonical   how sums of epsilon terms are rounded when -e is not a multiple of 2^-10: 'reference' = floria's running f64 sums\n"
           "                 in its hash containers' iteration order (as far as that order can be emulated), 'canonical' = every sum rounded once; auto [default] =\n"
           "                 reference, except for batches with fragments merged from mates / supplementary alignments or under --ignore-monomorphic\n"
@@ -108,6 +110,7 @@ Cli parse_args(int argc, char** argv) {
         else if (a == "--arith") { cli.arith_opt = val(); if (cli.arith_opt != "auto" && cli.arith_opt != "reference" && cli.arith_opt != "canonical") throw Error(FLORIA_E_INVALID, "--arith takes auto, reference or canonical"); }
         else if (a == "--bam-window-mb") cli.bam_window = std::max<size_t>(1, std::stoul(val())) << 20;
         else if (a == "--bam-window-kb") cli.bam_window = std::max<size_t>(1, std::stoul(val())) << 10;       // (tests: many segments on a small file)
+        else if (a == "--no-index") cli.no_index = true;
         else if (a == "--devices") {                                 // "0-7", "0,2,5", "0-3,6"; a device may be named twice (two contexts on it)
             std::stringstream ls(val());
             std::string item;

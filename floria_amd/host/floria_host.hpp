@@ -294,14 +294,30 @@ struct BamFile {
     BamFile(const BamFile&) = delete;
     BamFile& operator=(const BamFile&) = delete;
 };
+// The .bai index of a BAM (SAM specification 5.2), as far as a per-target seek needs it: for every target the virtual offset (coffset << 16 | uoffset) of its
+// first record, the smallest chunk begin over its real bins, and that of the end of its last one (the largest chunk end: a hint, the records decide).  A target
+// without a bin has no record.  The metadata pseudo-bin 37450 may be absent; where present its ref_beg must equal the smallest chunk begin.  Every length is checked
+// against the file: a truncated or malformed index is FLORIA_E_INVALID naming the index file.  CSI is not read.
+struct BaiIndex {
+    struct Target { bool has_records = false; uint64_t begin = 0, end = 0; };
+    std::string path;
+    std::vector<Target> targets;
+    uint64_t n_no_coor = 0;
+    bool has_n_no_coor = false;
+};
+BaiIndex read_bai(const std::string& path);
+std::string find_bai(const std::string& bam_path);         // X.bam.bai, then X.bai; "" when neither exists
 // A coordinate-sorted BAM in bounded memory: the file is mapped, its BGZF members are indexed from their headers (no inflation), and next() inflates
 // (in parallel) just enough members to return the records of the next run of COMPLETE targets — at least `min_bytes` of inflated records, more only when one
-// target alone is larger.  The reference reaches the same records through the .bai index, one contig at a time (file_reader.rs:389-436); no index is
-// needed here because targets come in header order in a sorted file.  A file that is not sorted by target is refused, a gzip file without BGZF members
-// is read whole (one segment).
+// target alone is larger.  A file that is not sorted by target is refused, a gzip file without BGZF members is read whole (one segment).
+// Without an index every member is inflated in file order: targets come in header order in a sorted file.  With `use_index` and a .bai beside the file (find_bai)
+// the member headers are walked lazily and select() narrows next() to the targets named: each is read from the offset the index gives for it up to the first
+// record of another target, as the reference fetches one contig at a time (file_reader.rs:389-436); a target without a bin costs nothing.  Segments stay runs of
+// complete targets [tid_begin, tid_end) in header order, the unselected ones among them without records.  Before select() (the parameter estimate) and without
+// an index the stream reads the file from its start, segment by segment, as it always has.
 class BamStream {
 public:
-    BamStream(const std::string& path, size_t threads = 1);
+    BamStream(const std::string& path, size_t threads = 1, bool use_index = false);
     ~BamStream();
     BamStream(const BamStream&) = delete;
     BamStream& operator=(const BamStream&) = delete;
@@ -309,6 +325,11 @@ public:
     bool next(BamFile& segment, size_t min_bytes);     // false: end of file (every target has been handed out)
     void rewind();
     size_t peak_buffer_bytes() const;                  // largest inflated buffer so far (what "bounded" means for this file)
+    // Only these targets from here on (once, at the start of a pass).  Without an index the call changes nothing: every record is still handed out.
+    void select(const std::vector<int32_t>& tids);
+    const std::string& index_path() const;             // "" when no index is in use
+    struct IndexUse { size_t selected, members_inflated, members_in_file; };
+    IndexUse index_use() const;                        // (members_in_file walks the member headers that have not been walked yet)
 private:
     struct Impl;
     std::unique_ptr<Impl> p_;

@@ -15,7 +15,8 @@
 //                                  adaptive banded SIMD aligner, fixed 8-wide blocks); here they come from the exact affine-gap DP, which
 //                                  the banded heuristic approximates — identical wherever its band contains an optimal path (parity of this
 //                                  step is unpinned: third-party arithmetic).  Only runs when a reference FASTA is given, as in the reference.
-// The whole BAM is read once and records are bucketed by contig in file order, so no .bai is needed; `count` (the enumerate
+// Without an index the whole BAM is read once and records are bucketed by contig in file order; with a .bai beside it only the contigs selected for phasing
+// are read, each from its indexed offset (BamStream::select; read_bai: SAM specification 5.2).  Either way `count` (the enumerate
 // index frag_from_record stores in counter_id, which breaks ties of Frag::cmp in all_frags.sort(), floria.rs:289) is the
 // record's index among the contig's records, as with the reference's fetch().
 #include "floria_host.hpp"
@@ -79,20 +80,27 @@ template <class F> void parallel_tasks(size_t n, size_t threads, F&& f) {
 // before any is inflated: -> false if `in` is not made of BGZF members only (plain gzip: the serial path takes it)
 struct BgzfBlock { size_t in_off, in_len, out_off, out_len; };
 struct ByteSpan { const unsigned char* p; size_t n; size_t size() const { return n; } const unsigned char& operator[](size_t i) const { return p[i]; } };
+// the header of the member that starts at in[o]: its compressed size and the inflated size its last four bytes give; false: no BGZF member starts there
+bool bgzf_member(const ByteSpan& in, size_t o, size_t& bsize, uint32_t& isize) {
+    if (o + 18 > in.size() || in[o] != 0x1f || in[o + 1] != 0x8b || in[o + 2] != 8 || !(in[o + 3] & 4)) return false;
+    const size_t xlen = in[o + 10] | (in[o + 11] << 8);
+    if (o + 12 + xlen > in.size()) return false;
+    size_t x = o + 12;
+    bsize = 0;
+    while (x + 4 <= o + 12 + xlen) {
+        const size_t slen = in[x + 2] | (in[x + 3] << 8);
+        if (in[x] == 'B' && in[x + 1] == 'C' && slen == 2 && x + 6 <= o + 12 + xlen) bsize = (size_t)(in[x + 4] | (in[x + 5] << 8)) + 1;
+        x += 4 + slen;
+    }
+    if (bsize < 12 + xlen + 8 || o + bsize > in.size()) return false;
+    memcpy(&isize, &in[o + bsize - 4], 4);
+    return true;
+}
 bool bgzf_index(const ByteSpan& in, std::vector<BgzfBlock>& blocks) {
     size_t o = 0, out = 0;
     while (o < in.size()) {
-        if (o + 18 > in.size() || in[o] != 0x1f || in[o + 1] != 0x8b || in[o + 2] != 8 || !(in[o + 3] & 4)) return false;
-        const size_t xlen = in[o + 10] | (in[o + 11] << 8);
-        if (o + 12 + xlen > in.size()) return false;
-        size_t x = o + 12, bsize = 0;
-        while (x + 4 <= o + 12 + xlen) {
-            const size_t slen = in[x + 2] | (in[x + 3] << 8);
-            if (in[x] == 'B' && in[x + 1] == 'C' && slen == 2 && x + 6 <= o + 12 + xlen) bsize = (size_t)(in[x + 4] | (in[x + 5] << 8)) + 1;
-            x += 4 + slen;
-        }
-        if (bsize < 12 + xlen + 8 || o + bsize > in.size()) return false;
-        uint32_t isize; memcpy(&isize, &in[o + bsize - 4], 4);
+        size_t bsize; uint32_t isize;
+        if (!bgzf_member(in, o, bsize, isize)) return false;
         blocks.push_back({o, bsize, out, isize});
         o += bsize; out += isize;
     }
@@ -156,6 +164,7 @@ struct Cursor {
     const std::string& what;
     void need(size_t k) const { if (o + k > n) throw Error(FLORIA_E_INVALID, what + " is truncated"); }
     uint32_t u32() { need(4); uint32_t v; memcpy(&v, p + o, 4); o += 4; return v; }
+    uint64_t u64() { need(8); uint64_t v; memcpy(&v, p + o, 8); o += 8; return v; }
     int32_t i32() { return (int32_t)u32(); }
     uint16_t u16() { need(2); uint16_t v; memcpy(&v, p + o, 2); o += 2; return v; }
     uint8_t u8() { need(1); return p[o++]; }
@@ -518,6 +527,64 @@ BamFile read_bam(const std::string& path, size_t threads) {
 static_assert(std::is_nothrow_move_constructible<Frag>::value && std::is_nothrow_move_assignable<Frag>::value,
               "RealignQueue::dst points into Frag::seq_dict: a vector of Frags must MOVE its elements when it grows");
 
+// ---- the .bai index ----------------------------------------------------------------------------------------------------------------------
+std::string find_bai(const std::string& bam_path) {
+    struct stat st;
+    const std::string a = bam_path + ".bai";
+    if (stat(a.c_str(), &st) == 0 && S_ISREG(st.st_mode)) return a;
+    const size_t dot = bam_path.rfind('.');
+    if (dot != std::string::npos && bam_path.find('/', dot) == std::string::npos) {
+        const std::string b = bam_path.substr(0, dot) + ".bai";
+        if (stat(b.c_str(), &st) == 0 && S_ISREG(st.st_mode)) return b;
+    }
+    return "";
+}
+
+BaiIndex read_bai(const std::string& path) {
+    const std::vector<unsigned char> raw = slurp(path);
+    const auto bad = [&](const std::string& why) { return Error(FLORIA_E_INVALID, path + " is not a valid BAI index: " + why); };
+    if (raw.size() < 8) throw Error(FLORIA_E_INVALID, path + " is truncated");
+    if (memcmp(raw.data(), "BAI\1", 4) != 0) throw bad("it does not begin with the magic BAI\\1 (a CSI index is not read)");
+    Cursor c{raw.data(), raw.size(), 4, path};
+    BaiIndex ix;
+    ix.path = path;
+    const uint32_t n_ref = c.u32();
+    c.need((size_t)n_ref * 8);                                  // (n_bin and n_intv of every reference at the least: bounds the allocation below)
+    ix.targets.resize(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        BaiIndex::Target& t = ix.targets[r];
+        bool have_meta = false;
+        uint64_t meta_beg = 0, meta_end = 0;
+        const uint32_t n_bin = c.u32();
+        for (uint32_t b = 0; b < n_bin; ++b) {
+            const uint32_t bin = c.u32(), n_chunk = c.u32();
+            c.need((size_t)n_chunk * 16);
+            if (bin == 37450) {                                 // the metadata pseudo-bin: (ref_beg, ref_end), (n_mapped, n_unmapped)
+                if (n_chunk != 2) throw bad("the pseudo-bin 37450 of reference " + std::to_string(r) + " has " + std::to_string(n_chunk) + " chunks, not 2");
+                meta_beg = c.u64(); meta_end = c.u64(); (void)c.u64(); (void)c.u64();
+                have_meta = true;
+                continue;
+            }
+            if (bin > 37448) throw bad("bin " + std::to_string(bin) + " of reference " + std::to_string(r));
+            for (uint32_t k = 0; k < n_chunk; ++k) {
+                const uint64_t beg = c.u64(), end = c.u64();
+                if (!t.has_records || beg < t.begin) t.begin = beg;
+                if (!t.has_records || end > t.end) t.end = end;
+                t.has_records = true;
+            }
+        }
+        if (have_meta && t.has_records && meta_beg != t.begin)
+            throw bad("reference " + std::to_string(r) + ": ref_beg of the pseudo-bin is not the smallest chunk begin of its bins");
+        if (have_meta && t.has_records) t.end = std::max(t.end, meta_end);
+        const uint32_t n_intv = c.u32();
+        c.need((size_t)n_intv * 8);
+        c.o += (size_t)n_intv * 8;
+    }
+    if (c.o + 8 == raw.size()) { ix.n_no_coor = c.u64(); ix.has_n_no_coor = true; }
+    else if (c.o != raw.size()) throw bad(std::to_string(raw.size() - c.o) + " bytes follow the last reference");
+    return ix;
+}
+
 // ---- BamStream -------------------------------------------------------------------------------------------------------------------------
 struct BamStream::Impl {
     std::string path;
@@ -525,8 +592,30 @@ struct BamStream::Impl {
     int fd = -1;
     const unsigned char* map = nullptr;
     size_t map_len = 0;
-    std::vector<BgzfBlock> blocks;            // BGZF members (empty: not a BGZF file -> `whole`)
+    // BGZF members from the start of the file (empty: not a BGZF file -> `whole`).  Without an index all of them, walked at open; with one, those walked
+    // so far (have_block walks on): the stretches select() asks for keep member lists of their own, from each seek point on
+    std::vector<BgzfBlock> blocks;
+    size_t walked = 0;                        // file offset behind the last member of `blocks`
     bool bgzf = false;
+    // the index and the selection
+    bool indexed = false;
+    BaiIndex bai;
+    std::vector<int32_t> sel;                 // select(): ascending
+    bool selecting = false, sel_done = false;
+    size_t sel_pos = 0;
+    size_t members_inflated = 0;              // since select()
+    struct CachedMember { size_t in_off = SIZE_MAX; std::vector<unsigned char> bytes; };
+    CachedMember cache[2];                    // the last two members of the previous stretch: the next selected target often begins in them
+
+    bool have_block(size_t i) {               // is there a member i?  (walks the headers up to it)
+        while (i >= blocks.size() && walked < map_len) {
+            size_t bsize; uint32_t isize;
+            if (!bgzf_member(ByteSpan{map, map_len}, walked, bsize, isize)) throw Error(FLORIA_E_INVALID, path + " is not a valid BGZF/gzip file");
+            blocks.push_back({walked, bsize, blocks.empty() ? 0 : blocks.back().out_off + blocks.back().out_len, isize});
+            walked += bsize;
+        }
+        return i < blocks.size();
+    }
     BamFile whole;                            // fallback: the file read at once
     bool whole_given = false;
     std::vector<std::string> names;
@@ -540,28 +629,188 @@ struct BamStream::Impl {
     bool eof = false;
     size_t peak = 0;
 
-    void inflate_range(size_t b0, size_t b1, unsigned char* dst) const {          // members [b0, b1) -> dst (contiguous)
+    void inflate_range(size_t b0, size_t b1, unsigned char* dst) const { inflate_range(blocks, b0, b1, dst); }
+    void inflate_run(const std::vector<BgzfBlock>& blocks, size_t b0, size_t b1, unsigned char* dst) const {            // members [b0, b1) -> dst (contiguous), on this thread
         const size_t base = blocks[b0].out_off;
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) throw Error(FLORIA_E_NOMEM, "inflateInit2 failed");
+        for (size_t b = b0; b < b1; ++b) {
+            const BgzfBlock& k = blocks[b];
+            zs.next_in = const_cast<unsigned char*>(map) + k.in_off; zs.avail_in = (uInt)k.in_len;
+            unsigned char dummy;
+            zs.next_out = k.out_len ? dst + (k.out_off - base) : &dummy; zs.avail_out = (uInt)k.out_len;
+            const int rc = inflate(&zs, Z_FINISH);
+            if (rc != Z_STREAM_END || zs.avail_out != 0) { inflateEnd(&zs); throw Error(FLORIA_E_INVALID, path + " is not a valid BGZF/gzip file"); }
+            inflateReset(&zs);
+        }
+        inflateEnd(&zs);
+    }
+    void inflate_range(const std::vector<BgzfBlock>& blocks, size_t b0, size_t b1, unsigned char* dst) const {          // the same on the threads
         const size_t per = 32;
         parallel_tasks((b1 - b0 + per - 1) / per, threads, [&](size_t t) {
-            z_stream zs;
-            memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) throw Error(FLORIA_E_NOMEM, "inflateInit2 failed");
-            for (size_t b = b0 + t * per; b < std::min(b1, b0 + (t + 1) * per); ++b) {
-                const BgzfBlock& k = blocks[b];
-                zs.next_in = const_cast<unsigned char*>(map) + k.in_off; zs.avail_in = (uInt)k.in_len;
-                unsigned char dummy;
-                zs.next_out = k.out_len ? dst + (k.out_off - base) : &dummy; zs.avail_out = (uInt)k.out_len;
-                const int rc = inflate(&zs, Z_FINISH);
-                if (rc != Z_STREAM_END || zs.avail_out != 0) { inflateEnd(&zs); throw Error(FLORIA_E_INVALID, path + " is not a valid BGZF/gzip file"); }
-                inflateReset(&zs);
-            }
-            inflateEnd(&zs);
+            const size_t k0 = b0 + t * per, k1 = std::min(b1, b0 + (t + 1) * per);
+            inflate_run(blocks, k0, k1, dst + (blocks[k0].out_off - blocks[b0].out_off));
         });
+    }
+
+    // ---- reading through the index.  A stretch is what the file holds of one selected target: from the virtual offset the index gives for its first record
+    // up to the first record of another target, the unplaced tail or the end of the file.  The index's end offset says which members to inflate (all stretches
+    // of a segment side by side, into one buffer); where a stretch really ends is read from its records, with members of look-ahead where the index's end is
+    // the end of a member or short of the truth.
+    struct Stretch {
+        int32_t tid = 0;
+        size_t u0 = 0;                          // the first record's offset inside the first member
+        std::vector<BgzfBlock> bl;              // the members from the first one on, out_off counted from its first inflated byte
+        size_t n_hint = 0, at = 0;              // bl[0, n_hint) are in the region; `at`: file offset behind bl.back()
+        size_t roff = 0, rlen = 0;              // the region: inflated bytes of bl[0, n_hint) in the segment's buffer
+        size_t lead = 0;                        // leading members the stretch before it (or the cache) already holds: copied, not inflated
+        size_t rec_end = 0;                     // buffer offset behind the last whole record of tid inside the region
+        std::vector<unsigned char> tail;        // the region's bytes from rec_end on and the look-ahead members behind them
+        size_t tail_recs = 0;                   // bytes of whole records of tid at the front of `tail`
+    };
+    Error bad_index(int32_t t, const std::string& why) const {
+        return Error(FLORIA_E_INVALID, bai.path + ": " + why + " (target " + names[(size_t)t] + " of " + path + "); rebuild the index, or run with --no-index");
+    }
+    bool stretch_more(Stretch& s) const {         // the header of one more member; false at the end of the file
+        if (s.at >= map_len) return false;
+        size_t bsize; uint32_t isize;
+        if (!bgzf_member(ByteSpan{map, map_len}, s.at, bsize, isize)) {
+            if (s.bl.empty()) throw bad_index(s.tid, "the offset of the first record does not land on the start of a BGZF member");
+            throw Error(FLORIA_E_INVALID, path + " is not a valid BGZF/gzip file");
+        }
+        s.bl.push_back({s.at, bsize, s.bl.empty() ? 0 : s.bl.back().out_off + s.bl.back().out_len, isize});
+        s.at += bsize;
+        return true;
+    }
+    Stretch plan_stretch(int32_t t) const {
+        const BaiIndex::Target& T = bai.targets[(size_t)t];
+        const size_t c0 = (size_t)(T.begin >> 16), ce = (size_t)(T.end >> 16), ue = (size_t)(T.end & 0xffff);
+        if (c0 >= map_len) throw bad_index(t, "the offset of the first record lies beyond the file");
+        Stretch s;
+        s.tid = t; s.u0 = (size_t)(T.begin & 0xffff); s.at = c0;
+        stretch_more(s);
+        if (s.u0 > s.bl[0].out_len) throw bad_index(t, "the offset of the first record lies beyond its BGZF member");
+        if (ce <= map_len) while (s.at < map_len && (s.at < ce || (s.at == ce && ue > 0))) stretch_more(s);      // (an end beyond the file is no hint)
+        s.n_hint = s.bl.size();
+        s.rlen = s.bl.back().out_off + s.bl.back().out_len;
+        return s;
+    }
+    // whole records of `tid` in [p + o, p + n): o moves behind them; true: a record of another target (or an unplaced one) follows, the stretch is complete
+    bool scan_stretch(const Stretch& s, const unsigned char* p, size_t n, size_t& o, bool& first) const {
+        while (o + 8 <= n) {
+            uint32_t bs; memcpy(&bs, p + o, 4);
+            int32_t tid; memcpy(&tid, p + o + 4, 4);
+            if (tid != s.tid) { if (first) throw bad_index(s.tid, "the record at the offset of the first record belongs to another target"); return true; }
+            if (bs < 32) throw Error(FLORIA_E_INVALID, path + ": malformed BAM record");
+            if (o + 4 + (size_t)bs > n) break;
+            first = false;
+            o += 4 + (size_t)bs;
+        }
+        return false;
+    }
+    // member k of a stretch's list where a neighbour already holds its bytes: in the region of `other` (buf) or in the cache; null: it has to be inflated
+    const unsigned char* held(const BgzfBlock& m, const Stretch* other, const unsigned char* buf) const {
+        if (other) for (size_t k = 0; k < other->n_hint; ++k) {
+            if (other->bl[k].in_off > m.in_off) break;
+            if (other->bl[k].in_off == m.in_off && other->bl[k].out_len == m.out_len) return buf + other->roff + other->bl[k].out_off;
+        }
+        for (const CachedMember& c : cache) if (c.in_off == m.in_off && c.bytes.size() == m.out_len) return c.bytes.empty() ? buf : c.bytes.data();
+        return nullptr;
+    }
+    // The records of the planned stretches -> buf, target after target
+    void read_stretches(std::vector<Stretch>& S, std::vector<unsigned char>& buf) {
+        size_t total = 0;
+        for (Stretch& s : S) { s.roff = total; total += s.rlen; }
+        buf.resize(total);
+        // one pass over every member of every stretch on the threads, but for the leading members that the stretch before holds as its last ones (a target
+        // begins in the member the one before it ends in) or that the cache holds from the segment before
+        struct Job { size_t s, k0, k1; };
+        std::vector<Job> jobs;
+        const size_t per = 8;
+        for (size_t i = 0; i < S.size(); ++i) {
+            Stretch& s = S[i];
+            const Stretch* before = i ? &S[i - 1] : nullptr;
+            while (s.lead < s.n_hint && held(s.bl[s.lead], before, buf.data())) ++s.lead;
+            for (size_t k = s.lead; k < s.n_hint; k += per) jobs.push_back({i, k, std::min(s.n_hint, k + per)});
+            members_inflated += s.n_hint - s.lead;
+        }
+        parallel_tasks(jobs.size(), threads, [&](size_t j) {
+            const Stretch& s = S[jobs[j].s];
+            inflate_run(s.bl, jobs[j].k0, jobs[j].k1, buf.data() + s.roff + s.bl[jobs[j].k0].out_off);
+        });
+        for (size_t i = 0; i < S.size(); ++i)                                       // (ascending: the stretch before is whole when its bytes are taken)
+            for (size_t k = 0; k < S[i].lead; ++k) {
+                const BgzfBlock& m = S[i].bl[k];
+                if (m.out_len) memcpy(buf.data() + S[i].roff + m.out_off, held(m, i ? &S[i - 1] : nullptr, buf.data()), m.out_len);
+            }
+        peak = std::max(peak, buf.size());
+        // where every stretch ends
+        bool any_tail_records = false;
+        for (size_t i = 0; i < S.size(); ++i) {
+            Stretch& s = S[i];
+            size_t o = s.u0;
+            bool first = true;
+            bool ended = scan_stretch(s, buf.data() + s.roff, s.rlen, o, first);
+            s.rec_end = s.roff + o;
+            if (ended) continue;
+            // the region ends with the stretch's last record, or inside a record: look ahead, first in what the next stretch or the cache holds
+            s.tail.assign(buf.begin() + (ptrdiff_t)s.rec_end, buf.begin() + (ptrdiff_t)(s.roff + s.rlen));
+            size_t p = 0, look = 1;
+            while (!ended) {
+                const size_t had = s.bl.size();
+                for (size_t k = 0; k < look && stretch_more(s); ++k) {}
+                if (s.bl.size() == had) {
+                    if (p != s.tail.size()) throw Error(FLORIA_E_INVALID, path + " is truncated");
+                    if (first) throw bad_index(s.tid, "there is no record at the offset of the first record");
+                    break;
+                }
+                look *= 2;
+                for (size_t k = had; k < s.bl.size(); ++k) {
+                    const BgzfBlock& m = s.bl[k];
+                    const size_t at = s.tail.size();
+                    s.tail.resize(at + m.out_len);
+                    const unsigned char* src = held(m, i + 1 < S.size() ? &S[i + 1] : nullptr, buf.data());
+                    if (src) { if (m.out_len) memcpy(s.tail.data() + at, src, m.out_len); }
+                    else { inflate_run(s.bl, k, k + 1, s.tail.data() + at); ++members_inflated; }
+                }
+                ended = scan_stretch(s, s.tail.data(), s.tail.size(), p, first);
+            }
+            s.tail_recs = p;
+            any_tail_records |= p != 0;
+        }
+        // the last two members of the last stretch stay at hand: the first target of the next segment often begins in them
+        if (!S.empty()) {
+            const Stretch& s = S.back();
+            CachedMember keep[2];
+            for (size_t j = 0; j < 2 && j < s.bl.size(); ++j) {
+                const size_t k = s.bl.size() - 1 - j;
+                const BgzfBlock& m = s.bl[k];
+                const unsigned char* src = k < s.n_hint ? buf.data() + s.roff + m.out_off
+                                                        : s.tail.data() + (s.roff + s.rlen - s.rec_end) + (m.out_off - s.bl[s.n_hint].out_off);
+                keep[j].in_off = m.in_off;
+                keep[j].bytes.assign(src, src + m.out_len);
+            }
+            for (size_t j = 0; j < 2; ++j) cache[j] = std::move(keep[j]);
+        }
+        // the records of the stretches, one behind the other
+        if (!any_tail_records) {
+            size_t d = 0;
+            for (const Stretch& s : S) { const size_t n = s.rec_end - (s.roff + s.u0); memmove(buf.data() + d, buf.data() + s.roff + s.u0, n); d += n; }
+            buf.resize(d);
+        } else {                                       // (an index whose end offsets fall short: records came by look-ahead)
+            std::vector<unsigned char> out;
+            for (const Stretch& s : S) {
+                out.insert(out.end(), buf.begin() + (ptrdiff_t)(s.roff + s.u0), buf.begin() + (ptrdiff_t)s.rec_end);
+                out.insert(out.end(), s.tail.begin(), s.tail.begin() + (ptrdiff_t)s.tail_recs);
+            }
+            peak = std::max(peak, buf.size() + out.size());
+            buf.swap(out);
+        }
     }
 };
 
-BamStream::BamStream(const std::string& path, size_t threads) : p_(new Impl) {
+BamStream::BamStream(const std::string& path, size_t threads, bool use_index) : p_(new Impl) {
     Impl& I = *p_;
     I.path = path; I.threads = std::max<size_t>(1, threads);
     I.fd = open(path.c_str(), O_RDONLY);
@@ -572,7 +821,20 @@ BamStream::BamStream(const std::string& path, size_t threads) : p_(new Impl) {
     void* m = mmap(nullptr, I.map_len, PROT_READ, MAP_PRIVATE, I.fd, 0);
     if (m == MAP_FAILED) throw Error(FLORIA_E_INVALID, "cannot map " + path);
     I.map = (const unsigned char*)m;
-    I.bgzf = bgzf_index(ByteSpan{I.map, I.map_len}, I.blocks) && !I.blocks.empty();
+    const std::string bai_path = use_index ? find_bai(path) : std::string();
+    size_t bsize0; uint32_t isize0;
+    if (!bai_path.empty() && bgzf_member(ByteSpan{I.map, I.map_len}, 0, bsize0, isize0)) {
+        // with an index the member headers are walked as far as the reading gets, not to the end of the file
+        I.bai = read_bai(bai_path);
+        I.indexed = I.bgzf = true;
+        struct stat sx;
+        if (stat(bai_path.c_str(), &sx) == 0 && (sx.st_mtim.tv_sec < st.st_mtim.tv_sec || (sx.st_mtim.tv_sec == st.st_mtim.tv_sec && sx.st_mtim.tv_nsec < st.st_mtim.tv_nsec)))
+            fprintf(stderr, "floria-hip: warning: the index %s is older than %s; it is used all the same (rebuild it, or run with --no-index, if the BAM was written again since)\n",
+                    bai_path.c_str(), path.c_str());
+    } else {
+        I.bgzf = bgzf_index(ByteSpan{I.map, I.map_len}, I.blocks) && !I.blocks.empty();
+        if (I.bgzf) I.walked = I.map_len;
+    }
     if (!I.bgzf) {                                   // plain gzip (or anything else zlib understands): no member index, the file is read whole
         I.whole = read_bam(path, threads);
         I.names = I.whole.target_names; I.lens = I.whole.target_len;
@@ -583,7 +845,7 @@ BamStream::BamStream(const std::string& path, size_t threads) : p_(new Impl) {
     std::vector<unsigned char> head;
     size_t b1 = 0;
     auto have = [&](size_t need) {
-        while (head.size() < need && b1 < I.blocks.size()) {
+        while (head.size() < need && I.have_block(b1)) {
             const size_t o = head.size();
             head.resize(o + I.blocks[b1].out_len);
             if (I.blocks[b1].out_len) { std::vector<unsigned char> tmp(I.blocks[b1].out_len); I.inflate_range(b1, b1 + 1, tmp.data()); memcpy(head.data() + o, tmp.data(), tmp.size()); }
@@ -607,8 +869,17 @@ BamStream::BamStream(const std::string& path, size_t threads) : p_(new Impl) {
     }
     // the records start at inflated offset o: find its member
     size_t b = 0;
-    while (b < I.blocks.size() && I.blocks[b].out_off + I.blocks[b].out_len <= o) ++b;
-    I.first_block = b; I.first_skip = b < I.blocks.size() ? o - I.blocks[b].out_off : 0;
+    while (I.have_block(b) && I.blocks[b].out_off + I.blocks[b].out_len <= o) ++b;
+    I.first_block = b; I.first_skip = I.have_block(b) ? o - I.blocks[b].out_off : 0;
+    if (I.indexed) {
+        if (I.bai.targets.size() != I.names.size())
+            throw Error(FLORIA_E_INVALID, I.bai.path + " indexes " + std::to_string(I.bai.targets.size()) + " reference sequences, the header of " + path + " has " +
+                                          std::to_string(I.names.size()) + ": it is the index of another file");
+        for (size_t t = 0; t < I.bai.targets.size(); ++t)
+            if (I.bai.targets[t].has_records && (I.bai.targets[t].begin >> 16) >= I.map_len)
+                throw Error(FLORIA_E_INVALID, I.bai.path + ": the offset of the first record of target " + I.names[t] + " lies beyond the end of " + path +
+                                              "; rebuild the index, or run with --no-index");
+    }
     rewind();
 }
 BamStream::~BamStream() {
@@ -617,11 +888,29 @@ BamStream::~BamStream() {
 }
 const std::vector<std::string>& BamStream::target_names() const { return p_->names; }
 size_t BamStream::peak_buffer_bytes() const { return p_->peak; }
+const std::string& BamStream::index_path() const { return p_->bai.path; }
+void BamStream::select(const std::vector<int32_t>& tids) {
+    Impl& I = *p_;
+    if (!I.indexed) return;
+    I.sel = tids;
+    std::sort(I.sel.begin(), I.sel.end());
+    I.sel.erase(std::unique(I.sel.begin(), I.sel.end()), I.sel.end());
+    if (!I.sel.empty() && (I.sel.front() < 0 || (size_t)I.sel.back() >= I.names.size())) throw Error(FLORIA_E_INVALID, "BamStream::select: no such target");
+    I.selecting = true; I.sel_done = false; I.sel_pos = 0; I.done_upto = 0; I.members_inflated = 0;
+    I.carry.clear();
+    for (Impl::CachedMember& m : I.cache) m = Impl::CachedMember();
+}
+BamStream::IndexUse BamStream::index_use() const {
+    Impl& I = *p_;
+    try { I.have_block(SIZE_MAX); } catch (const Error&) {}            // (a member the reading never reached: counted up to it)
+    return {I.sel.size(), I.members_inflated, I.blocks.size()};
+}
 void BamStream::rewind() {
     Impl& I = *p_;
     if (!I.bgzf) { if (I.whole_given) { I.whole = read_bam(I.path, I.threads); I.whole.tid_begin = 0; I.whole.tid_end = (int32_t)I.names.size(); } I.whole_given = false; return; }
     I.bi = I.first_block; I.carry.clear(); I.done_upto = 0; I.last_tid_seen = 0; I.eof = false;
-    if (I.bgzf && I.first_block < I.blocks.size() && I.first_skip) {       // the rest of the member the header ends in
+    I.sel_pos = 0; I.sel_done = false;
+    if (I.bgzf && I.have_block(I.first_block) && I.first_skip) {       // the rest of the member the header ends in
         std::vector<unsigned char> tmp(I.blocks[I.first_block].out_len);
         I.inflate_range(I.first_block, I.first_block + 1, tmp.data());
         I.carry.assign(tmp.begin() + (ptrdiff_t)I.first_skip, tmp.end());
@@ -639,13 +928,37 @@ bool BamStream::next(BamFile& seg, size_t min_bytes) {
         I.peak = std::max(I.peak, seg.raw.size());
         return true;
     }
-    if (I.eof && I.done_upto >= n_targets) return false;
     std::vector<unsigned char> buf;
+    if (I.selecting) {
+        // the selected targets in header order, each from its indexed offset, as many as the window takes; the targets between them have no records here
+        if (I.sel_done) return false;
+        int32_t upto = I.done_upto;
+        bool any = false;
+        std::vector<Impl::Stretch> stretches;
+        size_t planned = 0;
+        while (I.sel_pos < I.sel.size() && (!any || planned < min_bytes)) {
+            const int32_t t = I.sel[I.sel_pos++];
+            if (I.bai.targets[(size_t)t].has_records) { stretches.push_back(I.plan_stretch(t)); planned += stretches.back().rlen; }
+            upto = t + 1; any = true;
+        }
+        I.read_stretches(stretches, buf);
+        if (I.sel_pos >= I.sel.size()) { upto = n_targets; I.sel_done = true; }
+        seg = BamFile();
+        seg.target_names = I.names; seg.target_len = I.lens;
+        seg.by_tid.resize(I.names.size());
+        seg.raw = std::move(buf);
+        I.peak = std::max(I.peak, seg.raw.size());
+        decode_records(seg, 0, seg.raw.size(), I.path, I.threads);
+        seg.tid_begin = I.done_upto; seg.tid_end = upto;
+        I.done_upto = upto;
+        return true;
+    }
+    if (I.eof && I.done_upto >= n_targets) return false;
     size_t want = std::max<size_t>(min_bytes, 1 << 16);
     for (;;) {
         // ---- inflate members until the buffer holds `want` bytes (or the file ends)
         size_t b1 = I.bi, add = 0;
-        while (b1 < I.blocks.size() && I.carry.size() + buf.size() + add < want) add += I.blocks[b1++].out_len;
+        while (I.have_block(b1) && I.carry.size() + buf.size() + add < want) add += I.blocks[b1++].out_len;
         if (buf.empty()) { buf.swap(I.carry); I.carry.clear(); }
         if (b1 > I.bi) {
             const size_t o = buf.size();
@@ -653,7 +966,7 @@ bool BamStream::next(BamFile& seg, size_t min_bytes) {
             I.inflate_range(I.bi, b1, buf.data() + o);
             I.bi = b1;
         }
-        const bool at_end = I.bi >= I.blocks.size();
+        const bool at_end = !I.have_block(I.bi);
         // ---- walk the records: [0, cut) = whole records of targets that are certainly complete
         size_t o = 0, last_start_of_tid = 0, whole_end = 0;
         int32_t cur_tid = INT32_MIN, prev = I.last_tid_seen;
@@ -690,7 +1003,7 @@ bool BamStream::next(BamFile& seg, size_t min_bytes) {
         seg.tid_begin = I.done_upto; seg.tid_end = complete_upto;
         I.done_upto = complete_upto;
         I.last_tid_seen = std::max(I.last_tid_seen, std::min(prev, n_targets));
-        if (closing) { I.eof = true; I.carry.clear(); I.bi = I.blocks.size(); }
+        if (closing) { I.eof = true; I.carry.clear(); }
         return true;
     }
 }

@@ -29,6 +29,8 @@
 // keeps the haplosets there as a handle; the lists come back once (floria_hip_haplosets_download) for the writers and the four calls take the handle (the allele tables and
 // trims of a batch that mixes contigs with and without a handle of their own still go by lists).  Same files.
 // For tests: --dump-plan FILE (with --ingest-only, any route: the fragment plan per contig), --dump-handles FILE (any route: the resident arrays of every contig of every batch).
+// --no-index: a .bai beside the BAM (X.bam.bai, then X.bai) is used when present - the contigs that -G and --snp-count-filter leave are read through it, each from its
+// indexed offset, and the log gains one line (contigs selected, BGZF members inflated, members in the file); --no-index streams the whole file in order as without one.  Same files.
 // --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
 // RULE max | sum, TIE right | down): one member of the family of fixed-block walks (block 8) that scripts/probes/block_walk.c defines.  The reference's block-aligner is
 // some heuristic of this kind; which member, if any, is not known, so there is no bare `block`.  The run's log and cmd.log name the scoring used.
@@ -156,6 +158,11 @@ struct RunStats {
         const Options& o = cli.o;
         std::string buf;
         fprintf(stderr, "BAM: %zu records in %zu segments, %.3fs of inflate + decode, largest inflated buffer %zu MiB\n", n_records, n_segments, t_stream, stream.peak_buffer_bytes() >> 20);
+        if (!stream.index_path().empty()) {
+            const BamStream::IndexUse u = stream.index_use();
+            fprintf(stderr, "BAM index %s: %zu targets selected, %zu BGZF members inflated for them of %zu in the file\n", stream.index_path().c_str(), u.selected, u.members_inflated,
+                    u.members_in_file);
+        }
         const bool behind_walk = realigned_behind_walk(o.pileup, cli.no_realign);
         if (!behind_walk || n_realign_device)                                     // (fused, resident: only the contigs that kept the host walk queue windows)
         fprintf(stderr, "Realignment: %zu calls scored on the device in %.3fs (inside the ingest time), scoring %s\n", n_realign_device, t_realign, scoring_name(o, buf));
@@ -565,7 +572,8 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Preprocessing VCF/Reference\n");
         double tp = now_s();
         // the BAM is streamed: the records of a run of complete contigs at a time (about --bam-window-mb of inflated records), never the whole file
-        BamStream stream(o.bam_file, std::max<size_t>(1, o.num_threads));
+        // with an index beside it (unless --no-index) only the contigs that will be phased are read, each from its indexed offset
+        BamStream stream(o.bam_file, std::max<size_t>(1, o.num_threads), !cli.no_index);
         double t_bam = now_s() - tp;
         const Arithmetic arith = epsilon_policy(cli, stream, t_bam);
         if (!cli.ingest_only) write_run_files(o, argc, argv, arith.run_note);
@@ -580,6 +588,11 @@ int main(int argc, char** argv) {
 
         Run run(cli, vp, fasta, contigs, sessions, arith.reference_arith);
         if (!cli.ingest_only) check_contigs_in_fasta(run);
+        if (!stream.index_path().empty()) {           // the predicate of contigs_of_segment, which still sees every target and gives its warning
+            std::vector<int32_t> tids;
+            for (size_t tid = 0; tid < contigs.size(); ++tid) if (run.listed(contigs[tid]) && run.enough_snps(contigs[tid])) tids.push_back((int32_t)tid);
+            stream.select(tids);
+        }
         BamFile bam;                                  // the current segment: every record of the contigs [tid_begin, tid_end)
         for (;;) {
             { const double ts = now_s(); const bool more = stream.next(bam, cli.bam_window); stats.t_stream += now_s() - ts; if (!more) break; }

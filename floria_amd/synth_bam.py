@@ -61,17 +61,131 @@ def bam_record(tid, pos, name, flag, mapq, cigar, seq, qual, next_pos=-1, tlen=0
     return struct.pack("<I", len(body)) + body
 
 
-def write_bam(path, targets, records):
-    """targets: [(name, length)]; records: already coordinate-sorted list of bam_record() bytes."""
+def write_bam(path, targets, records, block_bytes=60000):
+    """targets: [(name, length)]; records: already coordinate-sorted list of bam_record() bytes.  block_bytes: inflated bytes per BGZF member
+    (a small value gives a small file many members, records that straddle them and targets that begin inside one)."""
+    if not 1 <= block_bytes <= 65280:
+        raise ValueError("block_bytes must be 1 .. 65280")
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{ln}\n" for n, ln in targets)
     head = b"BAM\1" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(targets))
     for n, ln in targets:
         head += struct.pack("<I", len(n) + 1) + n.encode() + b"\0" + struct.pack("<I", ln)
     raw = head + b"".join(records)
     with open(path, "wb") as f:
-        for o in range(0, len(raw), 60000):
-            f.write(_bgzf_block(raw[o:o + 60000]))
+        for o in range(0, len(raw), block_bytes):
+            f.write(_bgzf_block(raw[o:o + block_bytes]))
         f.write(_bgzf_block(b""))                               # EOF marker
+
+
+def _bgzf_members(packed):
+    """-> [(file offset, inflated offset)] of every BGZF member, and the inflated bytes of the whole file"""
+    members, parts, o, out = [], [], 0, 0
+    while o < len(packed):
+        if packed[o:o + 4] != b"\x1f\x8b\x08\x04":
+            raise ValueError(f"no BGZF member at byte {o}")
+        xlen, = struct.unpack_from("<H", packed, o + 10)
+        x, bsize = o + 12, None
+        while x + 4 <= o + 12 + xlen:
+            si1, si2, slen = struct.unpack_from("<BBH", packed, x)
+            if (si1, si2, slen) == (66, 67, 2):
+                bsize = struct.unpack_from("<H", packed, x + 4)[0] + 1
+            x += 4 + slen
+        if bsize is None:
+            raise ValueError(f"the gzip member at byte {o} has no BC subfield")
+        data = zlib.decompress(packed[o + 12 + xlen:o + bsize - 8], -15)
+        members.append((o, out))
+        parts.append(data)
+        o += bsize
+        out += len(data)
+    return members, b"".join(parts)
+
+
+def write_bai(bam_path, bai_path=None, pseudo_bin=True):
+    """Write the BAI index (SAM specification 5.2) of a coordinate-sorted BAM, by default as bam_path + ".bai"; -> its path.  Bins by _reg2bin with the
+    chunks of a bin merged where they meet in one BGZF member, the linear index at 16 kbp windows, the metadata pseudo-bin 37450 unless pseudo_bin=False
+    (not every indexer writes it), and the count of unplaced reads behind the last reference."""
+    import bisect
+    with open(bam_path, "rb") as f:
+        packed = f.read()
+    members, raw = _bgzf_members(packed)
+    starts = [m[1] for m in members]
+
+    def voffset(p):                     # of inflated position p; the end of a member is the start of the next one, as bgzf_tell gives it
+        k = bisect.bisect_right(starts, p) - 1
+        return (members[k][0] << 16) | (p - members[k][1])
+
+    if raw[:4] != b"BAM\1":
+        raise ValueError(f"{bam_path} is not a BAM file")
+    l_text, = struct.unpack_from("<I", raw, 4)
+    o = 8 + l_text
+    n_ref, = struct.unpack_from("<I", raw, o)
+    o += 4
+    for _ in range(n_ref):
+        l_name, = struct.unpack_from("<I", raw, o)
+        o += 4 + l_name + 4
+    bins = [dict() for _ in range(n_ref)]          # bin -> [[begin, end]]
+    linear = [dict() for _ in range(n_ref)]        # window -> smallest voffset
+    meta = [None] * n_ref                          # [ref_beg, ref_end, n_mapped, n_unmapped]
+    last_bin = [None] * n_ref
+    n_no_coor = 0
+    prev = (0, -1)
+    while o < len(raw):
+        block_size, = struct.unpack_from("<I", raw, o)
+        tid, pos, _l_name, _mapq, _bin, n_cigar, flag, _l_seq = struct.unpack_from("<iiBBHHHI", raw, o + 4)
+        beg_v, end_v = voffset(o), voffset(o + 4 + block_size)
+        if tid < 0:
+            n_no_coor += 1
+            prev = (n_ref, 0)
+            o += 4 + block_size
+            continue
+        if (tid, pos) < prev:
+            raise ValueError(f"{bam_path} is not sorted by coordinate")
+        prev = (tid, pos)
+        l_name = raw[o + 12]
+        cig = struct.unpack_from(f"<{n_cigar}I", raw, o + 36 + l_name)
+        end = pos + max(1, sum(c >> 4 for c in cig if (c & 15) in (0, 2, 3, 7, 8)))
+        b = _reg2bin(pos, end)
+        chunks = bins[tid].setdefault(b, [])
+        if last_bin[tid] == b and chunks:
+            chunks[-1][1] = end_v                   # the run of records of one bin is one chunk
+        else:
+            chunks.append([beg_v, end_v])
+        last_bin[tid] = b
+        for w in range(pos >> 14, ((end - 1) >> 14) + 1):
+            linear[tid].setdefault(w, beg_v)
+        m = meta[tid]
+        if m is None:
+            m = meta[tid] = [beg_v, end_v, 0, 0]
+        m[1] = end_v
+        m[3 if flag & 4 else 2] += 1
+        o += 4 + block_size
+    out = [b"BAI\1", struct.pack("<I", n_ref)]
+    for tid in range(n_ref):
+        n_bin = len(bins[tid]) + (1 if pseudo_bin and meta[tid] is not None else 0)
+        out.append(struct.pack("<I", n_bin))
+        for b in sorted(bins[tid]):
+            merged = []
+            for beg_v, end_v in bins[tid][b]:
+                if merged and merged[-1][1] >> 16 >= beg_v >> 16:
+                    merged[-1][1] = max(merged[-1][1], end_v)
+                else:
+                    merged.append([beg_v, end_v])
+            out.append(struct.pack("<II", b, len(merged)))
+            out.extend(struct.pack("<QQ", *c) for c in merged)
+        if pseudo_bin and meta[tid] is not None:
+            out.append(struct.pack("<IIQQQQ", 37450, 2, *meta[tid]))
+        n_intv = max(linear[tid]) + 1 if linear[tid] else 0
+        ioffset = [linear[tid].get(w) for w in range(n_intv)]
+        for w in range(n_intv - 2, -1, -1):         # a window no record starts in or overlaps takes the next one's offset
+            if ioffset[w] is None:
+                ioffset[w] = ioffset[w + 1]
+        out.append(struct.pack("<I", n_intv))
+        out.extend(struct.pack("<Q", v) for v in ioffset)
+    out.append(struct.pack("<Q", n_no_coor))
+    bai_path = bai_path or bam_path + ".bai"
+    with open(bai_path, "wb") as f:
+        f.write(b"".join(out))
+    return bai_path
 
 
 def contig_dataset(contig, rng, edit_frac=0.1, mapq=60, sub_rate=0.0):
@@ -312,9 +426,9 @@ def realign_dataset(d, flank=16, walk=None):
     return changed
 
 
-def write_dataset(prefix, contigs, seed=0, extra_vcf_lines=True, edit_frac=0.1, realign=True, sub_rate=0.0, walk=None):
+def write_dataset(prefix, contigs, seed=0, extra_vcf_lines=True, edit_frac=0.1, realign=True, sub_rate=0.0, walk=None, index=False, block_bytes=60000):
     """Write {prefix}.bam / .vcf / .fa for a list of synth Contigs (keep_layout=True).  With realign=False the returned pileups hold the
-    calls as sequenced (floria-hip --no-realign), with walk = (step, rule, tie) the calls as floria-hip --realign block:STEP,RULE,TIE makes them.  Returns, per contig name,
+    calls as sequenced (floria-hip --no-realign), with walk = (step, rule, tie) the calls as floria-hip --realign block:STEP,RULE,TIE makes them.  index=True also writes {prefix}.bam.bai (write_bai); block_bytes is write_bam's.  Returns, per contig name,
     dict(pileup=Pileup in the order a correct ingest produces, names=[read name], spans=[(first_pos_base, last_pos_base)], segments=[[SNPs of alignment k]],
          snp_pos0=[0-based genome position of every SNP], contig_len, seq_len=[bases of every read])."""
     rng = np.random.default_rng(seed)
@@ -375,5 +489,7 @@ def write_dataset(prefix, contigs, seed=0, extra_vcf_lines=True, edit_frac=0.1, 
                               snpless=[(nm, sp, sl) for nm, cells, sp, _, sl in reads if not cells],
                               alignments=sorted([(pos, seq, cig) for _, _, _, recs_r, _ in d["reads"] for pos, _, seq, cig in recs_r], key=lambda t: t[0]))
     fa.close(); vcf.close()
-    write_bam(prefix + ".bam", targets, all_recs)
+    write_bam(prefix + ".bam", targets, all_recs, block_bytes=block_bytes)
+    if index:
+        write_bai(prefix + ".bam")
     return expect

@@ -13,6 +13,11 @@ N runs each, then the median and the spread of the phasing stage (upload + S1 + 
 their sum and the wall time per setting (profiles/paths_resident.md).
 --config K --epsilon X --block-length N: the data set's synth configuration (4 = long reads [default], 3 = paired short reads) and the run's -e / -l, e.g.
 --config 3 --epsilon 0.04 --block-length 500 for the paired set in the reference arithmetic.
+--index-compare N [--parent-exe PATH]: the data set with a .bai written by synth_bam.write_bai beside one copy of the BAM and none beside the other; N runs each,
+ALTERNATING, of (a) this build on the copy without an index against --parent-exe (a build of the parent commit) on the same file, (b) -G with the last three contigs
+through the index against --no-index, (c) no -G with a VCF thinned to 40 SNPs for every other contig (every contig of this set has the same number of SNPs, so that is
+what lets --snp-count-filter 50 drop half of them) through the index against --no-index; then median and spread of the wall time, of the seconds BamStream spent
+opening the file (the "BAM header" figure) and of its inflate + decode seconds, and the inflated-member counts (profiles/bam_index.md).
 --realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
 
 Writes BAM / VCF / FASTA under $TMPDIR, runs the driver twice and prints its stage-time lines (stderr of floria-hip)."""
@@ -45,6 +50,8 @@ def main():
     ap.add_argument("--haplosets-compare", type=int, default=0, help="only: the batched flow with --haplosets host and resident alternating, this many runs each")
     ap.add_argument("--paths-compare", type=int, default=0, help="only: the batched flow under --haplosets resident with --paths host and resident alternating, this many runs each")
     ap.add_argument("--pileup-route", default="host", help="with --haplosets-compare / --paths-compare: the --pileup route of every run")
+    ap.add_argument("--index-compare", type=int, default=0, help="only: indexed against unindexed reading of the BAM, and this build against --parent-exe, this many runs each")
+    ap.add_argument("--parent-exe", default=None, help="with --index-compare: floria-hip of the parent commit (comparison (a); left out when not given)")
     ap.add_argument("--config", type=int, default=4, help="synth configuration of the contigs (4: long reads, 3: paired short reads)")
     ap.add_argument("--epsilon", default="0.03125", help="-e of every run")
     ap.add_argument("--block-length", default="10000", help="-l of every run")
@@ -59,6 +66,8 @@ def main():
     synth_bam.write_dataset(prefix, cs, seed=1, realign=False, sub_rate=a.sub_rate)
     print(f"data set: {a.contigs} contigs, {sum(c.pileup.n_reads for c in cs)} reads, {sum(len(c.snp_pos) for c in cs)} SNPs, "
           f"BAM {os.path.getsize(prefix + '.bam') >> 20} MiB, written in {time.time() - t:.1f}s; host cores {os.cpu_count()}", flush=True)
+    if a.index_compare:
+        return index_compare(a, exe, tmp, prefix, cs)
     base = [exe, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-e", a.epsilon, "-l", a.block_length, "--snp-count-filter", "50"]
     runs = (("batched", ["-t", str(a.threads)]), ("batched, 1 thread", ["-t", "1"]), ("one contig per batch", ["-t", str(a.threads), "--batch-contigs", "1"]),
             ("ingest only: realign DP on the host", ["-t", str(a.threads), "--ingest-only"]), ("ingest only, 1 thread", ["-t", "1", "--ingest-only"]))
@@ -130,6 +139,61 @@ def main():
         if v and v[0]:
             med = lambda xs: sorted(xs)[len(xs) // 2]
             print(f"[{key}] device calls (medians): " + ", ".join(f"{k} {med([d[k] for d in v]):g}" for k in v[0]))
+
+
+def index_compare(a, exe, tmp, prefix, cs):
+    t = time.time()
+    indexed = os.path.join(tmp, "dx")                     # the same BAM under a second name, with an index beside it
+    os.symlink(prefix + ".bam", indexed + ".bam")
+    synth_bam.write_bai(prefix + ".bam", indexed + ".bam.bai")
+    thin = prefix + ".thin.vcf"                           # every other contig keeps 40 SNPs: --snp-count-filter 50 drops it
+    odd = {c.name for c in cs[1::2]}
+    seen = {}
+    with open(prefix + ".vcf") as f, open(thin, "w") as g:
+        for ln in f:
+            name = ln.split("\t", 1)[0]
+            if ln.startswith("#") or name not in odd:
+                g.write(ln)
+            else:
+                seen[name] = seen.get(name, 0) + 1
+                if seen[name] <= 40:
+                    g.write(ln)
+    print(f"index written and VCF thinned in {time.time() - t:.1f}s; index {os.path.getsize(indexed + '.bam.bai')} bytes", flush=True)
+    last3 = [c.name for c in cs[-3:]]
+
+    def cmd(binary, bam, vcf, extra):
+        return [binary, "-b", bam + ".bam", "-v", vcf, "-r", prefix + ".fa", "-e", a.epsilon, "-l", a.block_length, "--snp-count-filter", "50", "-t", str(a.threads),
+                "--pileup", a.pileup_route, *extra]
+    groups = []
+    if a.parent_exe:
+        groups.append(("(a) no index", (("this build", cmd(exe, prefix, prefix + ".vcf", [])), ("parent build", cmd(a.parent_exe, prefix, prefix + ".vcf", [])))))
+    groups.append(("(b) -G last three contigs", (("indexed", cmd(exe, indexed, prefix + ".vcf", ["-G", *last3])), ("--no-index", cmd(exe, indexed, prefix + ".vcf", ["--no-index", "-G", *last3])))))
+    groups.append(("(c) half the contigs under --snp-count-filter", (("indexed", cmd(exe, indexed, thin, [])), ("--no-index", cmd(exe, indexed, thin, ["--no-index"])))))
+    for title, pair in groups:
+        got = {label: [] for label, _ in pair}
+        members = {}
+        for k in range(a.index_compare):
+            for label, c in pair:
+                out = os.path.join(tmp, f"o_ix_{len(got[label])}_{label.replace(' ', '_')}")
+                t = time.time()
+                r = subprocess.run(c + ["-o", out], capture_output=True, text=True)
+                wall = time.time() - t
+                if r.returncode:
+                    print(r.stderr[-2000:])
+                    raise SystemExit(1)
+                opened = float(re.search(r"Preprocessing: BAM header\S* ([\d.]+)s", r.stderr).group(1))
+                stream = float(re.search(r"BAM: \d+ records in \d+ segments, ([\d.]+)s of inflate", r.stderr).group(1))
+                got[label].append((wall, opened, stream, opened + stream))
+                m = re.search(r"BAM index \S+: (\d+) targets selected, (\d+) BGZF members inflated for them of (\d+) in the file", r.stderr)
+                if m:
+                    members[label] = m.groups()
+                subprocess.run(["rm", "-rf", out])
+        for label, _ in pair:
+            for k, what in enumerate(("wall", "BamStream open", "BamStream inflate + decode", "BamStream open + inflate + decode")):
+                x = sorted(t[k] for t in got[label])
+                print(f"[{title}] [{label}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs", flush=True)
+            if label in members:
+                print(f"[{title}] [{label}] targets selected {members[label][0]}, BGZF members inflated {members[label][1]} of {members[label][2]}", flush=True)
 
 
 if __name__ == "__main__":
