@@ -179,7 +179,7 @@ BigCache g_big;
 
 // Tuning / test knobs of a context (floria_hip_set_option); the defaults are what bench.py measures.  Read from the environment
 // ONCE, at floria_hip_create (FLORIA_HIP_GROUPS, FLORIA_HIP_BEAM=generic|slab|wide, FLORIA_HIP_NO_SPECIALIZED, FLORIA_HIP_NO_P1_SHORTCUT,
-// FLORIA_HIP_OPT_THREADS, FLORIA_HIP_OPT_GLOBAL, FLORIA_HIP_SPECULATE); none of them changes results.
+// FLORIA_HIP_OPT_THREADS, FLORIA_HIP_OPT_GLOBAL, FLORIA_HIP_SPECULATE, FLORIA_HIP_FUSE_P1); none of them changes results.
 struct Knobs {
     uint32_t groups = 0;          // job groups (0 = auto: 2 when the batch has >= 48 x CUs non-empty blocks)
     uint32_t beam_path = 0;       // 0 auto | 1 generic | 2 slab | 3 wide
@@ -207,6 +207,8 @@ struct Knobs {
     int32_t  tail_overlap = 0;    // one ploidy per stage: the LAST ploidy's beam launch runs beside the optimise launch of the ploidy below, every job waiting for its block's
                                   // stop rule (run_phase): 0 off (default: measured level) | 1 on
     uint32_t tail_waves = 2;      // ... with this many waves per CU
+    int32_t  fuse_p1 = -1;        // one ploidy per stage, canonical arithmetic, max_ploidy >= 2, ploidy-1 shortcut on: ploidy 1 has no launch of its own, the ploidy-2 optimise job
+                                  // computes it from its own histogram (optimize_kernel.h, with_p1): -1 auto (on where eligible) | 0 off | 1 on where eligible
 };
 
 struct Arena;
@@ -730,7 +732,10 @@ int run_phase(floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S
     const uint64_t fx_ctrl = fl::fx_ctrl_bytes(span_max + 1), fx_slot = fl::fx_slot_bytes(span_max + 1), fx_bytes = fx_ctrl + fx_slot;       // (+1: slack)
     const int t_phase = T.begin(K_PHASE);
     // ploidy 1 (always position 0 of the first stage) without a search: its beam partition is all zeros, for every group's reads
-    if (plan[1].shortcut) { HIPCHK(hipMemsetAsync(D.beam_part, 0, tot_reads, ctx->stream)); p1_shortcut = true; }
+    // ... or without a launch at all (ploidy_stages left its stage out): the ploidy-2 optimise job stands for it, and plane 0 of D.planes was zeroed with the call's memset
+    const bool p1_fused = stages.front().front() == 2;
+    if (p1_fused) p1_shortcut = true;
+    else if (plan[1].shortcut) { HIPCHK(hipMemsetAsync(D.beam_part, 0, tot_reads, ctx->stream)); p1_shortcut = true; }
     // fork: every group's first lane starts after what the main stream has queued so far (uploads, memsets, block_reads_kernel)
     if (G > 1) {
         HIPCHK(hipEventRecord(ctx->ev_fork[0], ctx->stream));
@@ -833,6 +838,7 @@ int run_phase(floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S
                     a.stopping_heuristic = prm->stopping_heuristic; a.mec_threshold = mec_threshold(prm, p);
                     a.blk_done_w = D.done; a.best_ploidy = D.best; a.tried = D.tried;
                     a.release_tried = tail_p != 0 ? 1u : 0u;
+                    a.with_p1 = p1_fused && p == 2 ? 1u : 0u;
                     a.pm_lds_off = q.pm_lds_off;
                     // (a plan with ANY speculative stage publishes ready bits and stop_at from every stage: a later stage's stop rule compares with these MEC values)
                     if (K.arith) {
@@ -987,6 +993,7 @@ int floria_hip_create(int device, floria_hip_ctx** out) {
         if (const char* v = getenv("FLORIA_HIP_SPECULATE")) K.speculate = std::max(-1, std::min(3, atoi(v)));
         K.trace = getenv("FLORIA_HIP_TRACE") != nullptr;
         if (const char* v = getenv("FLORIA_HIP_TAIL_OVERLAP")) K.tail_overlap = std::max(-1, std::min(1, atoi(v)));
+        if (const char* v = getenv("FLORIA_HIP_FUSE_P1")) K.fuse_p1 = std::max(-1, std::min(1, atoi(v)));
         if (const char* v = getenv("FLORIA_HIP_TAIL_WAVES")) K.tail_waves = (uint32_t)std::max(1, std::min(16, atoi(v)));
         if (const char* v = getenv("FLORIA_HIP_SPEC_GATE_DIV")) K.spec_gate_div = (uint32_t)std::max(1, std::min(16, atoi(v)));
         if (const char* v = getenv("FLORIA_HIP_STAGE_THREADS")) c->stage_threads = (uint32_t)std::max(1, std::min(16, atoi(v)));
@@ -1070,6 +1077,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "no_bulk") K.no_bulk = value != 0;
     else if (k == "opt_block_order") K.opt_block_order = value != 0;
     else if (k == "tail_overlap") { if (value < -1 || value > 1) return fail(FLORIA_E_INVALID, "tail_overlap: 0 | 1"); K.tail_overlap = (int32_t)value; }
+    else if (k == "fuse_p1") { if (value < -1 || value > 1) return fail(FLORIA_E_INVALID, "fuse_p1: -1 auto | 0 | 1"); K.fuse_p1 = (int32_t)value; }
     else if (k == "tail_waves") K.tail_waves = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 16));
     else if (k == "arith_hbm") K.arith_hbm = value != 0;
     else if (k == "arith_replay") { K.arith_replay = value != 0; ctx->ord_epoch = ~0ull; }      // (the cell orders are computed again, the long way or the short one)
@@ -1886,6 +1894,9 @@ std::vector<std::vector<uint32_t>> ploidy_stages(const floria_hip_ctx* ctx, cons
                           if (P > 3) { stages.emplace_back(); for (uint32_t p = 4; p <= P; ++p) stages.back().push_back(p); } }
     else for (uint32_t p = 1; p <= P; ++p) stages.push_back({p});
     if (spec == 3 && P < 5) { stages.clear(); for (uint32_t p = 1; p <= P; ++p) stages.push_back({p}); }
+    // one ploidy per stage: ploidy 1 needs no stage of its own where the ploidy-2 optimise job computes it on the way (Knobs::fuse_p1; run_phase sees that no stage holds ploidy 1)
+    const Knobs& K = ctx->knobs;
+    if (stages.size() == P && P >= 2 && !K.arith && !K.no_p1_shortcut && K.fuse_p1 != 0) stages.erase(stages.begin());
     return stages;
 }
 
@@ -1985,13 +1996,16 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
 
     // ---- device staging of the per-call arrays ----------------------------------------------------------------------
     Carve C;
-    const Seg s_rids = C.seg(4ull * tot + 4), s_jobs = C.seg(4ull * jobs.size() + 4), s_planes = C.seg((uint64_t)P * tot + 16), s_bpart = C.seg((uint64_t)(stage_w + 1) * (tot + 16)),        // (+1: the plane of a last-stage beam launch that runs beside the optimise launch below it)
+    const Seg s_rids = C.seg(4ull * tot + 4), s_jobs = C.seg(4ull * jobs.size() + 4), s_bpart = C.seg((uint64_t)(stage_w + 1) * (tot + 16)),        // (+1: the plane of a last-stage beam launch that runs beside the optimise launch below it)
               s_margin = C.seg(8ull * n_blocks * P + 16),
               // zero-initialised, contiguous (ONE memset): partition output, mec / num_alleles / iters, stop-rule state, queue counters, diagnostics
               s_out = C.seg(tot + 16), s_mec = C.seg(8ull * n_blocks * P + 8), s_na = C.seg(8ull * n_blocks * P + 8), s_it = C.seg(4ull * n_blocks * P + 4),
               s_done = C.seg(n_blocks + 4), s_best = C.seg(4ull * n_blocks + 4), s_tried = C.seg(4ull * n_blocks + 4), s_ready = C.seg(4ull * n_blocks + 4),
               s_q = C.seg(8ull * floria_hip_ctx::MAX_LANES * FLORIA_MAX_PLOIDY + 16), s_diag = C.seg(16 + 8 * 64), s_steps = C.seg(16);
-    const size_t zero_bytes = C.cursor - s_out.off;
+    // the partition planes follow: where no launch computes ploidy 1 (ploidy_stages, Knobs::fuse_p1) its plane — every read in partition 0 — is the tail of the same memset
+    const bool p1_fused = stages.front().front() == 2;
+    const Seg s_planes = C.seg((uint64_t)P * tot + 16);
+    const size_t zero_bytes = s_planes.off + (p1_fused ? tot : 0) - s_out.off;
     const Seg s_stop = C.seg(4ull * n_blocks + 4);             // speculative stages: smallest ploidy at which the stop rule is known to break, 0xffffffff = unknown
     rc = C.place(ctx->misc); if (rc) return rc;
     th = T.begin(K_H2D);

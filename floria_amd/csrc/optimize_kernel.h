@@ -56,6 +56,9 @@ struct OptArgs {
     uint8_t*  blk_done_w;
     uint32_t* best_ploidy;
     uint32_t* tried;
+    // != 0 (ploidy >= 2, canonical arithmetic, one ploidy per stage): this job also stands for its block's ploidy-1 job, whose all-reads histogram is the sum over
+    // partitions of the one built here — mec / num_alleles / iters of ploidy 1 and its stop rule come out of this job's histogram right after the build pass
+    uint32_t  with_p1;
     // speculative stages (several ploidies of a block in flight at once): the stop rule is published per block as soon as the two MEC
     // values it compares exist — stop_at[b] = the smallest ploidy at which the reference's loop breaks (as far as known), ready[b] =
     // bit p set once mec[b][p-1] is final.  Jobs of a block with ploidy > stop_at[b] are dropped wherever they are (beam: at dequeue
@@ -161,7 +164,7 @@ void optimize_kernel(OptArgs g) {
     __shared__ uint64_t s_errq[MAX_PLOIDY], s_goodq[MAX_PLOIDY];
     __shared__ uint32_t s_errm[MAX_PLOIDY];
     __shared__ uint32_t s_size[MAX_PLOIDY];
-    __shared__ uint32_t s_ncand, s_nmoves, s_job, s_skip, s_dq;
+    __shared__ uint32_t s_ncand, s_nmoves, s_job, s_skip, s_dq, s_p1stop;
     __shared__ uint32_t s_chg_lo, s_chg_hi;          // positions whose code byte changed in the last batch of moves (HL)
     __shared__ uint32_t s_bkt[OPT_BUCKETS];          // visiting order: reads per bucket of ceil(#cells / 64), then the buckets' write cursors
     __shared__ double s_score;
@@ -713,6 +716,55 @@ void optimize_kernel(OptArgs g) {
         // ARITH: the lists of the partition just scored become the accepted ones
         auto accept_lists = [&]() __attribute__((always_inline)) { if constexpr (ARITH) { __syncthreads(); if ((uint32_t)tid < p) s_bpar[tid] = s_tpar[tid]; __syncthreads(); } };
 
+        // ---- ploidy 1 of the same block (with_p1) ------------------------------------------------------------------------------------
+        // The ploidy-1 job's histogram holds every read in partition 0: cell by cell the sum over this job's partitions, whatever the beam search made of them (and
+        // whatever the moves below make of them).  Its job is build + get_mec_stats_epsilon_no_phred, nothing else (p == 1 leaves the loop below at once, iters = 1):
+        // the same unit-count statistics over the summed counts here, then its stop rule — a block that stops at ploidy 1 leaves before any further pass, and
+        // nothing of ploidy 2 is written for it.
+        if constexpr (!ARITH) {
+            if (g.with_p1 && p >= 2) {
+                if (tid == 0) { s_errq[0] = 0; s_goodq[0] = 0; s_errm[0] = 0; s_p1stop = 0; }
+                __syncthreads();
+                uint64_t eq = 0, gq = 0;
+                uint32_t em = 0;
+                for (uint32_t pr = tid; pr < span; pr += OPT_THREADS) {
+                    const uint64_t* cp = hist + (uint64_t)pr * PA;
+                    uint64_t mx = 0, tot = 0;
+#pragma unroll
+                    for (int al = 0; al < A; ++al) {
+                        uint64_t q = 0;
+                        for (uint32_t k = 0; k < p; ++k) q += cp[k * A + al] >> CNT_SHIFT;
+                        mx = q > mx ? q : mx; tot += q;
+                    }
+                    if (tot) {                                  // position key exists in the map of all reads
+                        gq += mx; eq += tot - mx;
+                        if (mx <= 1ull) em += 1;
+                    }
+                }
+                eq = opt_wave_sum_u64(eq); gq = opt_wave_sum_u64(gq); em = opt_wave_sum_u32(em);
+                if (lane == 0) { atomicAdd((unsigned long long*)&s_errq[0], (unsigned long long)eq); atomicAdd((unsigned long long*)&s_goodq[0], (unsigned long long)gq); atomicAdd(&s_errm[0], em); }
+                __syncthreads();
+                if (tid == 0) {
+                    double mecv = 0.0, na = 0.0;                // (as the statistics at the end of a job, for its one partition)
+                    const double good = (double)s_goodq[0];
+                    const double bad = (double)s_errq[0] + (double)s_errm[0] * g.eps;
+                    mecv += bad; na += good; na += bad;
+                    g.mec[(uint64_t)b * g.max_ploidy] = mecv;      // (read again by this thread only — the ploidy-2 stop rule below — and by later launches)
+                    g.num_alleles[(uint64_t)b * g.max_ploidy] = na;
+                    g.iters[(uint64_t)b * g.max_ploidy] = 1;
+                    if (mecv < na * g.eps) {                    // :247-250 (max_ploidy >= 2: ploidy 1 ends a block by the stop rule only)
+                        if (g.release_tried) {
+                            __hip_atomic_store(&g.blk_done_w[b], (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); g.best_ploidy[b] = 1;
+                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                            __hip_atomic_store(&g.tried[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        } else { g.blk_done_w[b] = 1; g.best_ploidy[b] = 1; g.tried[b] = 1; }
+                        s_p1stop = 1;
+                    }
+                }
+                __syncthreads();
+                if (s_p1stop) continue;
+            }
+        }
         refresh_codes(false);
         OPT_TICK(0);     // build
         bool not_empty = n > 0;                                 // :76-85 (a job always has reads)

@@ -687,7 +687,9 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * 0 one ploidy at a time, 1 all ploidies of a block at once, 2 {1,2,3} then {4..P}), "spec_gate_div" (grid divisor of the gated ploidies of a
  * speculative stage, default 2), "tail_overlap" (one ploidy per stage: the beam launch of the LAST ploidy runs beside the optimise launch of the
  * ploidy below, every job waiting for its block's stop rule; 0 off = default (measured level with it on BASELINE config 4), 1 on), "tail_waves" (waves per CU of that launch,
- * default 2), "beam_path" (0 auto, 1 generic, 2 slab, 3 wide), "no_specialized", "no_p1_shortcut", "opt_threads"
+ * default 2), "fuse_p1" (one ploidy per stage, canonical arithmetic, max_ploidy >= 2, ploidy-1 shortcut on: ploidy 1 gets no launches of its own, a block's ploidy-2
+ * optimise job computes its MEC statistics and stop rule from the histogram it has built anyway; -1 auto = default = on where eligible, 0 off, 1 on where eligible;
+ * FLORIA_HIP_FUSE_P1 in the environment), "beam_path" (0 auto, 1 generic, 2 slab, 3 wide), "no_specialized", "no_p1_shortcut", "opt_threads"
  * (0|128|512|1024), "opt_global", "opt_block_order" (tests / A/B: the optimise kernel's passes visit a block's reads in block order instead of longest first), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
