@@ -1,5 +1,5 @@
 """ctypes mirror of include/floria_hip.h (struct layouts only; no library is loaded here).  The opaque handles (floria_hip_ctx, floria_hip_contig,
-floria_hip_haplosets) have no layout: lib.py holds them as c_void_p (FloriaHip, ResidentContig, Haplosets)."""
+floria_hip_haplosets, floria_hip_blob) have no layout: lib.py holds them as c_void_p (FloriaHip, ResidentContig, Haplosets, Blob)."""
 import ctypes as C
 
 import numpy as np
@@ -102,6 +102,12 @@ class CRealignCounts(C.Structure):
 
 class CRecordSummary(C.Structure):
     _fields_ = [("n_records", C.c_uint32), ("cell_off", u64p), ("first_snp", u32p), ("last_snp", u32p), ("ref_end", i64p), ("counts", CRealignCounts), ("token", C.c_uint64)]
+
+
+class CBlobRecords(C.Structure):
+    _fields_ = [("n_chains", C.c_uint32), ("n_records", C.c_uint64), ("chain_rec_off", u64p), ("chain_stop", u64p), ("offset", u64p), ("block_size", u32p),
+                ("ref_id", i32p), ("pos", i32p), ("l_seq", u32p), ("cigar0", u32p), ("flag", u16p), ("n_cigar_op", u16p), ("mapq", u8p), ("l_read_name", u8p),
+                ("name_off", u64p), ("names", u8p)]
 
 
 class CFragmentPlan(C.Structure):

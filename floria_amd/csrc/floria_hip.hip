@@ -52,6 +52,7 @@
 #include "span_kernel.h"
 #include "haploset_kernel.h"
 #include "path_kernel.h"
+#include "inflate_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -279,6 +280,9 @@ struct floria_hip_ctx {
     DevBuf span_buf;                          // floria_hip_read_spans: the groups, the contig table and the two result arrays (a buffer of its own: no residency ends)
     DevBuf hs_tmp;                            // floria_hip_reassign_batch_resident: the slot tables between its kernels (the handle has a buffer of its own); floria_hip_join_paths: its path tables
     DevBuf join_bits;                         // floria_hip_join_paths: the paths' bitmaps
+    DevBuf inf_in;                            // floria_hip_inflate_bgzf: the compressed bytes and the per-member tables (the blob has a buffer of its own)
+    DevBuf rec_in, rec_out, rec_names;        // floria_hip_blob_records: the chains' tables, the per-record arrays, the compacted names (buffers of their own: no residency ends)
+    uint32_t inflate_slots = 0;               // (tests) floria_hip_inflate_bgzf: members in flight, 0 = two per CU
     uint32_t stage_threads = 8;
 };
 
@@ -1016,7 +1020,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits, &c->inf_in, &c->rec_in, &c->rec_out, &c->rec_names}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -1092,6 +1096,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "upload_chunks") K.upload_chunks = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, floria_hip_ctx::MAX_GROUPS));
     else if (k == "trace") K.trace = value != 0;
     else if (k == "reassign_path") { if (value < 0 || value > 2) return fail(FLORIA_E_INVALID, "reassign_path: 0 auto | 1 parallel | 2 chain"); K.reassign_path = (uint32_t)value; }
+    else if (k == "inflate_slots") { if (value < 0 || value > (int64_t)0x7fffffff) return fail(FLORIA_E_INVALID, "inflate_slots: 0 = two members per CU | the largest number of members in flight"); ctx->inflate_slots = (uint32_t)value; }
     else if (k == "slots") ctx->user_slots = (uint32_t)std::max<int64_t>(0, value);
     else if (k == "stage_threads") ctx->stage_threads = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 16));
     else return fail(FLORIA_E_INVALID, "unknown option '" + k + "'");
@@ -2584,10 +2589,10 @@ int floria_hip_realign_walk(floria_hip_ctx* ctx, const uint8_t* read_windows, co
 // ---- frag_from_record (file_reader.rs:661-736) for a batch of alignment records (pileup_kernel.h) -------------------------------------------------
 namespace {
 // every length the kernels rely on, checked on the host before anything is uploaded or launched
-int pileup_validate(const floria_alignments* A, const floria_snp_table* S) {
+int pileup_validate(const floria_alignments* A, const floria_snp_table* S, bool device_blob = false) {
     const uint32_t n = A->n_records, nc = S->n_contigs;
     if (n && (!A->pos || !A->flags || !A->contig || !A->cigar_off || !A->n_cigar || !A->seq_off || !A->l_seq || !A->qual_off)) return fail(FLORIA_E_INVALID, "floria_alignments: null array");
-    if (A->blob_bytes && !A->blob) return fail(FLORIA_E_INVALID, "floria_alignments: null blob");
+    if (A->blob_bytes && !A->blob && !device_blob) return fail(FLORIA_E_INVALID, "floria_alignments: null blob");
     if (!S->snp_off) return fail(FLORIA_E_INVALID, "floria_snp_table: null snp_off");
     for (uint32_t c = 0; c < nc; ++c)
         if (S->snp_off[c] > S->snp_off[c + 1]) return fail(FLORIA_E_INVALID, "floria_snp_table: snp_off decreases at contig " + std::to_string(c));
@@ -2630,19 +2635,34 @@ void floria_hip_record_cells_free(floria_record_cells* r) {
     g_big.put(r->cell_off); g_big.put(r->snp); g_big.put(r->allele); g_big.put(r->qual); g_big.put(r->seq_pos); g_big.put(r->ref_end); free(r);
 }
 
+// Inflated BGZF members on the device (floria_hip_inflate_bgzf): a buffer of its own, so creating, using or freeing it ends no residency.
+struct floria_hip_blob {
+    floria_hip_ctx* ctx = nullptr;
+    DevBuf buf;
+    uint64_t bytes = 0;
+};
+
 namespace {
 // The body of floria_hip_pileup_records and floria_hip_pileup_records_realign: upload, COUNT, offset scan, FILL, download.  With reference sequences (F) the cells'
 // alleles are realigned on the device between FILL and the download (realign_gather_kernel.h): DECIDE, one read of its counters, then — when anything is left
 // undecided — FILL of the work list, the scoring kernel (walk == null: the exact DP) and the scatter.  Without F nothing of that is allocated, uploaded or launched.
 // `resident` (floria_hip_pileup_records_resident): the cell arrays stay where FILL put them; only the per-record arrays come back, with the SNP of every record's
 // first / last cell (record_span_kernel) in the places of R->snp / R->seq_pos ([n] instead of [cells]).
-int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F, const floria_realign_walk* walk,
-                        floria_record_cells** out, floria_realign_counts* counts, bool resident = false) {
-    if (!ctx || !A || !S || !out) return fail(FLORIA_E_INVALID, "null argument");
+// `H` (floria_hip_pileup_records_resident_blob): the record bytes are the handle's, already on the device; the offsets index it and nothing of a blob is uploaded.
+int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A_in, const floria_snp_table* S, const floria_ref_seqs* F, const floria_realign_walk* walk,
+                        floria_record_cells** out, floria_realign_counts* counts, bool resident = false, const floria_hip_blob* H = nullptr) {
+    if (!ctx || !A_in || !S || !out) return fail(FLORIA_E_INVALID, "null argument");
     *out = nullptr;
     ctx->res_token = 0; ctx->res_summary = nullptr;      // pile_in / pile_out are about to be rewritten: a residency ends here
     if (counts) *counts = floria_realign_counts{};
-    if (int rc = pileup_validate(A, S)) return rc;
+    floria_alignments A_view = *A_in;
+    if (H) {
+        if (H->ctx != ctx) return fail(FLORIA_E_INVALID, "the blob belongs to another context");
+        if (A_in->blob) return fail(FLORIA_E_INVALID, "floria_alignments: blob must be NULL beside a blob handle (the offsets index the handle)");
+        A_view.blob_bytes = H->bytes;
+    }
+    const floria_alignments* A = &A_view;
+    if (int rc = pileup_validate(A, S, H != nullptr)) return rc;
     if (F) { if (int rc = refs_validate(F, S)) return rc; }
     if (walk) { if (int rc = walk_member_validate(walk)) return rc; }
     const uint32_t n = A->n_records, nc = S->n_contigs;
@@ -2668,7 +2688,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
         const uint64_t snp_b = S->snp_off[0], n_snps = S->snp_off[nc] - snp_b;
         const uint32_t n_tiles = (n + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
         Carve C;
-        const Seg s_blob = C.seg(A->blob_bytes), s_pos = C.seg(4ull * n), s_flag = C.seg(2ull * n), s_ctg = C.seg(4ull * n), s_co = C.seg(8ull * n), s_nc = C.seg(4ull * n),
+        const Seg s_blob = C.seg(H ? 0 : A->blob_bytes), s_pos = C.seg(4ull * n), s_flag = C.seg(2ull * n), s_ctg = C.seg(4ull * n), s_co = C.seg(8ull * n), s_nc = C.seg(4ull * n),
                   s_so = C.seg(8ull * n), s_ls = C.seg(4ull * n), s_qo = C.seg(8ull * n), s_soff = C.seg(8ull * (nc + 1)), s_sp = C.seg(8 * n_snps), s_al = C.seg(4 * n_snps),
                   s_na = C.seg(n_snps), s_off = C.seg(8ull * ((uint64_t)n + 1)), s_tile = C.seg(8ull * n_tiles), s_re = C.seg(8ull * n);
         const Seg s_f1 = C.seg(resident ? 4ull * n : 0), s_l1 = C.seg(resident ? 4ull * n : 0);
@@ -2689,7 +2709,7 @@ int pileup_records_impl(floria_hip_ctx* ctx, const floria_alignments* A, const f
             T.end(t);
         }
         fl::PileupArgs a{};
-        a.blob = C.at<const uint8_t>(s_blob); a.pos = C.at<const int32_t>(s_pos); a.flags = C.at<const uint16_t>(s_flag); a.contig = C.at<const uint32_t>(s_ctg);
+        a.blob = H ? H->buf.as<const uint8_t>() : C.at<const uint8_t>(s_blob); a.pos = C.at<const int32_t>(s_pos); a.flags = C.at<const uint16_t>(s_flag); a.contig = C.at<const uint32_t>(s_ctg);
         a.cigar_off = C.at<const uint64_t>(s_co); a.n_cigar = C.at<const uint32_t>(s_nc); a.seq_off = C.at<const uint64_t>(s_so); a.l_seq = C.at<const uint32_t>(s_ls);
         a.qual_off = C.at<const uint64_t>(s_qo); a.snp_off = C.at<const uint64_t>(s_soff);
         // (the table travels from its first used entry: the kernels index it with the caller's offsets)
@@ -2823,6 +2843,246 @@ int floria_hip_pileup_records_resident(floria_hip_ctx* ctx, const floria_alignme
 void floria_hip_record_summary_free(floria_record_summary* s) {
     if (!s) return;
     g_big.put(s->cell_off); g_big.put(s->first_snp); g_big.put(s->last_snp); g_big.put(s->ref_end); free(s);
+}
+
+// ---- BGZF members inflated on the device, and the record table of the inflated bytes (inflate_kernel.h) --------------------------------------------------------------
+namespace {
+const char* inflate_reason(uint32_t st) {
+    static const char* const R[fl::INF_N_STATUS] = {"ok", "bits ran out", "reserved block type", "LEN/NLEN mismatch", "over-subscribed code lengths", "incomplete code lengths",
+                                                    "distance beyond the bytes produced", "output longer than ISIZE", "output shorter than ISIZE", "CRC mismatch", "invalid code",
+                                                    "step bound reached"};
+    return st < fl::INF_N_STATUS ? R[st] : "unknown status";
+}
+inline uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+inline uint32_t le32(const uint8_t* p) { return le16(p) | le16(p + 2) << 16; }
+}  // namespace
+
+int floria_hip_inflate_bgzf(floria_hip_ctx* ctx, const uint8_t* file, uint64_t n_bytes, const uint64_t* member_off, const uint32_t* member_bytes, uint32_t n, floria_hip_blob** out) {
+    if (!ctx || !out || (n && (!file || !member_off || !member_bytes))) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    // the host part: every member's gzip header and trailer, before anything is uploaded or launched
+    std::vector<uint64_t> pay_off(n), out_off((size_t)n + 1, 0);
+    std::vector<uint32_t> pay_bytes(n), crc(n);
+    uint64_t lo = n_bytes, hi = 0;
+    for (uint32_t m = 0; m < n; ++m) {
+        const std::string who = "BGZF member " + std::to_string(m);
+        const uint64_t off = member_off[m], mb = member_bytes[m];
+        if (off > n_bytes || mb > n_bytes - off) return fail(FLORIA_E_INVALID, who + ": bytes " + std::to_string(off) + " + " + std::to_string(mb) + " reach past n_bytes (" + std::to_string(n_bytes) + ")");
+        if (mb < 12 + 6 + 8) return fail(FLORIA_E_INVALID, who + ": " + std::to_string(mb) + " bytes are less than a BGZF header and trailer");
+        const uint8_t* p = file + off;
+        if (p[0] != 31 || p[1] != 139) return fail(FLORIA_E_INVALID, who + ": no gzip magic");
+        if (p[2] != 8) return fail(FLORIA_E_INVALID, who + ": compression method " + std::to_string((unsigned)p[2]) + " (8 = DEFLATE)");
+        if (p[3] != 4) return fail(FLORIA_E_INVALID, who + ": gzip flags " + std::to_string((unsigned)p[3]) + " (BGZF sets FEXTRA alone)");
+        const uint64_t xlen = le16(p + 10);
+        if (12 + xlen + 8 > mb) return fail(FLORIA_E_INVALID, who + ": the extra field (" + std::to_string(xlen) + " bytes) reaches past the member");
+        uint64_t x = 12, bsize = 0;
+        while (x + 4 <= 12 + xlen) {
+            const uint32_t slen = le16(p + x + 2);
+            if (p[x] == 66 && p[x + 1] == 67 && slen == 2 && x + 6 <= 12 + xlen) { bsize = (uint64_t)le16(p + x + 4) + 1; break; }
+            x += 4 + (uint64_t)slen;
+        }
+        if (!bsize) return fail(FLORIA_E_INVALID, who + ": no BC subfield in the extra field");
+        if (bsize != mb) return fail(FLORIA_E_INVALID, who + ": BSIZE says " + std::to_string(bsize) + " bytes, member_bytes " + std::to_string(mb));
+        const uint32_t isize = le32(p + mb - 4);
+        if (isize > fl::INF_MAX_OUT) return fail(FLORIA_E_UNSUPPORTED, who + ": ISIZE " + std::to_string(isize) + " is more than 65536: a gzip file that is not BGZF");
+        pay_off[m] = off + 12 + xlen; pay_bytes[m] = (uint32_t)(mb - 12 - xlen - 8);
+        crc[m] = le32(p + mb - 8);
+        out_off[m + 1] = out_off[m] + isize;
+        lo = std::min(lo, off); hi = std::max(hi, off + mb);
+    }
+    floria_hip_blob* B = new (std::nothrow) floria_hip_blob();
+    if (!B) return fail(FLORIA_E_NOMEM, "new");
+    struct Guard { floria_hip_blob* b; hipStream_t st; ~Guard() { if (b) { (void)hipStreamSynchronize(st); b->buf.release(); delete b; } } } guard{B, ctx->stream};
+    B->ctx = ctx; B->bytes = out_off[n];
+    ctx->timing = floria_timing{};
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = B->buf.ensure(B->bytes + 256)) return rc;
+    if (n) {
+        lo &= ~(uint64_t)3;                                  // the kernel reads the file as aligned words
+        const uint64_t span = hi - lo, span_words = (span + 3) / 4;
+        for (uint32_t m = 0; m < n; ++m) pay_off[m] -= lo;
+        Carve C;
+        const Seg s_file = C.seg(4 * span_words), s_po = C.seg(8ull * n), s_pb = C.seg(4ull * n), s_oo = C.seg(8ull * ((uint64_t)n + 1)), s_crc = C.seg(4ull * n), s_st = C.seg(4ull * n);
+        if (int rc = C.place(ctx->inf_in)) return rc;
+        EventTimer T(ctx->stream);
+        uint64_t pinned_b = 0, staged_b = 0;
+        {
+            std::vector<CopyRun> runs;
+            runs.push_back({(const char*)file + lo, C.at<char>(s_file), (size_t)span});
+            runs.push_back({(const char*)pay_off.data(), C.at<char>(s_po), 8 * (size_t)n}); runs.push_back({(const char*)pay_bytes.data(), C.at<char>(s_pb), 4 * (size_t)n});
+            runs.push_back({(const char*)out_off.data(), C.at<char>(s_oo), 8 * ((size_t)n + 1)}); runs.push_back({(const char*)crc.data(), C.at<char>(s_crc), 4 * (size_t)n});
+            const int t = T.begin(K_H2D);
+            if (int rc = issue_copies(ctx, runs, &pinned_b, &staged_b)) return rc;
+            T.end(t);
+        }
+        fl::InflateArgs a{};
+        a.file = C.at<const uint8_t>(s_file); a.file_words = span_words; a.pay_off = C.at<const uint64_t>(s_po); a.pay_bytes = C.at<const uint32_t>(s_pb);
+        a.out_off = C.at<const uint64_t>(s_oo); a.blob = B->buf.as<uint8_t>(); a.status = C.at<uint32_t>(s_st); a.n_members = n;
+        const uint32_t slots = ctx->inflate_slots ? ctx->inflate_slots : 2 * (uint32_t)ctx->n_cu;
+        HIPCHK(hipFuncSetAttribute((const void*)fl::inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl::INF_LDS_BYTES));
+        int t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::inflate_kernel, dim3(std::min(n, slots)), dim3(64), fl::INF_LDS_BYTES, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(fl::inflate_crc_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint8_t*)a.blob, a.out_off, C.at<const uint32_t>(s_crc), a.status, n);
+        HIPCHK(hipGetLastError());
+        T.end(t);
+        std::vector<uint32_t> status(n);
+        t = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(status.data(), a.status, 4ull * n, hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        T.publish(ctx->timing);
+        ctx->timing.upload_pinned_bytes = pinned_b; ctx->timing.upload_staged_bytes = staged_b;
+        for (uint32_t m = 0; m < n; ++m)
+            if (status[m] != fl::INF_OK) return fail(FLORIA_E_INVALID, "BGZF member " + std::to_string(m) + ": " + inflate_reason(status[m]));
+    }
+    guard.b = nullptr;
+    *out = B;
+    return 0;
+}
+
+uint64_t floria_hip_blob_bytes(const floria_hip_blob* b) { return b ? b->bytes : 0; }
+
+int floria_hip_blob_download(const floria_hip_blob* b, uint64_t off, void* dst, uint64_t bytes) {
+    if (!b || (bytes && !dst)) return fail(FLORIA_E_INVALID, "null argument");
+    if (off > b->bytes || bytes > b->bytes - off) return fail(FLORIA_E_INVALID, "blob download: bytes " + std::to_string(off) + " + " + std::to_string(bytes) + " reach past the blob (" + std::to_string(b->bytes) + ")");
+    if (!bytes) return 0;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    HIPCHK(hipMemcpy(dst, b->buf.as<char>() + off, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+void floria_hip_blob_free(floria_hip_blob* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    b->buf.release();
+    delete b;
+}
+
+void floria_hip_blob_records_free(floria_blob_records* r) {
+    if (!r) return;
+    for (void* p : {(void*)r->chain_rec_off, (void*)r->chain_stop, (void*)r->offset, (void*)r->block_size, (void*)r->ref_id, (void*)r->pos, (void*)r->l_seq, (void*)r->cigar0,
+                    (void*)r->flag, (void*)r->n_cigar_op, (void*)r->mapq, (void*)r->l_read_name, (void*)r->name_off, (void*)r->names}) g_big.put(p);
+    free(r);
+}
+
+int floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* begin, const uint64_t* end, uint32_t nch, floria_blob_records** out) {
+    if (!ctx || !blob || !out || (nch && (!begin || !end))) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    if (blob->ctx != ctx) return fail(FLORIA_E_INVALID, "the blob belongs to another context");
+    for (uint32_t c = 0; c < nch; ++c)
+        if (begin[c] > end[c] || end[c] > blob->bytes)
+            return fail(FLORIA_E_INVALID, "blob_records: chain " + std::to_string(c) + " [" + std::to_string(begin[c]) + ", " + std::to_string(end[c]) + ") is no range of the blob (" + std::to_string(blob->bytes) + " bytes)");
+    floria_blob_records* R = (floria_blob_records*)calloc(1, sizeof(floria_blob_records));
+    if (!R) return fail(FLORIA_E_NOMEM, "calloc");
+    struct Guard { floria_blob_records* r; hipStream_t st; ~Guard() { if (r) { (void)hipStreamSynchronize(st); floria_hip_blob_records_free(r); } } } guard{R, ctx->stream};
+    R->n_chains = nch;
+    R->chain_rec_off = (uint64_t*)cells_bytes(8ull * ((uint64_t)nch + 1)); R->chain_stop = (uint64_t*)cells_bytes(8ull * nch);
+    if (!R->chain_rec_off || !R->chain_stop) return fail(FLORIA_E_NOMEM, "malloc");
+    R->chain_rec_off[0] = 0;
+    ctx->timing = floria_timing{};
+    uint64_t N = 0, name_bytes = 0;
+    EventTimer T(ctx->stream);
+    fl::RecordArgs q{};
+    if (nch) {
+        HIPCHK(hipSetDevice(ctx->device));
+        const uint32_t n_tiles = (nch + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+        Carve C;
+        const Seg s_b = C.seg(8ull * nch), s_e = C.seg(8ull * nch), s_cnt = C.seg(8ull * ((uint64_t)nch + 1)), s_stop = C.seg(8ull * nch), s_st = C.seg(4ull * nch), s_tile = C.seg(8ull * n_tiles);
+        if (int rc = C.place(ctx->rec_in)) return rc;
+        int t = T.begin(K_H2D);
+        HIPCHK(C.up(s_b, begin, 8ull * nch, ctx->stream)); HIPCHK(C.up(s_e, end, 8ull * nch, ctx->stream));
+        T.end(t);
+        fl::ChainArgs a{};
+        a.blob = blob->buf.as<const uint8_t>(); a.blob_bytes = blob->bytes; a.begin = C.at<const uint64_t>(s_b); a.end = C.at<const uint64_t>(s_e);
+        a.count = C.at<uint64_t>(s_cnt); a.stop = C.at<uint64_t>(s_stop); a.status = C.at<uint32_t>(s_st); a.n_chains = nch;
+        t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::blob_chain_kernel<false>, dim3((nch + 255) / 256), dim3(256), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        launch_offset_scan(ctx, a.count, C.at<uint64_t>(s_tile), nch);
+        HIPCHK(hipGetLastError());
+        T.end(t);
+        std::vector<uint32_t> status(nch);
+        t = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(R->chain_rec_off, a.count, 8ull * ((uint64_t)nch + 1), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(R->chain_stop, a.stop, 8ull * nch, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(status.data(), a.status, 4ull * nch, hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        for (uint32_t c = 0; c < nch; ++c)
+            if (status[c] != fl::CHAIN_OK)
+                return fail(FLORIA_E_INVALID, "blob_records: chain " + std::to_string(c) + " stopped at offset " + std::to_string(R->chain_stop[c]) + ": " +
+                                                  (status[c] == fl::CHAIN_SHORT ? "a block_size below the 32 fixed bytes of a record" : "a record that runs past the chain's end (" + std::to_string(end[c]) + ")"));
+        N = R->chain_rec_off[nch];
+        if (N >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "blob_records: 2^32 and more records");
+        if (N) {
+            const uint32_t r_tiles = ((uint32_t)N + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
+            Carve O;
+            const Seg o_off = O.seg(8 * N), o_bs = O.seg(4 * N), o_ref = O.seg(4 * N), o_pos = O.seg(4 * N), o_ls = O.seg(4 * N), o_cg = O.seg(4 * N), o_fl = O.seg(2 * N), o_nc = O.seg(2 * N),
+                      o_mq = O.seg(N), o_ln = O.seg(N), o_no = O.seg(8 * (N + 1)), o_tile = O.seg(8ull * r_tiles);
+            if (int rc = O.place(ctx->rec_out)) return rc;
+            a.rec_off = O.at<uint64_t>(o_off);
+            q.blob = a.blob; q.blob_bytes = a.blob_bytes; q.rec_off = a.rec_off; q.ref_id = O.at<int32_t>(o_ref); q.pos = O.at<int32_t>(o_pos); q.block_size = O.at<uint32_t>(o_bs);
+            q.l_seq = O.at<uint32_t>(o_ls); q.cigar0 = O.at<uint32_t>(o_cg); q.flag = O.at<uint16_t>(o_fl); q.n_cigar_op = O.at<uint16_t>(o_nc); q.mapq = O.at<uint8_t>(o_mq);
+            q.l_read_name = O.at<uint8_t>(o_ln); q.name_off = O.at<uint64_t>(o_no); q.n_records = N;
+            const uint32_t rgrid = (uint32_t)((N + 255) / 256);
+            t = T.begin(K_PILEUP);
+            hipLaunchKernelGGL(fl::blob_chain_kernel<true>, dim3((nch + 255) / 256), dim3(256), 0, ctx->stream, a);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(fl::blob_record_kernel, dim3(rgrid), dim3(256), 0, ctx->stream, q);
+            HIPCHK(hipGetLastError());
+            launch_offset_scan(ctx, q.name_off, O.at<uint64_t>(o_tile), (uint32_t)N);
+            HIPCHK(hipGetLastError());
+            T.end(t);
+            t = T.begin(K_D2H);
+            HIPCHK(hipMemcpyAsync(&name_bytes, q.name_off + N, 8, hipMemcpyDeviceToHost, ctx->stream));
+            T.end(t);
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            if (name_bytes > 255 * N) return fail(FLORIA_E_DEVICE, "blob_records: the names are longer than 255 bytes per record");
+            if (int rc = ctx->rec_names.ensure(name_bytes + 256)) return rc;
+            q.names = ctx->rec_names.as<uint8_t>();
+            t = T.begin(K_PILEUP);
+            hipLaunchKernelGGL(fl::blob_names_kernel, dim3(rgrid), dim3(256), 0, ctx->stream, q);
+            HIPCHK(hipGetLastError());
+            T.end(t);
+        }
+    }
+    R->n_records = N;
+    R->offset = (uint64_t*)cells_bytes(8 * N); R->block_size = (uint32_t*)cells_bytes(4 * N); R->ref_id = (int32_t*)cells_bytes(4 * N); R->pos = (int32_t*)cells_bytes(4 * N);
+    R->l_seq = (uint32_t*)cells_bytes(4 * N); R->cigar0 = (uint32_t*)cells_bytes(4 * N); R->flag = (uint16_t*)cells_bytes(2 * N); R->n_cigar_op = (uint16_t*)cells_bytes(2 * N);
+    R->mapq = (uint8_t*)cells_bytes(N); R->l_read_name = (uint8_t*)cells_bytes(N); R->name_off = (uint64_t*)cells_bytes(8 * (N + 1)); R->names = (uint8_t*)cells_bytes(name_bytes);
+    if (!R->offset || !R->block_size || !R->ref_id || !R->pos || !R->l_seq || !R->cigar0 || !R->flag || !R->n_cigar_op || !R->mapq || !R->l_read_name || !R->name_off || !R->names)
+        return fail(FLORIA_E_NOMEM, "malloc");
+    R->name_off[0] = 0;
+    if (N) {
+        const int t = T.begin(K_D2H);
+        const auto down = [&](void* dst, const void* src, uint64_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
+        HIPCHK(down(R->offset, q.rec_off, 8 * N)); HIPCHK(down(R->block_size, q.block_size, 4 * N)); HIPCHK(down(R->ref_id, q.ref_id, 4 * N)); HIPCHK(down(R->pos, q.pos, 4 * N));
+        HIPCHK(down(R->l_seq, q.l_seq, 4 * N)); HIPCHK(down(R->cigar0, q.cigar0, 4 * N)); HIPCHK(down(R->flag, q.flag, 2 * N)); HIPCHK(down(R->n_cigar_op, q.n_cigar_op, 2 * N));
+        HIPCHK(down(R->mapq, q.mapq, N)); HIPCHK(down(R->l_read_name, q.l_read_name, N)); HIPCHK(down(R->name_off, q.name_off, 8 * (N + 1))); HIPCHK(down(R->names, q.names, name_bytes));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    if (nch) T.publish(ctx->timing);
+    guard.r = nullptr;
+    *out = R;
+    return 0;
+}
+
+int floria_hip_pileup_records_resident_blob(floria_hip_ctx* ctx, const floria_hip_blob* blob, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F,
+                                            const floria_realign_walk* walk, floria_record_summary** out) {
+    if (!out || !blob) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    floria_record_summary* Y = (floria_record_summary*)calloc(1, sizeof(floria_record_summary));
+    if (!Y) return fail(FLORIA_E_NOMEM, "calloc");
+    floria_record_cells* R = nullptr;
+    if (int rc = pileup_records_impl(ctx, A, S, F, walk, &R, &Y->counts, true, blob)) { free(Y); return rc; }
+    Y->n_records = R->n_records; Y->cell_off = R->cell_off; Y->first_snp = R->snp; Y->last_snp = R->seq_pos; Y->ref_end = R->ref_end;
+    free(R);
+    Y->token = ++ctx->token_counter;
+    ctx->res_token = Y->token; ctx->res_summary = Y;
+    *out = Y;
+    return 0;
 }
 
 // `ordered`: floria_hip_assemble_contigs_ordered — the contigs that hold a merged fragment get their set_order from the device (assemble_order_kernel.h)

@@ -34,6 +34,8 @@ SYMBOLS = [
     "floria_hip_drop_monomorphic", "floria_hip_mono_result_free", "floria_hip_mono_timing",
     "floria_hip_reassign_batch_resident", "floria_hip_haplosets_free", "floria_hip_haplosets_download", "floria_hip_haploset_stats_resident", "floria_hip_hapq_batch_resident",
     "floria_hip_haploset_alleles_resident", "floria_hip_read_spans_resident", "floria_hip_join_paths", "floria_hip_reassign_haplosets_resident",
+    "floria_hip_inflate_bgzf", "floria_hip_blob_bytes", "floria_hip_blob_download", "floria_hip_blob_free", "floria_hip_blob_records", "floria_hip_blob_records_free",
+    "floria_hip_pileup_records_resident_blob",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -108,6 +110,17 @@ def load():
         L.floria_hip_join_paths.argtypes = [C.c_void_p, C.POINTER(capi.CBlockResult), C.c_void_p, C.c_uint32, capi.u32p, capi.u64p, capi.u32p, capi.u8p, capi.u32p, C.c_uint32,
                                             C.POINTER(C.c_void_p)]
         L.floria_hip_reassign_haplosets_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.POINTER(C.c_void_p)]
+        L.floria_hip_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, capi.u64p, capi.u32p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.floria_hip_blob_bytes.restype = C.c_uint64
+        L.floria_hip_blob_bytes.argtypes = [C.c_void_p]
+        L.floria_hip_blob_download.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        L.floria_hip_blob_free.restype = None
+        L.floria_hip_blob_free.argtypes = [C.c_void_p]
+        L.floria_hip_blob_records.argtypes = [C.c_void_p, C.c_void_p, capi.u64p, capi.u64p, C.c_uint32, C.POINTER(C.POINTER(capi.CBlobRecords))]
+        L.floria_hip_blob_records_free.restype = None
+        L.floria_hip_blob_records_free.argtypes = [C.POINTER(capi.CBlobRecords)]
+        L.floria_hip_pileup_records_resident_blob.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(capi.CRefSeqs),
+                                                              C.POINTER(capi.CRealignWalk), C.POINTER(C.POINTER(capi.CRecordSummary))]
         _LIB = L
     return _LIB
 
@@ -352,6 +365,32 @@ class Haplosets:
             pass
 
 
+class Blob:
+    """floria_hip_blob: BGZF members inflated on the device by FloriaHip.inflate_bgzf, back to back.  nbytes; download(off=0, nbytes=None) -> uint8 array; free().
+    FloriaHip.blob_records(blob, ...) gives its record table, FloriaHip.pileup_records_resident(blob=blob, ...) walks its records where they lie."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+        self.nbytes = int(load().floria_hip_blob_bytes(handle))
+
+    def download(self, off=0, nbytes=None):
+        n = self.nbytes - int(off) if nbytes is None else int(nbytes)
+        out = np.zeros(max(n, 0), np.uint8)
+        _check(load().floria_hip_blob_download(self._h, C.c_uint64(int(off)), out.ctypes.data_as(C.c_void_p), C.c_uint64(max(n, 0))))
+        return out
+
+    def free(self):
+        if self._h is not None:
+            load().floria_hip_blob_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def _contig_array(contigs):
     n = len(contigs)
     return contigs._arr if isinstance(contigs, ContigBatch) else (C.c_void_p * max(n, 1))(*[c._h for c in contigs])
@@ -563,9 +602,40 @@ class FloriaHip:
 
     def pileup_records_resident(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, ref_off=None, ref_seq=None, walk=None):
         """floria_hip_pileup_records_resident: pileup_records() (ref_off None) or pileup_records_realign() whose cells stay on the device -> RecordSummary
-        (free() it when the fragments are assembled).  Any later pileup_records* call on this context ends the residency."""
+        (free() it when the fragments are assembled).  Any later pileup_records* call on this context ends the residency.
+        blob= a Blob (inflate_bgzf): floria_hip_pileup_records_resident_blob, the offsets index the handle and no record byte is uploaded."""
         return self._pileup_records(blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles,
                                     refs=None if ref_off is None else (ref_off, ref_seq), walk=walk, resident=True)
+
+    def inflate_bgzf(self, file_bytes, member_off, member_bytes):
+        """floria_hip_inflate_bgzf: the BGZF members (member_off uint64 [n], member_bytes uint32 [n]) of the file image `file_bytes` (bytes or a uint8 array; one
+        that lives in a PinnedArena goes up by DMA) inflated on the device -> Blob, the inflated bytes back to back in the order given."""
+        fb = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8)
+        mo = np.ascontiguousarray(member_off, np.uint64); mb = np.ascontiguousarray(member_bytes, np.uint32)
+        if len(mo) != len(mb):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "inflate_bgzf: one length per member offset")
+        h = C.c_void_p()
+        _check(load().floria_hip_inflate_bgzf(self._h, fb.ctypes.data_as(C.c_void_p), C.c_uint64(fb.size), capi.ptr(mo, C.c_uint64), capi.ptr(mb, C.c_uint32), C.c_uint32(len(mo)), C.byref(h)))
+        return Blob(self, h)
+
+    def blob_records(self, blob, begin, end):
+        """floria_hip_blob_records: the record table of a Blob of BAM alignment records, chain c following the block_size prefixes from begin[c] while a whole
+        record fits before end[c] -> dict of numpy arrays (chain_rec_off uint64 [n_chains + 1], chain_stop uint64 [n_chains]; per record offset uint64, block_size,
+        ref_id, pos, l_seq, cigar0, flag, n_cigar_op, mapq, l_read_name; name_off uint64 [n + 1] and names uint8, the names as stored, NUL included)."""
+        b = np.ascontiguousarray(np.atleast_1d(begin), np.uint64); e = np.ascontiguousarray(np.atleast_1d(end), np.uint64)
+        if len(b) != len(e):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "blob_records: one end per begin")
+        out = C.POINTER(capi.CBlobRecords)()
+        _check(load().floria_hip_blob_records(self._h, blob._h, capi.ptr(b, C.c_uint64), capi.ptr(e, C.c_uint64), C.c_uint32(len(b)), C.byref(out)))
+        r = out.contents
+        n, nch = int(r.n_records), int(r.n_chains)
+        res = dict(chain_rec_off=capi.np_from(r.chain_rec_off, nch + 1, np.uint64), chain_stop=capi.np_from(r.chain_stop, nch, np.uint64), name_off=capi.np_from(r.name_off, n + 1, np.uint64))
+        for f, dt in (("offset", np.uint64), ("block_size", np.uint32), ("ref_id", np.int32), ("pos", np.int32), ("l_seq", np.uint32), ("cigar0", np.uint32), ("flag", np.uint16),
+                      ("n_cigar_op", np.uint16), ("mapq", np.uint8), ("l_read_name", np.uint8)):
+            res[f] = capi.np_from(getattr(r, f), n, dt)
+        res["names"] = capi.np_from(r.names, int(res["name_off"][n]), np.uint8)
+        load().floria_hip_blob_records_free(out)
+        return res
 
     def assemble_contigs_ordered(self, summary, frag_off, part_off, part_rec):
         """floria_hip_assemble_contigs_ordered: assemble_contigs() whose merged contigs (a fragment with two or more parts that have cells) carry the set_order
@@ -679,6 +749,11 @@ class FloriaHip:
     def _pileup_records(self, blob, pos, flags, contig, cigar_off, n_cigar, seq_off, l_seq, qual_off, snp_off, snp_pos, alleles, n_alleles, refs=None, walk=None, resident=False):
         def arr(a, dt):
             return a if isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous else np.ascontiguousarray(a, dt)
+        handle = blob if isinstance(blob, Blob) else None
+        if handle is not None:
+            if not resident:
+                raise FloriaHipError(capi.FLORIA_E_INVALID, "pileup_records: a Blob handle is taken by pileup_records_resident alone")
+            blob = np.zeros(0, np.uint8)
         keep = [arr(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8), arr(pos, np.int32), arr(flags, np.uint16),
                 arr(contig, np.uint32), arr(cigar_off, np.uint64), arr(n_cigar, np.uint32), arr(seq_off, np.uint64), arr(l_seq, np.uint32), arr(qual_off, np.uint64),
                 arr(snp_off, np.uint64), arr(snp_pos, np.int64), arr(alleles, np.uint8), arr(n_alleles, np.uint8)]      # every input buffer stays alive until the call returns
@@ -695,6 +770,22 @@ class FloriaHip:
         counts = None
         if resident:
             out = C.POINTER(capi.CRecordSummary)()
+        if handle is not None:
+            A.blob = None
+            F = w = None
+            if refs is not None:
+                roff = arr(refs[0], np.uint64)
+                rseq = arr(np.frombuffer(refs[1], np.uint8) if isinstance(refs[1], (bytes, bytearray, memoryview)) else (refs[1] if refs[1] is not None else []), np.uint8)
+                keep += [roff, rseq]
+                if len(roff) < 1 or (refs[1] is not None and int(roff.max()) > rseq.size):
+                    raise FloriaHipError(capi.FLORIA_E_INVALID, "pileup_records_realign: ref_off needs n_contigs + 1 entries, the last at most len(ref_seq)")
+                F = capi.CRefSeqs(len(roff) - 1, capi.ptr(roff, C.c_uint64), capi.ptr(rseq, C.c_uint8) if rseq.size else None)
+                if walk is not None:
+                    block, step, rule, tie = walk if len(walk) == 4 else (8,) + tuple(walk)
+                    w = capi.CRealignWalk(int(block), int(step), {"max": 0, "sum": 1}.get(rule, rule), {"right": 0, "down": 1}.get(tie, tie))
+            _check(load().floria_hip_pileup_records_resident_blob(self._h, handle._h, C.byref(A), C.byref(S), C.byref(F) if F is not None else None,
+                                                                  C.byref(w) if w is not None else None, C.byref(out)))
+            return RecordSummary(self, out, n)
         if refs is None and resident:
             _check(load().floria_hip_pileup_records_resident(self._h, C.byref(A), C.byref(S), None, None, C.byref(out)))
             return RecordSummary(self, out, n)

@@ -435,6 +435,71 @@ int  floria_hip_pileup_records_resident(floria_hip_ctx* ctx, const floria_alignm
                                         const floria_realign_walk* walk /* NULL = exact DP */, floria_record_summary** out);
 void floria_hip_record_summary_free(floria_record_summary* s);
 
+/* ---- BGZF members inflated ON THE DEVICE: the record bytes never cross the link ---------------------------------------------------------------------------------------
+ * floria_hip_inflate_bgzf inflates n_members BGZF members of a file image (file_bytes[0 .. n_bytes); member m is the member_bytes[m] bytes at member_off[m]) into a
+ * floria_hip_blob: a device buffer of its own — creating, using or freeing it ends no residency — that holds the members' inflated bytes back to back in the order
+ * given.  The compressed file is roughly a tenth of the inflated bytes a host would otherwise upload.
+ * HOST PART, all of it before anything is uploaded or launched, FLORIA_E_INVALID naming the member: the offset range against n_bytes; the gzip header (magic, CM = 8,
+ * FLG = FEXTRA, the BC subfield — other subfields may stand before it — and BSIZE against member_bytes); the CRC32 and ISIZE trailer is read, the output offsets are
+ * the prefix sums of ISIZE.  ISIZE > 65 536 is FLORIA_E_UNSUPPORTED: a gzip file that is not BGZF.  The compressed bytes (from the first to the last member given) go
+ * up by DMA where they lie in floria_hip_host_alloc memory and through the pinned staging ring otherwise.
+ * KERNELS (csrc/inflate_kernel.h): raw DEFLATE (RFC 1951) per member — stored, fixed and dynamic blocks, any number of blocks — one wavefront per member in a
+ * persistent grid, the member's output and the Huffman tables in LDS, one coalesced flush; then the CRC32 of every member's output.  Every input read is bounded by the
+ * member's payload length, every output write by its ISIZE, every table index by its table, and every decoding step consumes an input bit or emits an output byte.
+ * A per-member status word reports: bits ran out, reserved block type, LEN/NLEN mismatch, over-subscribed or incomplete code lengths, distance beyond the bytes
+ * produced, output longer or shorter than ISIZE, CRC mismatch, invalid code.  Any non-zero status makes the call FLORIA_E_INVALID with the first such member and its
+ * reason in the message; no handle is returned and the context stays usable.  The decoder is one host/device function template; tests/cpp/inflate_core_check.cpp runs
+ * the same text on the CPU against zlib under the sanitizers.
+ * floria_hip_last_timing then reports h2d_ms, pileup_ms (the two kernels), d2h_ms (the status words), total_ms and upload_pinned_bytes / upload_staged_bytes.
+ * (Test option "inflate_slots" = N: at most N members in flight; 0 = default, two per CU.)
+ * floria_hip_blob_download copies bytes [off, off + bytes) of the blob to the host: for tests, and for the rare host that needs a record's aux bytes. */
+typedef struct floria_hip_blob floria_hip_blob;
+int  floria_hip_inflate_bgzf(floria_hip_ctx* ctx, const uint8_t* file_bytes, uint64_t n_bytes, const uint64_t* member_off /* [n_members] */,
+                             const uint32_t* member_bytes /* [n_members] */, uint32_t n_members, floria_hip_blob** out);
+uint64_t floria_hip_blob_bytes(const floria_hip_blob* blob);
+int  floria_hip_blob_download(const floria_hip_blob* blob, uint64_t off, void* dst, uint64_t bytes);
+void floria_hip_blob_free(floria_hip_blob* blob);
+
+/* The header-sized record table of a blob that holds BAM alignment records.  Chain c starts at byte begin[c] and follows the block_size prefixes while a whole record
+ * fits before end[c], one lane per chain (a host with a .bai gives one chain per contig; without an index there is one chain per segment); a second pass, one thread
+ * per record (count, scan, fill), returns per record the offset of its block_size prefix, block_size, refID, pos, mapq, flag, n_cigar_op, l_seq, l_read_name and its
+ * first CIGAR word (0 for a record without CIGAR), by which a host recognises the kSmN placeholder of a CG-tag record, and the names, compacted into one byte array
+ * (record i owns names[name_off[i] .. name_off[i + 1]): the l_read_name bytes as stored, the closing NUL included).  Records stand chain by chain: chain c owns records
+ * chain_rec_off[c] .. chain_rec_off[c + 1]; chain_stop[c] is the offset where it stopped.  From offset, l_read_name, n_cigar_op and l_seq the host computes
+ * cigar_off = offset + 36 + l_read_name, seq_off = cigar_off + 4 n_cigar_op and qual_off = seq_off + (l_seq + 1) / 2 itself.
+ * A block_size below the 32 fixed bytes of a record, or one that runs past end[c] (or a prefix cut by it), stops the chain: FLORIA_E_INVALID naming chain and offset —
+ * a chain that stops exactly at end[c] is complete.  Refused before any launch, FLORIA_E_INVALID: a null argument, a blob of another context, begin[c] > end[c] or
+ * end[c] past the blob.  FLORIA_E_UNSUPPORTED: 2^32 and more records.  The call works in buffers of its own and ends no residency; floria_hip_last_timing then reports
+ * pileup_ms (the kernels), h2d_ms, d2h_ms, total_ms. */
+typedef struct {
+    uint32_t  n_chains;
+    uint64_t  n_records;
+    uint64_t* chain_rec_off;   /* [n_chains+1] */
+    uint64_t* chain_stop;      /* [n_chains]   */
+    uint64_t* offset;          /* [n] byte offset of the record's block_size prefix in the blob */
+    uint32_t* block_size;      /* [n] */
+    int32_t*  ref_id;          /* [n] */
+    int32_t*  pos;             /* [n] */
+    uint32_t* l_seq;           /* [n] */
+    uint32_t* cigar0;          /* [n] the first CIGAR word (len << 4 | op), 0 if n_cigar_op == 0 */
+    uint16_t* flag;            /* [n] */
+    uint16_t* n_cigar_op;      /* [n] */
+    uint8_t*  mapq;            /* [n] */
+    uint8_t*  l_read_name;     /* [n] */
+    uint64_t* name_off;        /* [n+1] */
+    uint8_t*  names;           /* [name_off[n]] */
+} floria_blob_records;
+int  floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* begin /* [n_chains] */, const uint64_t* end /* [n_chains] */,
+                             uint32_t n_chains, floria_blob_records** out);
+void floria_hip_blob_records_free(floria_blob_records* r);
+
+/* floria_hip_pileup_records_resident whose record bytes are a blob handle: alignments->blob must be NULL (FLORIA_E_INVALID otherwise), alignments->blob_bytes is
+ * ignored and the offsets index the handle.  The same validation, against the handle's length; the same kernels, pointed at the handle's buffer; the same summary,
+ * token and RESIDENCY rule; no record byte is uploaded.  A blob of another context is FLORIA_E_INVALID.  The blob must stay alive while the call runs; the residency
+ * does not need it afterwards (the cells are in the context's pileup buffers). */
+int  floria_hip_pileup_records_resident_blob(floria_hip_ctx* ctx, const floria_hip_blob* blob, const floria_alignments* alignments, const floria_snp_table* snps,
+                                             const floria_ref_seqs* refs /* NULL = walk only */, const floria_realign_walk* walk /* NULL = exact DP */, floria_record_summary** out);
+
 /* A fragment plan: which records of the resident call form a fragment (a `Frag` after combine_frags, file_reader.rs:539-541 and :636-639), in which order they
  * are merged, and in which order the fragments of a contig stand.  All of it follows from names, flags and the per-record spans of the summary. */
 typedef struct {
@@ -695,7 +760,7 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
  * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
  * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic, the epilogue of floria_hip_reassign_batch_resident, floria_hip_join_paths, the device prologue of floria_hip_reassign_haplosets_resident — uses at most N workgroups, and the one-thread order kernel at most N threads,
- * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "hw_queues" (tests: override the number of
+ * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "inflate_slots" (tests: N >= 1 = floria_hip_inflate_bgzf keeps at most N members in flight, so that a wavefront of its persistent grid meets a second member; 0 = default, two per CU), "hw_queues" (tests: override the number of
  * concurrently running streams floria_hip_create measured — 6 on an MI355X whose host set GPU_MAX_HW_QUEUES=12 before HIP initialised, 4 or fewer
  * with the runtime's default; below 5 the launch plans stay within two job groups and do not speculate). */
 int  floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value);
