@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <math.h>
 
 namespace fl {
 
@@ -30,7 +31,33 @@ struct ContigDev {
     uint32_t        n_reads;
     uint32_t        pad;
     const uint32_t* set_order;  // [n_cells] or null: host-given iteration order of every read's position set (include/floria_hip.h), used by the reference-arithmetic mode
+    const uint32_t* cell_pk;    // [n_cells] or null: the packed cell (below) of the optimise kernel's 4-byte stream; null for contigs whose quality bytes never were on the device
 };
+
+// Packed cell: (SNP index - first SNP index of the read) << 12 | allele << 8 | quality byte.  One 4-byte word instead of cell_snp + cell_aw; the weight comes
+// from the 256-entry Q24 table (the one flatten_kernel folds into cell_aw).  A read whose span reaches 2^20 cannot be packed: its contig carries no cell_pk.
+constexpr uint32_t PK_DELTA_BITS = 20;
+constexpr uint32_t PK_DELTA_MAX  = (1u << PK_DELTA_BITS) - 1u;
+__host__ __device__ __forceinline__ bool     pk_fits(uint32_t delta) { return delta <= PK_DELTA_MAX; }
+__host__ __device__ __forceinline__ uint32_t pk_pack(uint32_t delta, uint32_t allele, uint32_t qual) { return (delta << 12) | ((allele & 15u) << 8) | (qual & 255u); }
+__host__ __device__ __forceinline__ uint32_t pk_delta(uint32_t pk)  { return pk >> 12; }
+__host__ __device__ __forceinline__ uint32_t pk_allele(uint32_t pk) { return (pk >> 8) & 15u; }
+__host__ __device__ __forceinline__ uint32_t pk_qual(uint32_t pk)   { return pk & 255u; }
+// The 256-entry Q24 weight table, phred_scale (utils_frags.rs:702-711): w = 1f32 - 10f32.powf(q as f32 / -10.), always k * 2^-24.  The one definition: floria_hip_create
+// fills the table flatten_kernel folds into cell_aw and the packed-cell instances of optimize_kernel stage in LDS.  False if some weight is not a multiple of 2^-24.
+inline bool w24_table(uint32_t* w24) {
+    bool exact = true;
+    for (int q = 0; q < 256; ++q) {
+        const float x = (float)q / -10.0f;
+        const float prob = 1.0f - powf(10.0f, x);
+        const double s = (double)prob * 16777216.0;
+        w24[q] = (uint32_t)s;
+        exact = exact && (double)w24[q] == s;
+    }
+    return exact;
+}
+// cell_aw of a packed cell, given the weight table: what flatten_kernel wrote beside it
+__host__ __device__ __forceinline__ uint32_t pk_to_aw(uint32_t pk, const uint32_t* w24) { return (pk_allele(pk) << 28) | w24[pk_qual(pk)]; }
 
 // A ContigDev is loaded from memory, so hipcc cannot tell that its pointers are global: loads through them would be FLAT loads, which
 // count in lgkmcnt as well as vmcnt (every LDS wait then also waits for them) and take the slower flat path.  G(p) asserts "global".

@@ -208,6 +208,8 @@ struct Knobs {
     int32_t  tail_overlap = 0;    // one ploidy per stage: the LAST ploidy's beam launch runs beside the optimise launch of the ploidy below, every job waiting for its block's
                                   // stop rule (run_phase): 0 off (default: measured level) | 1 on
     uint32_t tail_waves = 2;      // ... with this many waves per CU
+    uint32_t opt_packed = 1;      // optimise: the build / distance passes stream the 4-byte packed cells (ContigDev::cell_pk) with 16-byte loads where every contig of the call has
+                                  // them and the plan takes a 512-thread ploidy-specialised instance (plan_ploidies); 0 = the 8-byte cells (cell_snp + cell_aw)
     int32_t  fuse_p1 = -1;        // one ploidy per stage, canonical arithmetic, max_ploidy >= 2, ploidy-1 shortcut on: ploidy 1 has no launch of its own, the ploidy-2 optimise job
                                   // computes it from its own histogram (optimize_kernel.h, with_p1): -1 auto (on where eligible) | 0 off | 1 on where eligible
 };
@@ -451,6 +453,7 @@ struct PloidyPlan {
     uint32_t threads = 128, opt_slots = 0;
     size_t opt_lds = 0;
     bool hl = false, opt_spec = false;
+    bool opt_pk = false;          // optimise: the packed-cell instances (their weight table shares LDS with the candidate sort: no bytes of its own)
     uint32_t pm_lds_off = 0;      // optimise: where the visiting order of the reads (u16, longest first) sits in the workgroup's LDS (0 = none: the reads in block order)
     uint32_t fk_lds_off = 0;      // ... and the first-insertion keys as 32-bit words
     uint32_t fx_tags = 0;         // ... and the words of a map's claim table
@@ -464,6 +467,7 @@ struct PhaseShape {
     uint32_t n_jobs = 0;                // non-empty blocks
     uint64_t tot_reads = 0;             // reads of all blocks
     uint32_t n_max = 1, span_max = 1;   // most reads / widest SNP span of one block
+    bool all_pk = false;                // every contig with reads carries packed cells (ContigDev::cell_pk)
 };
 
 // s1_core's per-call device arrays that the launch loop reads and writes
@@ -508,7 +512,8 @@ hipError_t launch_beam(const PloidyPlan& q, bool arith, bool any_q0, bool spec, 
 }
 
 // The one place where a ploidy's plan becomes an optimise kernel instance:
-//   optimize_kernel<A, HL, THREADS = 128 | 512 | 1024>, and <2, true, 512 | 1024, p = 1..5> where the plan says opt_spec;
+//   optimize_kernel<A, HL, THREADS = 128 | 512 | 1024>, and <2, true, 512 | 1024, p = 1..5> where the plan says opt_spec, <2, true, 512, p = 1..5, false, 0, PK = true> where it also
+//   says opt_pk (packed cells);
 //   reference arithmetic: <A, HL, THREADS, 0, true>, <A, true, 512, 0, true, 4>, and <2, true, 512, p = 1..5, true, 0 | 4> (biallelic, histogram in LDS, ploidy <= 5).
 template <int A>
 hipError_t launch_optimize(const PloidyPlan& q, const Knobs& K, uint32_t slots, hipStream_t st, const fl::OptArgs& a) {
@@ -527,6 +532,7 @@ hipError_t launch_optimize(const PloidyPlan& q, const Knobs& K, uint32_t slots, 
         if (two_wg) return go(fl::optimize_kernel<A, true, 512, 0, true, 4>);
         return with_bool(q.hl, [&](auto HL) { return pick<1024, 512, 128>(q.threads, [&](auto T) { return go(fl::optimize_kernel<A, HL, T, 0, true>); }); });
     }
+    if (q.opt_spec && q.opt_pk) return pick<1, 2, 3, 4, 5>(q.p, [&](auto TP) { return go(fl::optimize_kernel<2, true, 512, TP, false, 0, true>); });
     if (q.opt_spec) return pick<1024, 512>(q.threads, [&](auto T) { return pick<1, 2, 3, 4, 5>(q.p, [&](auto TP) { return go(fl::optimize_kernel<2, true, T, TP>); }); });
     return with_bool(q.hl, [&](auto HL) { return pick<1024, 512, 128>(q.threads, [&](auto T) { return go(fl::optimize_kernel<A, HL, T>); }); });
 }
@@ -633,6 +639,8 @@ int plan_ploidies(const floria_hip_ctx* ctx, const floria_params* prm, const Pha
                 q.pm_lds_off = (uint32_t)q.opt_lds; q.opt_lds += pm_bytes;
             }
         }
+        // the packed-cell instances (optimize_kernel<.., PK = true>: biallelic, histogram in LDS, ploidy <= 5, 512 threads); their weight table takes no LDS of its own
+        q.opt_pk = K.opt_packed && S.all_pk && q.opt_spec && threads == 512;
         uint32_t per_cu = wg_per_cu(q.opt_lds);
         per_cu = std::min<uint32_t>(per_cu, 8);
         q.opt_slots = std::min<uint32_t>((uint32_t)ctx->n_cu * per_cu, nj_max);
@@ -844,6 +852,7 @@ int run_phase(floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S
                     a.release_tried = tail_p != 0 ? 1u : 0u;
                     a.with_p1 = p1_fused && p == 2 ? 1u : 0u;
                     a.pm_lds_off = q.pm_lds_off;
+                    a.w24 = ctx->d_w24.as<uint32_t>();
                     // (a plan with ANY speculative stage publishes ready bits and stop_at from every stage: a later stage's stop rule compares with these MEC values)
                     if (K.arith) {
                         a.cell_ord = ctx->cur_ord; a.cell_ord_off = ctx->cur_ord_off;
@@ -861,6 +870,7 @@ int run_phase(floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S
                     T.end(t);
                     if (le != hipSuccess) return fail(FLORIA_E_DEVICE, std::string("optimize_kernel launch: ") + hipGetErrorString(le));
                     ctx->timing.optimize_launches++;
+                    if (q.opt_spec && q.opt_pk && !K.arith) ctx->timing.optimize_packed_launches++;
                 }
                 if (tail_p && p + 1 == tail_p) {          // (queued AFTER the optimise launch it depends on: streams that share a hardware queue then still make progress)
                     if (!ctx->tstream[g]) HIPCHK(hipStreamCreateWithFlags(&ctx->tstream[g], hipStreamNonBlocking));
@@ -970,13 +980,7 @@ int floria_hip_create(int device, floria_hip_ctx** out) {
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(FLORIA_E_DEVICE, "hipStreamCreate failed"); }
     // phred_scale (utils_frags.rs:702-711): w = 1f32 - 10f32.powf(q as f32 / -10.), exact multiple of 2^-24
     uint32_t w24[256];
-    for (int q = 0; q < 256; ++q) {
-        float x = (float)q / -10.0f;
-        float prob = 1.0f - powf(10.0f, x);
-        double s = (double)prob * 16777216.0;
-        w24[q] = (uint32_t)s;
-        if ((double)w24[q] != s) { delete c; return fail(FLORIA_E_DEVICE, "quality weight is not a multiple of 2^-24"); }
-    }
+    if (!fl::w24_table(w24)) { delete c; return fail(FLORIA_E_DEVICE, "quality weight is not a multiple of 2^-24"); }
     memcpy(c->w24, w24, sizeof(w24));
     uint64_t s = 0xf10a1a2024ull;
     for (int k = 0; k < FLORIA_MAX_PLOIDY; ++k) { c->Rk1[k] = splitmix64(s) | 1ull; c->Rk2[k] = splitmix64(s) | 1ull; }
@@ -994,6 +998,7 @@ int floria_hip_create(int device, floria_hip_ctx** out) {
         if (const char* v = getenv("FLORIA_HIP_OPT_THREADS")) { const int tv = atoi(v); if (tv == 1024 || tv == 512 || tv == 128) K.opt_threads = (uint32_t)tv; }
         K.opt_global = getenv("FLORIA_HIP_OPT_GLOBAL") != nullptr;
         K.opt_block_order = getenv("FLORIA_HIP_OPT_BLOCK_ORDER") != nullptr;
+        if (const char* v = getenv("FLORIA_HIP_OPT_PACKED")) K.opt_packed = atoi(v) != 0;
         if (const char* v = getenv("FLORIA_HIP_SPECULATE")) K.speculate = std::max(-1, std::min(3, atoi(v)));
         K.trace = getenv("FLORIA_HIP_TRACE") != nullptr;
         if (const char* v = getenv("FLORIA_HIP_TAIL_OVERLAP")) K.tail_overlap = std::max(-1, std::min(1, atoi(v)));
@@ -1080,6 +1085,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "speculate") { if (value < -1 || value > 3) return fail(FLORIA_E_INVALID, "speculate: -1 auto | 0 | 1 | 2 | 3"); K.speculate = (int32_t)value; }
     else if (k == "no_bulk") K.no_bulk = value != 0;
     else if (k == "opt_block_order") K.opt_block_order = value != 0;
+    else if (k == "opt_packed") K.opt_packed = value != 0;
     else if (k == "tail_overlap") { if (value < -1 || value > 1) return fail(FLORIA_E_INVALID, "tail_overlap: 0 | 1"); K.tail_overlap = (int32_t)value; }
     else if (k == "fuse_p1") { if (value < -1 || value > 1) return fail(FLORIA_E_INVALID, "fuse_p1: -1 auto | 0 | 1"); K.fuse_p1 = (int32_t)value; }
     else if (k == "tail_waves") K.tail_waves = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 16));
@@ -1201,21 +1207,24 @@ namespace {
 // of resident contigs goes through (plan_upload, floria_hip_assemble_contigs, floria_hip_drop_monomorphic), so that their handles cannot differ in layout.  16-B tails:
 // the beam kernel's LDS-DMA moves cells in 16-B pieces.  The set-order region exists only when some contig carries one, the seq_pos region only when some contig carries
 // positions; it lies behind every other region, so no other offset depends on it.
-struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, o_sp = 0, bytes = 0; };
-ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so, bool any_sp) {
+struct ArenaLayout { size_t o_ro = 0, o_first = 0, o_last = 0, o_snp = 0, o_aw = 0, o_tw = 0, o_meta = 0, o_so = 0, o_sp = 0, o_pk = 0, bytes = 0; bool pk = false; };
+ArenaLayout layout_arena(uint64_t R, uint64_t C, uint32_t n, bool any_so, bool any_sp, bool pk) {
     ArenaLayout Y;
     Carve X;
     Y.o_ro = X.seg(4 * (R + n)).off; Y.o_first = X.seg(4 * R).off; Y.o_last = X.seg(4 * R).off; Y.o_snp = X.seg(4 * C + 16).off; Y.o_aw = X.seg(4 * C + 16).off;
     Y.o_tw = X.seg(16 * R).off; Y.o_meta = X.seg(32 * R).off;
     Y.o_so = any_so ? X.seg(4 * C + 16).off : 0;
     Y.o_sp = any_sp ? X.seg(4 * C + 16).off : 0;
+    // the packed cells (common.h): optimize_kernel reads them in aligned 16-B pieces, which may reach up to 12 bytes before a contig's first and behind its last cell -
+    // into the neighbouring contig's cells, or into the region's own head (256-B aligned) and tail (the 16 bytes here)
+    Y.pk = pk; Y.o_pk = pk ? X.seg(4 * C + 16).off : 0;
     Y.bytes = X.cursor;
     return Y;
 }
 // ... and contig i's views into them (rp / cp: reads / cells before every contig)
 void arena_contig(const ArenaLayout& Y, char* D, const std::vector<uint64_t>& rp, const std::vector<uint64_t>& cp, uint32_t i, fl::UploadContig& u) {
     u.read_off = (const uint32_t*)(D + Y.o_ro + 4 * (rp[i] + i)); u.first = (const uint32_t*)(D + Y.o_first + 4 * rp[i]); u.last = (const uint32_t*)(D + Y.o_last + 4 * rp[i]);
-    u.snp = (const uint32_t*)(D + Y.o_snp + 4 * cp[i]); u.cell_aw = (uint32_t*)(D + Y.o_aw + 4 * cp[i]); u.tw = (uint64_t*)(D + Y.o_tw + 16 * rp[i]); u.meta = (uint32_t*)(D + Y.o_meta + 32 * rp[i]);
+    u.snp = (const uint32_t*)(D + Y.o_snp + 4 * cp[i]); u.cell_aw = (uint32_t*)(D + Y.o_aw + 4 * cp[i]); u.cell_pk = Y.pk ? (uint32_t*)(D + Y.o_pk + 4 * cp[i]) : nullptr; u.tw = (uint64_t*)(D + Y.o_tw + 16 * rp[i]); u.meta = (uint32_t*)(D + Y.o_meta + 32 * rp[i]);
     u.n_reads = (uint32_t)(rp[i + 1] - rp[i]); u.n_cells = (uint32_t)(cp[i + 1] - cp[i]);
 }
 
@@ -1257,15 +1266,15 @@ struct UploadPlan {
     void release() { arena_put(A); A = nullptr; }      // (back to the cache without a wait: nothing was issued yet)
     uint32_t* so_at(uint32_t i) const { return (uint32_t*)(D + Y.o_so + 4 * cp[i]); }      // where contig i's set order / positions lie if it carries them
     uint32_t* sp_at(uint32_t i) const { return (uint32_t*)(D + Y.o_sp + 4 * cp[i]); }
-    fl::ContigDev dev(uint32_t i) const { const fl::UploadContig& u = ucd[i]; return fl::ContigDev{u.read_off, u.first, u.last, u.snp, u.cell_aw, u.tw, u.meta, u.n_reads, 0, so_dev[i]}; }      // what the kernels see of contig i
+    fl::ContigDev dev(uint32_t i) const { const fl::UploadContig& u = ucd[i]; return fl::ContigDev{u.read_off, u.first, u.last, u.snp, u.cell_aw, u.tw, u.meta, u.n_reads, 0, so_dev[i], u.cell_pk}; }      // what the kernels see of contig i
     // `raw`: the flatten launch reads raw allele / qual bytes from up_tmp (a host upload's DMA or assemble's FILL puts them there), and its tables lie behind them, with
     // `more` bytes of the caller's at t_more.  Without it nothing of up_tmp is touched: the producer writes the resident form and keeps the tables where it likes.
     int open(floria_hip_ctx* c, uint32_t n_contigs, std::vector<uint64_t> read_prefix, std::vector<uint64_t> cell_prefix, bool any_so, bool any_sp, floria_hip_contig** handles,
-             bool raw, size_t more = 0) {
+             bool raw, size_t more = 0, bool with_pk = false) {
         ctx = c; out = handles; n = n_contigs; rp = std::move(read_prefix); cp = std::move(cell_prefix); R = rp[n]; C = cp[n];
         ctx->upload_epoch++;                               // (device memory of contigs is about to be rewritten: cached cell orders no longer describe it)
         n_chunks = 1; chunk_first = {0, n}; contig_chunk.assign(n, 0);
-        Y = layout_arena(R, C, n, any_so, any_sp);
+        Y = layout_arena(R, C, n, any_so, any_sp, with_pk && raw);      // (packed cells are written by flatten_kernel, from the raw quality bytes)
         A = arena_get(ctx, Y.bytes + 256);
         if (!A) return FLORIA_E_NOMEM;
         A->n_contigs = n; A->R = R; A->C = C; A->off_ro = Y.o_ro; A->off_first = Y.o_first; A->off_last = Y.o_last; A->read_prefix = rp; A->host_meta = false;
@@ -1321,7 +1330,7 @@ int plan_upload(floria_hip_ctx* ctx, const floria_pileup* pileups, const floria_
         s_bo = X.seg(4 * (rp[n] + n)); s_pr = X.seg(pb[n] + 16); s_a2 = X.seg(cp[n] / 4 + n + 16); s_pk = X.seg(sizeof(fl::PackedContig) * n);
     }
     P.packed = pk != nullptr;
-    if (int rc = P.open(ctx, n, std::move(rp), std::move(cp), any_so, false, out, true, X.cursor)) return rc;      // (uploads carry no positions)
+    if (int rc = P.open(ctx, n, std::move(rp), std::move(cp), any_so, false, out, true, X.cursor, true)) return rc;      // (uploads carry no positions)
     const uint64_t C = P.C;
     const size_t o_ro = P.Y.o_ro, o_first = P.Y.o_first, o_last = P.Y.o_last, o_snp = P.Y.o_snp, t_al = P.t_al, t_q = P.t_q;
     const size_t t_bo = P.t_more + s_bo.off, t_pr = P.t_more + s_pr.off, t_a2 = P.t_more + s_a2.off;
@@ -1443,6 +1452,7 @@ int UploadPlan::commit() {
         c->ctx = ctx; c->arena = P.A; c->idx = i; c->n_reads = P.ucd[i].n_reads; c->n_cells = P.cp[i + 1] - P.cp[i];
         c->max_len = P.ust[i].max_len; c->n_alleles = P.ust[i].max_allele >= 2 ? 4 : 2; c->has_q0 = P.ust[i].has_q0 != 0;
         c->dev = dev(i);
+        if (P.ust[i].no_pk) c->dev.cell_pk = nullptr;      // (a read spanning 2^20 SNP indices: no block can hold it, but nothing may decode its packed cells either)
         c->seq_pos = P.sp_dev.empty() ? nullptr : P.sp_dev[i];
         out[i] = c;
     }
@@ -2063,7 +2073,9 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     struct ResultGuard { floria_hip_ctx* c; floria_block_result* r; ~ResultGuard() { if (r) { sync_all(c); floria_hip_block_result_free(r); } } } guard{ctx, R};   // every early return below
     if (!R->best_ploidy || !R->ploidies_tried || !R->read_off || (lists && (!R->read_id || !R->part)) || !R->mec) { return fail(FLORIA_E_NOMEM, "malloc"); }
     bool p1_shortcut = false;
-    const PhaseShape shape{bs, any_q0, (uint32_t)jobs.size(), tot, n_max, span_max};
+    bool all_pk = true;
+    for (const fl::ContigDev& cd : cdev) all_pk = all_pk && (cd.n_reads == 0 || cd.cell_pk != nullptr);
+    const PhaseShape shape{bs, any_q0, (uint32_t)jobs.size(), tot, n_max, span_max, all_pk};
     const PhaseBufs bufs{C.at<const uint32_t>(s_jobs), C.at<uint8_t>(s_planes), C.at<uint8_t>(s_bpart), C.at<double>(s_mec), C.at<double>(s_na), C.at<uint32_t>(s_it),
                          C.at<uint8_t>(s_done), C.at<uint32_t>(s_best), C.at<uint32_t>(s_tried), C.at<uint32_t>(s_stop), C.at<uint32_t>(s_ready), C.at<uint32_t>(s_q),
                          C.at<double>(s_margin), C.at<uint32_t>(s_diag), C.at<unsigned long long>(s_steps)};
@@ -2333,6 +2345,7 @@ static int phase_pileups_impl(floria_hip_ctx* ctx, const floria_pileup* pileups,
         }
         bool plan_ok = true;
         for (auto* h : handles) plan_ok = plan_ok && h->n_alleles == 2 && !h->has_q0;
+        for (uint32_t i = 0; i < n_contigs; ++i) plan_ok = plan_ok && !UP.ust[i].no_pk;      // (the plan took every contig's packed cells for granted)
         if (!plan_ok) {                                                                   // rare: phase again with the kernels this batch needs
             floria_hip_block_result_free(R); R = nullptr;
             if (int rc = floria_hip_phase_blocks_batch(ctx, handles.data(), n_contigs, blk_contig, blk_start, blk_end, n_blocks, prm, &R)) return rc;

@@ -80,6 +80,8 @@ struct OptArgs {
     uint32_t  fx_tags;           // words of a map's conflict-detection table (a power of two, FX_TAGS_MIN..FX_TAGS_MAX)
     uint32_t  pm_lds_off;        // != 0: the visiting order of the build and distance passes (u16 read indices, longest reads first) in LDS at this offset ([n_max])
     uint32_t  fk_lds_off;        // != 0: the first-insertion keys as 32-bit words (read << 12 | cell rank: reads < 2^20, cells per read < 2^12) in LDS at this offset ([ploidy*span_max])
+    // packed-cell instances (PK = true): the 256-entry Q24 weight table (what flatten_kernel folds into cell_aw), which the workgroup stages in LDS
+    const uint32_t* w24;
 };
 // fired(q): the reference's loop breaks at ploidy q (graph_processing.rs:196-251); needs mec[q-1] (q > 1) and mec[q], num_alleles[q]
 __device__ inline bool stop_rule_fires(const OptArgs& g, uint32_t b, uint32_t q) {
@@ -101,6 +103,9 @@ __device__ inline bool stop_rule_fires(const OptArgs& g, uint32_t b, uint32_t q)
 #endif
 
 // all-reduce (sum) over each row of 16 lanes with DPP (no LDS crossbar): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
+typedef uint32_t opt_u32x4 __attribute__((ext_vector_type(4)));      // four packed cells: one 16-byte global load
+constexpr int OPT_PK_LANES = 8;           // packed-cell instances: lanes per read (8 reads per wavefront)
+constexpr int OPT_PK_BU = 4, OPT_PK_DU = 2;      // ... and 16-byte pieces a lane requests per trip of the build pass / of a distance pass
 template <int CTRL> __device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xf, 0xf, false);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xf, 0xf, false);
@@ -110,6 +115,12 @@ __device__ __forceinline__ uint64_t row16_sum_u64(uint64_t v) {
     v += dpp_u64<0xB1>(v); v += dpp_u64<0x4E>(v); v += dpp_u64<0x141>(v); v += dpp_u64<0x140>(v);
     return v;
 }
+// ... over each half row of 8 lanes: the two quad_perm steps, then row_half_mirror (lane i <-> 7 - i of the half row)
+__device__ __forceinline__ uint64_t row8_sum_u64(uint64_t v) {
+    v += dpp_u64<0xB1>(v); v += dpp_u64<0x4E>(v); v += dpp_u64<0x141>(v);
+    return v;
+}
+template <int L> __device__ __forceinline__ uint64_t rowL_sum_u64(uint64_t v) { if constexpr (L == 8) return row8_sum_u64(v); else return row16_sum_u64(v); }
 
 // whole-wave sums by DPP inside the rows of 16 lanes and four v_readlane across them.  (The __shfl_xor butterflies of common.h need six lane-address registers that
 // hipcc computes before the job loop and keeps - spilled to scratch in the register-capped instances - until the loop is left: round 5 found the same in the beam kernel.)
@@ -120,6 +131,9 @@ __device__ __forceinline__ uint64_t opt_wave_sum_u64(uint64_t v) {
 }
 __device__ __forceinline__ uint32_t opt_wave_sum_u32(uint32_t v) { return (uint32_t)opt_wave_sum_u64((uint64_t)v); }
 
+// v, behind an empty asm: what is computed from it cannot be hoisted out of the job loop.  hipcc computes the addresses a thread touches first in a loop over `tid` once per
+// workgroup and keeps them for the whole job loop - in the 80-VGPR packed-cell instances, spilled to scratch
+__device__ __forceinline__ uint32_t opt_opaque(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ bool cand_before(uint64_t ga, uint32_t ka, uint64_t gb, uint32_t kb) {
     return ga > gb || (ga == gb && ka < kb);
 }
@@ -153,10 +167,14 @@ __device__ inline void bitonic_sort(G gain, K key, uint32_t n, int tid, int nthr
 // map (local_clustering.rs:226-256), which is emulated per partition (arith_kernel.h).
 // (the ploidy 1-3 instances of 512 threads are held to the 80 VGPRs that let three workgroups share a CU: six waves per SIMD)
 constexpr int OPT_WAVES_ARITH = 6;
-constexpr int opt_min_waves(int tp, int threads, bool arith, int ow = 0) { return arith ? (threads == 512 ? (ow ? ow : OPT_WAVES_ARITH) : 1) : ((threads == 512 && tp >= 1 && tp <= 3) ? 6 : 1); }      // (ARITH, 512 threads: 80 VGPRs = three workgroups per CU; the 149 hipcc takes when left alone leave one.  Measured on config 4, arith = 1: 4 / 5 / 6 waves 177 / 175 / 171 ms)
+constexpr int opt_min_waves(int tp, int threads, bool arith, int ow = 0, bool pk = false) { return arith ? (threads == 512 ? (ow ? ow : OPT_WAVES_ARITH) : 1) : ((threads == 512 && tp >= 1 && tp <= 3) ? 6 : (pk ? 5 : 1)); }      // (packed cells, ploidy 4 / 5: five waves as the 8-byte instances have, which hipcc left alone overshoots by three registers)      // (ARITH, 512 threads: 80 VGPRs = three workgroups per CU; the 149 hipcc takes when left alone leave one.  Measured on config 4, arith = 1: 4 / 5 / 6 waves 177 / 175 / 171 ms)
 // OW (ARITH): waves per SIMD to compile for, 0 = the default above (where LDS allows two workgroups per CU anyway — ploidy >= 3 on config 4 — four waves' worth of registers)
-template <int A, bool HL, int OPT_THREADS, int TP = 0, bool ARITH = false, int OW = 0>
-__global__ __launch_bounds__(OPT_THREADS) __attribute__((amdgpu_waves_per_eu(opt_min_waves(TP, OPT_THREADS, ARITH, OW))))
+// PK: the build pass and the distance passes stream ContigDev::cell_pk (4 bytes per cell, common.h) instead of cell_snp + cell_aw.  OPT_PK_LANES = 8 lanes share a read, and every
+// lane loads FOUR cells with one 16-byte load from the 16-byte aligned pieces that cover the read (the first and the last piece may reach up to three cells outside it: those are
+// masked by index, the arena pads the array).  Per lane the build pass has 4 loads x 16 B in flight where the 8-byte stream has 16 x 4 B, the distance pass 2 x 16 B for 8 x 4 B —
+// and eight reads per wavefront instead of four, so a wavefront asks for as many bytes per trip as before although a read is half as many.  Weights: the 256-entry table in LDS.
+template <int A, bool HL, int OPT_THREADS, int TP = 0, bool ARITH = false, int OW = 0, bool PK = false>
+__global__ __launch_bounds__(OPT_THREADS) __attribute__((amdgpu_waves_per_eu(opt_min_waves(TP, OPT_THREADS, ARITH, OW, PK))))
 void optimize_kernel(OptArgs g) {
     extern __shared__ __align__(16) unsigned char smem[];   // moved bitset [n_max/8 rounded] | histogram (HL)
     __shared__ uint64_t s_gain[OPT_SORT_LDS];
@@ -175,6 +193,8 @@ void optimize_kernel(OptArgs g) {
     __shared__ uint32_t s_ldir[2][MAX_PLOIDY];       // ... list [parity][k] came from the home-bucket rule (no first-insertion keys stand behind it)
     __shared__ uint32_t s_bpar[MAX_PLOIDY], s_tpar[MAX_PLOIDY], s_keep[MAX_PLOIDY];      // ARITH: which of its two lists holds partition k's ACCEPTED order / the order of the partition being scored; keys unchanged
     uint32_t* s_moved = (uint32_t*)smem;
+    static_assert(!PK || (HL && !ARITH && TP >= 1 && TP <= OPT_PK_LANES), "packed cells: ploidy-specialised canonical instances with the histogram in LDS");
+    constexpr int LPR = PK ? OPT_PK_LANES : 16;      // lanes per read of the build / distance passes
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t p = TP ? (uint32_t)TP : g.ploidy, PA = p * A;
@@ -198,6 +218,10 @@ void optimize_kernel(OptArgs g) {
     uint64_t* cgain = g.cand_gain_pool + (uint64_t)blockIdx.x * g.cand_cap;
     uint32_t* ckey = g.cand_key_pool + (uint64_t)blockIdx.x * g.cand_cap;
     uint32_t* moves = g.moves_pool + (uint64_t)blockIdx.x * g.n_max;
+    // (PK) the weight table lives in the first KB of the candidate sort's s_gain, which is idle whenever a pass streams cells: no LDS of its own, so no plan loses a workgroup per CU
+    // to it (ploidy 2 on config 4 sits 1 KB below that edge).  It is staged when a job starts and again behind every sort that used s_gain; barriers stand between either and the next pass.
+    uint32_t* const wt = (uint32_t*)s_gain;
+    auto stage_weights = [&]() { if constexpr (PK) for (uint32_t x = tid; x < 256u; x += OPT_THREADS) wt[x] = g.w24[x]; };
 
     for (;;) {
         __syncthreads();
@@ -228,9 +252,13 @@ void optimize_kernel(OptArgs g) {
 #endif
 
         // ---- hap_block_from_partition (utils_frags.rs:177-184): phred sums and unit counts in one cell -----
-        for (uint32_t x = tid; x < ncell; x += OPT_THREADS) hist[x] = 0;
-        if (tid < MAX_PLOIDY) s_size[tid] = 0;
-        if (tid < OPT_BUCKETS) s_bkt[tid] = 0;
+        {
+            const uint32_t tq = PK ? opt_opaque((uint32_t)tid) : (uint32_t)tid;      // (PK: addresses that are not kept across the job loop, see opt_opaque)
+            for (uint32_t x = tq; x < ncell; x += OPT_THREADS) hist[x] = 0;
+            if (tq < (uint32_t)MAX_PLOIDY) s_size[tq] = 0;
+            if (tq < (uint32_t)OPT_BUCKETS) s_bkt[tq] = 0;
+        }
+        stage_weights();
         __syncthreads();
         // stage (first cell, #cells, partition) of every read once: the chain reads[i] -> read_off[r] -> cells is then one hop
         const bool meta = meta_n != 0;
@@ -273,10 +301,42 @@ void optimize_kernel(OptArgs g) {
         };
         // 16 lanes per read (4 reads per wavefront, 16 per workgroup pass): 64-B coalesced cell segments, up to 8 cells
         // per lane loaded before the first atomic
-        const uint32_t grp = tid >> 4, sub = tid & 15;
+        const uint32_t grp = tid / LPR, sub = tid % LPR;
         const uint32_t n16 = (n + 15) & ~15u;
+        auto visit = [&](uint32_t iv) -> uint32_t { return (m_pm && iv < n) ? (uint32_t)m_pm[iv] : iv; };
+        // (PK) the read's first position relative to the block, and the 16-byte pieces that cover its cells: piece q holds the cells 4q - mis .. 4q - mis + 3 of the read
+        auto first_rel = [&](uint32_t i) -> uint32_t { return (meta && span <= 65535u) ? (m_fl[i] & 0xffffu) : G(cd.first)[reads[i]] - pos0; };
+        auto pieces = [&](uint32_t cb, uint32_t len, uint32_t& mis, uint32_t& L) -> const opt_u32x4* {
+            const uint32_t* pp = cd.cell_pk + cb;
+            mis = len ? ((uint32_t)(uintptr_t)pp >> 2) & 3u : 0u; L = len ? len + mis : 0u;
+            return (const opt_u32x4*)(pp - mis);
+        };
+        if constexpr (PK) {
+            for (uint32_t iv = grp; iv < n16; iv += OPT_THREADS / LPR) {
+                const uint32_t i = visit(iv);
+                uint32_t cb = 0, len = 0, k = 0, mis = 0, L = 0, f0 = 0;
+                if (i < n) { read_meta(i, cb, len, k); f0 = first_rel(i); }
+                const opt_u32x4* q4 = pieces(cb, len, mis, L);
+                uint64_t* hrow = hist + (uint64_t)f0 * PA + k * A;
+                for (uint32_t q0 = sub; 4u * q0 < L; q0 += LPR * OPT_PK_BU) {          // four pieces = 16 cells per lane requested before the first atomic
+                    opt_u32x4 v[OPT_PK_BU];
+#pragma unroll
+                    for (int u = 0; u < OPT_PK_BU; ++u) { const uint32_t q = q0 + LPR * u; v[u] = 4u * q < L ? G(q4)[q] : opt_u32x4{0u, 0u, 0u, 0u}; }
+#pragma unroll
+                    for (int u = 0; u < OPT_PK_BU; ++u) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const uint32_t j = 4u * (q0 + LPR * u) + e, pk = v[u][e];
+                            if (j >= mis && j < L)
+                                atomicAdd((unsigned long long*)&hrow[(uint64_t)pk_delta(pk) * PA + pk_allele(pk)], (unsigned long long)((1ull << CNT_SHIFT) | wt[pk_qual(pk)]));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);          // (one piece at a time: without the two barriers of this kind the ploidy-3 instance spills two registers)
+                    }
+                }
+            }
+        } else
         for (uint32_t iv = grp; iv < n16; iv += OPT_THREADS / 16) {
-            const uint32_t i = (m_pm && iv < n) ? (uint32_t)m_pm[iv] : iv;
+            const uint32_t i = visit(iv);
             uint32_t cb = 0, len = 0, k = 0;
             if (i < n) read_meta(i, cb, len, k);
             for (uint32_t c0 = sub; c0 < len; c0 += 16 * 8) {
@@ -783,8 +843,8 @@ void optimize_kernel(OptArgs g) {
                 const bool incremental = HL && meta && it > 0 && span <= 65535u;
                 const uint32_t chg_lo = incremental ? s_chg_lo : 0u, chg_hi = incremental ? s_chg_hi : 0xffffffffu;
                 if constexpr (ARITH) { /* the distances of this round were computed beside the last statistics call (dist_arith) */                } else
-                for (uint32_t iv = grp; iv < n16; iv += OPT_THREADS / 16) {
-                    const uint32_t i = (m_pm && iv < n) ? (uint32_t)m_pm[iv] : iv;
+                for (uint32_t iv = grp; iv < n16; iv += OPT_THREADS / LPR) {
+                    const uint32_t i = visit(iv);
                     uint32_t cb = 0, len = 0, kk = 0;
                     if (i < n) read_meta(i, cb, len, kk);
                     if (incremental && i < n) {             // no code changed at any position of this read: its distances stand
@@ -794,6 +854,34 @@ void optimize_kernel(OptArgs g) {
                     uint64_t acc[KMAX];
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) acc[k] = 0;
+                    if constexpr (PK) {
+                        uint32_t mis = 0, L = 0;
+                        const opt_u32x4* q4 = pieces(cb, len, mis, L);
+                        const uint8_t* cbase = codes + (i < n && len ? first_rel(i) : 0u) * p;
+                        for (uint32_t q0 = sub; 4u * q0 < L; q0 += LPR * OPT_PK_DU) {          // two pieces = 8 cells per lane and trip, 64 cells per read as in the 8-byte stream
+                            opt_u32x4 v[OPT_PK_DU];
+#pragma unroll
+                            for (int u = 0; u < OPT_PK_DU; ++u) { const uint32_t q = q0 + LPR * u; v[u] = 4u * q < L ? G(q4)[q] : opt_u32x4{0u, 0u, 0u, 0u}; }
+#pragma unroll
+                            for (int u = 0; u < OPT_PK_DU; ++u) {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) {
+                                    const uint32_t j = 4u * (q0 + LPR * u) + e, pk = v[u][e];
+                                    if (j >= mis && j < L) {
+                                        const uint32_t al = pk_allele(pk);
+                                        const uint64_t w = wt[pk_qual(pk)];
+                                        const uint8_t* crow = cbase + pk_delta(pk) * p;
+#pragma unroll
+                                        for (int k = 0; k < KMAX; ++k) {
+                                            const uint32_t c = crow[k];
+                                            acc[k] += c == 0 ? 1ull : (((c >> al) & 1u) ? 0ull : (w << 16));
+                                        }
+                                    }
+                                }
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
+                    } else
                     for (uint32_t c0 = sub; c0 < len; c0 += 16 * 4) {
                         uint32_t sn[4], aqs[4];
 #pragma unroll
@@ -830,7 +918,7 @@ void optimize_kernel(OptArgs g) {
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) {
                         if ((uint32_t)k < p) {
-                            const uint64_t t = row16_sum_u64(acc[k]);
+                            const uint64_t t = rowL_sum_u64<LPR>(acc[k]);
                             if (sub == (uint32_t)k && i < n && len != 0) dist[i * p + k] = qm_to_f64(t >> 16, t & 0xffff, g.eps);
                         }
                     }
@@ -858,9 +946,10 @@ void optimize_kernel(OptArgs g) {
                 while (M2 < M) M2 <<= 1;
                 const bool in_lds = M2 <= OPT_SORT_LDS;
                 if (in_lds) {
-                    for (uint32_t x = tid; x < M2; x += OPT_THREADS) { s_gain[x] = x < M ? cgain[x] : 0; s_key[x] = x < M ? ckey[x] : 0xffffffffu; }
+                    for (uint32_t x = PK ? opt_opaque((uint32_t)tid) : (uint32_t)tid; x < M2; x += OPT_THREADS) { s_gain[x] = x < M ? cgain[x] : 0; s_key[x] = x < M ? ckey[x] : 0xffffffffu; }
                     __syncthreads();
                     bitonic_sort(s_gain, s_key, M2, tid, OPT_THREADS);          // best_moves.sort_by(desc) :330
+                    stage_weights();          // (the moves are read from s_key; s_gain is the weight table again)
                 } else {
                     for (uint32_t x = M + tid; x < M2; x += OPT_THREADS) { cgain[x] = 0; ckey[x] = 0xffffffffu; }
                     __syncthreads();

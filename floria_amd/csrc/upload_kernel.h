@@ -3,6 +3,7 @@
 // indices, allele index < 4) and flatten them into the resident form the clustering kernels read:
 //
 //   cell_aw[c] = allele << 28 | w24[qual]      phred_scale (utils_frags.rs:702-711) folded into the cell, no LUT in any kernel
+//   cell_pk[c] = (snp - first) << 12 | allele << 8 | qual      the optimise kernel's 4-byte cell (common.h), where the contig has the array
 //   tw[2r..]   = sum over the read's cells of Rq{1,2}[hash_idx(snp, allele)] * w   (the read's term of the linear state hash)
 //   meta[8r..] = {cell offset, cell count, first, last, tw1 lo/hi, tw2 lo/hi}       one 32-B record per beam step
 //
@@ -25,13 +26,14 @@ struct UploadContig {              // raw inputs (device copies) and flattened o
     const uint8_t*  allele;        // [n_cells] raw, transient
     const uint8_t*  qual;          // [n_cells] raw, transient
     uint32_t* cell_aw;
+    uint32_t* cell_pk;             // packed cells (common.h) or null: this contig gets none
     uint64_t* tw;
     uint32_t* meta;
     uint32_t  n_reads, n_cells;    // n_cells = read_off[n_reads] as the host read it (bounds every cell access)
 };
 struct UploadStatus {              // per contig, zero-initialised except err
     unsigned long long err;        // min over failing reads of (read << 8 | code); ~0 = valid
-    uint32_t max_len, max_allele, has_q0, pad;
+    uint32_t max_len, max_allele, has_q0, no_pk;      // no_pk: some read spans 2^20 SNP indices or more, its cells cannot be packed
 };
 struct UploadArgs {
     const UploadContig* contigs;
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(64) void flatten_kernel(UploadArgs g) {
         const bool live = lr < g.n_reads_total;
         if (live) while (g.read_prefix[ci + 1] <= gr) ++ci;
         uint64_t t1 = 0, t2 = 0;
-        uint32_t r = 0, b = 0, e = 0, code = UP_OK, ma = 0, q0 = 0, F = 0, L = 0;
+        uint32_t r = 0, b = 0, e = 0, code = UP_OK, ma = 0, q0 = 0, F = 0, L = 0, npk = 0;
         UploadContig cd{};
         if (live) {
             cd = g.contigs[ci];
@@ -195,6 +197,7 @@ __global__ __launch_bounds__(64) void flatten_kernel(UploadArgs g) {
                         if (c >= e) break;
                         if (c > b && sn[u] <= sp[u]) flag(UP_NOT_ASCENDING);
                         cd.cell_aw[c] = (al[u] << 28) | w[u];
+                        if (cd.cell_pk) { const uint32_t d = sn[u] - F; cd.cell_pk[c] = pk_pack(d, al[u], q[u]); npk |= pk_fits(d) ? 0u : 1u; }
                         ma = al[u] > ma ? al[u] : ma; q0 |= q[u] == 0 ? 1u : 0u;
                         t1 += r1[u] * (uint64_t)w[u]; t2 += r2[u] * (uint64_t)w[u];
                     }
@@ -204,9 +207,9 @@ __global__ __launch_bounds__(64) void flatten_kernel(UploadArgs g) {
         t1 = row_sum(t1); t2 = row_sum(t2);
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) {
-            const uint32_t oc = __shfl_xor(code, o), om = __shfl_xor(ma, o), oq = __shfl_xor(q0, o);
+            const uint32_t oc = __shfl_xor(code, o), om = __shfl_xor(ma, o), oq = __shfl_xor(q0, o), on = __shfl_xor(npk, o);
             code = (oc != UP_OK && (code == UP_OK || oc < code)) ? oc : code;
-            ma = om > ma ? om : ma; q0 |= oq;
+            ma = om > ma ? om : ma; q0 |= oq; npk |= on;
         }
         if (live && sub == 0) {
             cd.tw[2 * (uint64_t)r] = t1; cd.tw[2 * (uint64_t)r + 1] = t2;
@@ -217,6 +220,7 @@ __global__ __launch_bounds__(64) void flatten_kernel(UploadArgs g) {
             atomicMax(&st->max_len, e - b);
             if (ma) atomicMax(&st->max_allele, ma);
             if (q0) atomicOr(&st->has_q0, 1u);
+            if (npk) atomicOr(&st->no_pk, 1u);
             if (code != UP_OK) atomicMin(&st->err, ((unsigned long long)r << 8) | code);
         }
     }

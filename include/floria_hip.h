@@ -167,7 +167,7 @@ typedef struct {
     uint64_t upload_pinned_bytes; /* last upload: bytes that went by DMA straight from the caller's pinned memory */
     uint64_t upload_staged_bytes; /* last upload: bytes staged through the library's pinned ring (pageable sources)  */
     uint32_t upload_chunks;    /* floria_hip_phase_pileups_batch: chunks whose transfer overlapped the kernels (1 = not pipelined) */
-    uint32_t reserved;
+    uint32_t optimize_packed_launches; /* optimise launches of the last S1 call that streamed the 4-byte packed cells ("opt_packed"); the others read the 8-byte cells */
     double   beam_union_ms;    /* wall time with at least one beam-search launch in flight (<= phase_ms; beam_ms, a sum over overlapping launches, can exceed it) */
     double   optimize_union_ms;/* ... with at least one optimise launch in flight */
     double   pileup_ms;        /* floria_hip_pileup_records: sum over the call's launches (count pass, offset scan, fill pass).  Appended with that entry point:
@@ -755,7 +755,10 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * default 2), "fuse_p1" (one ploidy per stage, canonical arithmetic, max_ploidy >= 2, ploidy-1 shortcut on: ploidy 1 gets no launches of its own, a block's ploidy-2
  * optimise job computes its MEC statistics and stop rule from the histogram it has built anyway; -1 auto = default = on where eligible, 0 off, 1 on where eligible;
  * FLORIA_HIP_FUSE_P1 in the environment), "beam_path" (0 auto, 1 generic, 2 slab, 3 wide), "no_specialized", "no_p1_shortcut", "opt_threads"
- * (0|128|512|1024), "opt_global", "opt_block_order" (tests / A/B: the optimise kernel's passes visit a block's reads in block order instead of longest first), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
+ * (0|128|512|1024), "opt_global", "opt_block_order" (tests / A/B: the optimise kernel's passes visit a block's reads in block order instead of longest first),
+ * "opt_packed" (1 = default: the optimise kernel's build and distance passes stream one 4-byte packed cell per cell — SNP delta, allele, quality byte, weights from a table
+ * in LDS — with 16-byte loads, where every contig of the call was uploaded through the library's flatten launch and the kernel is a ploidy-specialised instance; 0 = the
+ * 8-byte cells everywhere; FLORIA_HIP_OPT_PACKED in the environment), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
  * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
