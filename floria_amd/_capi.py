@@ -13,6 +13,8 @@ FLORIA_FIELD_SET_ORDER = 7      # floria_hip_contig_download: uint32 [n_cells] o
 FLORIA_FIELD_SEQ_POS = 8        # ... uint32 [n_cells], the SEQ_POS words (mate << 31 | seq_pos) of a contig that carries positions
 FLORIA_ASM_DERIVE_SET_ORDER = 1
 FLORIA_ASM_KEEP_SEQ_POS = 2
+FLORIA_CHAIN_CUT_TAIL = 1       # floria_hip_blob_records_opt: a prefix or record cut by end[c] ends the chain without an error
+FLORIA_CHAIN_ONE_REF = 2        # ... the chain ends in front of the first record of another reference
 FLORIA_SPAN_NONE = 0xFFFFFFFF
 FLORIA_MAX_ALLELES = 4
 FLORIA_MAX_PLOIDY = 16
@@ -107,7 +109,11 @@ class CRecordSummary(C.Structure):
 class CBlobRecords(C.Structure):
     _fields_ = [("n_chains", C.c_uint32), ("n_records", C.c_uint64), ("chain_rec_off", u64p), ("chain_stop", u64p), ("offset", u64p), ("block_size", u32p),
                 ("ref_id", i32p), ("pos", i32p), ("l_seq", u32p), ("cigar0", u32p), ("flag", u16p), ("n_cigar_op", u16p), ("mapq", u8p), ("l_read_name", u8p),
-                ("name_off", u64p), ("names", u8p)]
+                ("name_off", u64p), ("names", u8p), ("chain_why", u32p)]
+
+
+class CBlobSequences(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("base_off", u64p), ("bases", u8p), ("quals", u8p)]
 
 
 class CFragmentPlan(C.Structure):

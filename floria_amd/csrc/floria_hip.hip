@@ -53,6 +53,7 @@
 #include "haploset_kernel.h"
 #include "path_kernel.h"
 #include "inflate_kernel.h"
+#include "blob_seq_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -284,6 +285,7 @@ struct floria_hip_ctx {
     DevBuf join_bits;                         // floria_hip_join_paths: the paths' bitmaps
     DevBuf inf_in;                            // floria_hip_inflate_bgzf: the compressed bytes and the per-member tables (the blob has a buffer of its own)
     DevBuf rec_in, rec_out, rec_names;        // floria_hip_blob_records: the chains' tables, the per-record arrays, the compacted names (buffers of their own: no residency ends)
+    DevBuf seq_in, seq_out;                   // floria_hip_blob_sequences: the records' offsets, and the bases and qualities (buffers of their own: no residency ends)
     uint32_t inflate_slots = 0;               // (tests) floria_hip_inflate_bgzf: members in flight, 0 = two per CU
     uint32_t stage_threads = 8;
 };
@@ -1025,7 +1027,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits, &c->inf_in, &c->rec_in, &c->rec_out, &c->rec_names}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits, &c->inf_in, &c->rec_in, &c->rec_out, &c->rec_names, &c->seq_in, &c->seq_out}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -2974,15 +2976,22 @@ void floria_hip_blob_free(floria_hip_blob* b) {
 
 void floria_hip_blob_records_free(floria_blob_records* r) {
     if (!r) return;
-    for (void* p : {(void*)r->chain_rec_off, (void*)r->chain_stop, (void*)r->offset, (void*)r->block_size, (void*)r->ref_id, (void*)r->pos, (void*)r->l_seq, (void*)r->cigar0,
+    for (void* p : {(void*)r->chain_rec_off, (void*)r->chain_stop, (void*)r->chain_why, (void*)r->offset, (void*)r->block_size, (void*)r->ref_id, (void*)r->pos, (void*)r->l_seq, (void*)r->cigar0,
                     (void*)r->flag, (void*)r->n_cigar_op, (void*)r->mapq, (void*)r->l_read_name, (void*)r->name_off, (void*)r->names}) g_big.put(p);
     free(r);
 }
 
+static_assert(FLORIA_CHAIN_CUT_TAIL == fl::CHAIN_CUT_TAIL && FLORIA_CHAIN_ONE_REF == fl::CHAIN_ONE_REF, "chain flags out of sync");
+
 int floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* begin, const uint64_t* end, uint32_t nch, floria_blob_records** out) {
+    return floria_hip_blob_records_opt(ctx, blob, begin, end, nch, 0, out);
+}
+
+int floria_hip_blob_records_opt(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* begin, const uint64_t* end, uint32_t nch, uint32_t flags, floria_blob_records** out) {
     if (!ctx || !blob || !out || (nch && (!begin || !end))) return fail(FLORIA_E_INVALID, "null argument");
     *out = nullptr;
     if (blob->ctx != ctx) return fail(FLORIA_E_INVALID, "the blob belongs to another context");
+    if (flags & ~(uint32_t)(FLORIA_CHAIN_CUT_TAIL | FLORIA_CHAIN_ONE_REF)) return fail(FLORIA_E_INVALID, "blob_records: flags " + std::to_string(flags) + " (FLORIA_CHAIN_CUT_TAIL | FLORIA_CHAIN_ONE_REF)");
     for (uint32_t c = 0; c < nch; ++c)
         if (begin[c] > end[c] || end[c] > blob->bytes)
             return fail(FLORIA_E_INVALID, "blob_records: chain " + std::to_string(c) + " [" + std::to_string(begin[c]) + ", " + std::to_string(end[c]) + ") is no range of the blob (" + std::to_string(blob->bytes) + " bytes)");
@@ -2990,8 +2999,8 @@ int floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, co
     if (!R) return fail(FLORIA_E_NOMEM, "calloc");
     struct Guard { floria_blob_records* r; hipStream_t st; ~Guard() { if (r) { (void)hipStreamSynchronize(st); floria_hip_blob_records_free(r); } } } guard{R, ctx->stream};
     R->n_chains = nch;
-    R->chain_rec_off = (uint64_t*)cells_bytes(8ull * ((uint64_t)nch + 1)); R->chain_stop = (uint64_t*)cells_bytes(8ull * nch);
-    if (!R->chain_rec_off || !R->chain_stop) return fail(FLORIA_E_NOMEM, "malloc");
+    R->chain_rec_off = (uint64_t*)cells_bytes(8ull * ((uint64_t)nch + 1)); R->chain_stop = (uint64_t*)cells_bytes(8ull * nch); R->chain_why = (uint32_t*)cells_bytes(4ull * nch);
+    if (!R->chain_rec_off || !R->chain_stop || !R->chain_why) return fail(FLORIA_E_NOMEM, "malloc");
     R->chain_rec_off[0] = 0;
     ctx->timing = floria_timing{};
     uint64_t N = 0, name_bytes = 0;
@@ -3001,14 +3010,14 @@ int floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, co
         HIPCHK(hipSetDevice(ctx->device));
         const uint32_t n_tiles = (nch + fl::PILEUP_SCAN_TILE - 1) / fl::PILEUP_SCAN_TILE;
         Carve C;
-        const Seg s_b = C.seg(8ull * nch), s_e = C.seg(8ull * nch), s_cnt = C.seg(8ull * ((uint64_t)nch + 1)), s_stop = C.seg(8ull * nch), s_st = C.seg(4ull * nch), s_tile = C.seg(8ull * n_tiles);
+        const Seg s_b = C.seg(8ull * nch), s_e = C.seg(8ull * nch), s_cnt = C.seg(8ull * ((uint64_t)nch + 1)), s_stop = C.seg(8ull * nch), s_st = C.seg(4ull * nch), s_why = C.seg(4ull * nch), s_tile = C.seg(8ull * n_tiles);
         if (int rc = C.place(ctx->rec_in)) return rc;
         int t = T.begin(K_H2D);
         HIPCHK(C.up(s_b, begin, 8ull * nch, ctx->stream)); HIPCHK(C.up(s_e, end, 8ull * nch, ctx->stream));
         T.end(t);
         fl::ChainArgs a{};
         a.blob = blob->buf.as<const uint8_t>(); a.blob_bytes = blob->bytes; a.begin = C.at<const uint64_t>(s_b); a.end = C.at<const uint64_t>(s_e);
-        a.count = C.at<uint64_t>(s_cnt); a.stop = C.at<uint64_t>(s_stop); a.status = C.at<uint32_t>(s_st); a.n_chains = nch;
+        a.count = C.at<uint64_t>(s_cnt); a.stop = C.at<uint64_t>(s_stop); a.status = C.at<uint32_t>(s_st); a.why = C.at<uint32_t>(s_why); a.n_chains = nch; a.flags = flags;
         t = T.begin(K_PILEUP);
         hipLaunchKernelGGL(fl::blob_chain_kernel<false>, dim3((nch + 255) / 256), dim3(256), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
@@ -3020,6 +3029,7 @@ int floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, co
         HIPCHK(hipMemcpyAsync(R->chain_rec_off, a.count, 8ull * ((uint64_t)nch + 1), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(R->chain_stop, a.stop, 8ull * nch, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(status.data(), a.status, 4ull * nch, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(R->chain_why, a.why, 4ull * nch, hipMemcpyDeviceToHost, ctx->stream));
         T.end(t);
         HIPCHK(hipStreamSynchronize(ctx->stream));
         for (uint32_t c = 0; c < nch; ++c)
@@ -3077,6 +3087,67 @@ int floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, co
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if (nch) T.publish(ctx->timing);
+    guard.r = nullptr;
+    *out = R;
+    return 0;
+}
+
+void floria_hip_blob_sequences_free(floria_blob_sequences* r) {
+    if (!r) return;
+    g_big.put(r->base_off); g_big.put(r->bases); g_big.put(r->quals);
+    free(r);
+}
+
+int floria_hip_blob_sequences(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* seq_off, const uint32_t* l_seq, const uint64_t* qual_off, uint64_t n, floria_blob_sequences** out) {
+    if (!ctx || !blob || !out || (n && (!seq_off || !l_seq || !qual_off))) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    if (blob->ctx != ctx) return fail(FLORIA_E_INVALID, "the blob belongs to another context");
+    if (n >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "blob_sequences: 2^32 and more records");
+    // the host part: every range against the blob's length, before anything is uploaded or launched
+    const uint64_t B = blob->bytes;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t ls = l_seq[i], packed = (ls + 1) / 2;
+        const char* what = seq_off[i] > B || packed > B - seq_off[i] ? "sequence" : qual_off[i] > B || ls > B - qual_off[i] ? "quality" : nullptr;
+        if (what) return fail(FLORIA_E_INVALID, std::string("blob_sequences: the ") + what + " bytes of record " + std::to_string(i) + " reach past the blob (" + std::to_string(B) + " bytes)");
+        total += ls;
+    }
+    if (total >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "blob_sequences: 2^32 and more bases (" + std::to_string(total) + ")");
+    floria_blob_sequences* R = (floria_blob_sequences*)calloc(1, sizeof(floria_blob_sequences));
+    if (!R) return fail(FLORIA_E_NOMEM, "calloc");
+    struct Guard { floria_blob_sequences* r; hipStream_t st; ~Guard() { if (r) { (void)hipStreamSynchronize(st); floria_hip_blob_sequences_free(r); } } } guard{R, ctx->stream};
+    R->n = n;
+    R->base_off = (uint64_t*)cells_bytes(8 * (n + 1)); R->bases = (uint8_t*)cells_bytes(total); R->quals = (uint8_t*)cells_bytes(total);
+    if (!R->base_off || !R->bases || !R->quals) return fail(FLORIA_E_NOMEM, "malloc");
+    R->base_off[0] = 0;
+    for (uint64_t i = 0; i < n; ++i) R->base_off[i + 1] = R->base_off[i] + l_seq[i];
+    ctx->timing = floria_timing{};
+    if (total) {
+        HIPCHK(hipSetDevice(ctx->device));
+        Carve C, O;
+        const Seg s_so = C.seg(8 * n), s_qo = C.seg(8 * n), s_ls = C.seg(4 * n), s_bo = C.seg(8 * (n + 1));
+        const Seg o_b = O.seg(total), o_q = O.seg(total);
+        if (int rc = C.place(ctx->seq_in)) return rc;
+        if (int rc = O.place(ctx->seq_out)) return rc;
+        EventTimer T(ctx->stream);
+        int t = T.begin(K_H2D);
+        HIPCHK(C.up(s_so, seq_off, 8 * n, ctx->stream)); HIPCHK(C.up(s_qo, qual_off, 8 * n, ctx->stream)); HIPCHK(C.up(s_ls, l_seq, 4 * n, ctx->stream));
+        HIPCHK(C.up(s_bo, R->base_off, 8 * (n + 1), ctx->stream));
+        T.end(t);
+        fl::BlobSeqArgs a{};
+        a.blob = blob->buf.as<const uint8_t>(); a.seq_off = C.at<const uint64_t>(s_so); a.qual_off = C.at<const uint64_t>(s_qo); a.l_seq = C.at<const uint32_t>(s_ls);
+        a.base_off = C.at<const uint64_t>(s_bo); a.bases = O.at<uint8_t>(o_b); a.quals = O.at<uint8_t>(o_q); a.n = n;
+        const uint64_t wgs = (n + fl::SEQ_WAVES - 1) / fl::SEQ_WAVES;
+        t = T.begin(K_PILEUP);
+        hipLaunchKernelGGL(fl::blob_seq_kernel, dim3((uint32_t)std::min<uint64_t>(wgs, 8ull * (uint64_t)ctx->n_cu)), dim3(64 * fl::SEQ_WAVES), 0, ctx->stream, a);
+        HIPCHK(hipGetLastError());
+        T.end(t);
+        t = T.begin(K_D2H);
+        HIPCHK(hipMemcpyAsync(R->bases, a.bases, total, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(hipMemcpyAsync(R->quals, a.quals, total, hipMemcpyDeviceToHost, ctx->stream));
+        T.end(t);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        T.publish(ctx->timing);
+    }
     guard.r = nullptr;
     *out = R;
     return 0;

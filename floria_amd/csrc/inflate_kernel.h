@@ -1,4 +1,4 @@
-// inflate_kernel.h — BGZF members inflated on the device (floria_hip_inflate_bgzf) and the record table of the inflated bytes (floria_hip_blob_records).
+// inflate_kernel.h — BGZF members inflated on the device (floria_hip_inflate_bgzf) and the record table of the inflated bytes (floria_hip_blob_records, floria_hip_blob_records_opt).
 //
 // ONE DECODER TEXT.  inflate_core is raw DEFLATE (RFC 1951: stored, fixed and dynamic blocks, any number of blocks) as one __host__ __device__ function template
 // over three memory accessors, so the text the GPU runs also compiles for the CPU (tests/cpp/inflate_core_check.cpp runs it under the sanitizers against zlib):
@@ -369,6 +369,9 @@ __global__ __launch_bounds__(256) void inflate_crc_kernel(const uint8_t* blob, c
 
 // ---- the record table of a blob (floria_hip_blob_records) -----------------------------------------------------------------------------------------------------------
 enum : uint32_t { CHAIN_OK = 0, CHAIN_SHORT = 1 /* block_size < 32 */, CHAIN_PAST = 2 /* the record, or its block_size prefix, runs past the chain's end */ };
+// how a chain may end (floria_hip_blob_records_opt; == FLORIA_CHAIN_*) and how it did end (floria_blob_records::chain_why)
+enum : uint32_t { CHAIN_CUT_TAIL = 1, CHAIN_ONE_REF = 2 };
+enum : uint32_t { WHY_END = 0 /* reached end[c] exactly */, WHY_CUT = 1 /* a prefix or record cut by end[c] */, WHY_REF = 2 /* a record of another reference */ };
 
 __device__ __forceinline__ uint32_t blob_u16(const uint8_t* p, uint64_t o) { return (uint32_t)G(p)[o] | (uint32_t)G(p)[o + 1] << 8; }
 __device__ __forceinline__ uint32_t blob_u32(const uint8_t* p, uint64_t o) { return blob_u16(p, o) | blob_u16(p, o + 2) << 16; }
@@ -379,27 +382,36 @@ struct ChainArgs {
     uint64_t* count;                  // [n_chains + 1] COUNT: records of the chain; then their prefix sums
     uint64_t* stop;                   // [n_chains] where the chain stopped
     uint32_t* status;                 // [n_chains]
+    uint32_t* why;                    // [n_chains] WHY_*
     uint64_t* rec_off;                // FILL: [n_records] offset of every record's block_size prefix
     uint32_t n_chains;
+    uint32_t flags;                   // CHAIN_CUT_TAIL | CHAIN_ONE_REF, the same in COUNT and FILL: both passes stop at the same record
 };
 
 // One lane per chain: follow the block_size prefixes while a whole record fits before the chain's end.  Every trip advances by at least 36 bytes.
+// CHAIN_CUT_TAIL: a prefix or a record cut by the end stops the chain in front of that prefix without a status.  CHAIN_ONE_REF: the chain stops in front of the
+// first record whose refID is not its first record's; the refID is read behind the fit checks, which have shown the record's 32 fixed bytes to lie before `end`.
 template <bool FILL> __global__ __launch_bounds__(256) void blob_chain_kernel(ChainArgs g) {
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c >= g.n_chains) return;
     const uint64_t end = g.end[c] < g.blob_bytes ? g.end[c] : g.blob_bytes;
+    const bool cut_tail = g.flags & CHAIN_CUT_TAIL, one_ref = g.flags & CHAIN_ONE_REF;
     uint64_t off = g.begin[c], n = 0;
     const uint64_t slot = FILL ? g.count[c] : 0, cap = FILL ? g.count[c + 1] - slot : 0;
-    uint32_t st = CHAIN_OK;
+    uint32_t st = CHAIN_OK, why = WHY_END, ref0 = 0;
     while (off < end) {
-        if (end - off < 4) { st = CHAIN_PAST; break; }
+        if (end - off < 4) { if (cut_tail) why = WHY_CUT; else st = CHAIN_PAST; break; }
         const uint32_t bs = blob_u32(g.blob, off);
         if (bs < 32) { st = CHAIN_SHORT; break; }
-        if ((uint64_t)bs > end - off - 4) { st = CHAIN_PAST; break; }
+        if ((uint64_t)bs > end - off - 4) { if (cut_tail) why = WHY_CUT; else st = CHAIN_PAST; break; }
+        if (one_ref) {
+            const uint32_t ref = blob_u32(g.blob, off + 4);
+            if (n == 0) ref0 = ref; else if (ref != ref0) { why = WHY_REF; break; }
+        }
         if (FILL) { if (n >= cap) break; g.rec_off[slot + n] = off; }
         ++n; off += 4 + (uint64_t)bs;
     }
-    if (!FILL) { g.count[c] = n; g.stop[c] = off; g.status[c] = st; }
+    if (!FILL) { g.count[c] = n; g.stop[c] = off; g.status[c] = st; g.why[c] = why; }
 }
 
 struct RecordArgs {

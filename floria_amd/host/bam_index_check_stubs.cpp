@@ -5,6 +5,15 @@
 
 #define DEVICE_ENTRY(name) extern "C" int name(...) { fprintf(stderr, "bam_index_check: device entry point " #name " reached\n"); abort(); }
 DEVICE_ENTRY(floria_hip_assemble_contigs_opt)
+DEVICE_ENTRY(floria_hip_blob_bytes)
+DEVICE_ENTRY(floria_hip_blob_download)
+DEVICE_ENTRY(floria_hip_blob_free)
+DEVICE_ENTRY(floria_hip_blob_records_free)
+DEVICE_ENTRY(floria_hip_blob_records_opt)
+DEVICE_ENTRY(floria_hip_blob_sequences)
+DEVICE_ENTRY(floria_hip_blob_sequences_free)
+DEVICE_ENTRY(floria_hip_inflate_bgzf)
+DEVICE_ENTRY(floria_hip_pileup_records_resident_blob)
 DEVICE_ENTRY(floria_hip_contig_free)
 DEVICE_ENTRY(floria_hip_drop_monomorphic)
 DEVICE_ENTRY(floria_hip_last_timing)

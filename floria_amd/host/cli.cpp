@@ -37,6 +37,11 @@ void usage() {
           "                    round; fused: that device call also re-aligns the calls (instead of the host loop that queues windows for the device); resident: the calls\n"
           "                    never come back - fragments are planned from the records' headers and assembled, filtered (--ignore-monomorphic) and phased on the device,\n"
           "                    the writers ask it for allele tables and read trims (one device only; no --dump-frags).  Same files\n"
+          "  --inflate host|device   where the BGZF members of the BAM are inflated: host [default] = on the host threads, the inflated records uploaded for the walk; device =\n"
+          "                    the compressed members of a segment go up as they lie in the file, are inflated there (floria_hip_inflate_bgzf) and the records are read where\n"
+          "                    they are walked: the host sees a header-sized table of them (floria_hip_blob_records_opt), --output-reads' bases come back in one call per\n"
+          "                    ingest round (floria_hip_blob_sequences).  Needs --pileup resident (no other route leaves the record bytes unread on the host); the BAM header\n"
+          "                    and the -e / -l estimate are still inflated on the host.  Same files\n"
           "  --haplosets host|resident   where the haplosets live between S2 and the writers: host [default] = S2 returns the group lists and the four calls behind it\n"
           "                    (COV / ERR, HAPQ, allele tables, read trims) take them up again; resident = S2 splits and sorts on the device and keeps the haplosets there\n"
           "                    (floria_hip_reassign_batch_resident), the lists come back once for the writers and the four calls take the handle.  Any --pileup route.  Same files\n"
@@ -150,6 +155,11 @@ Cli parse_args(int argc, char** argv) {
                 throw Error(FLORIA_E_INVALID, "--pileup takes host or device (or fused: device, and the calls re-aligned there; or resident: the calls stay on the device), not '" + v + "'");
             o.pileup = v == "device" ? PileupRoute::Device : v == "fused" ? PileupRoute::Fused : v == "resident" ? PileupRoute::Resident : PileupRoute::Host;
         }
+        else if (a == "--inflate") {
+            const std::string v = val();
+            if (v != "host" && v != "device") throw Error(FLORIA_E_INVALID, "--inflate takes host or device, not '" + v + "'");
+            cli.inflate_device = v == "device";
+        }
         else if (a == "--haplosets") {
             const std::string v = val();
             if (v != "host" && v != "resident") throw Error(FLORIA_E_INVALID, "--haplosets takes host or resident, not '" + v + "'");
@@ -187,6 +197,9 @@ void validate(const Cli& cli) {
     if (o.pileup == PileupRoute::Resident && !cli.dump_frags.empty())
         throw Error(FLORIA_E_UNSUPPORTED, "--dump-frags is not available under --pileup resident: the quality bytes are folded into weights on the device and cannot be printed "
                                           "(--dump-handles and --dump-seq-pos work)");
+    if (cli.inflate_device && o.pileup != PileupRoute::Resident)
+        throw Error(FLORIA_E_UNSUPPORTED, "--inflate device needs --pileup resident: only that route leaves the record bytes unread on the host (every other route walks or "
+                                          "merges the records' CIGARs, bases and qualities there, so they would have to come back down)");
     if (!cli.dump_plan.empty() && !cli.ingest_only) throw Error(FLORIA_E_INVALID, "--dump-plan needs --ingest-only");
     if (o.bam_file.empty()) throw Error(FLORIA_E_INVALID, "Must input a BAM file.");
     if (o.vcf_file.empty() || o.reference_fasta.empty()) throw Error(FLORIA_E_INVALID, "-v and -r are required");

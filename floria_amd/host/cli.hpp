@@ -22,6 +22,7 @@ struct Cli {
     std::vector<int> devices;            // --devices: the GPUs the contigs of a batch are dealt to (empty: --device alone)
     size_t bam_window = (size_t)512 << 20;   // --bam-window-mb: inflated BAM bytes held at a time (more only when one contig alone is larger)
     bool no_index = false;               // --no-index: stream the whole BAM in file order even when an index lies beside it
+    bool inflate_device = false;         // --inflate device: the BGZF members of a segment are inflated, and their records read, on the device (--pileup resident only)
     std::string arith_opt = "auto";      // --arith auto|reference|canonical: the reference's running f64 sums (device mode arith = 1) or the exact (Q24, #eps) form; auto = reference
                                          // arithmetic exactly when epsilon is not a multiple of 2^-10 (where the two are different functions)
     bool eps_round = false;              // --epsilon-round: round an auto-estimated -e to a multiple of 2^-10 (default: used as estimated, like the reference)

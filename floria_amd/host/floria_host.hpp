@@ -281,8 +281,23 @@ struct BamRecord {
     BamSeqView seq;                    // ASCII bases through operator[]
     BamBytesView qual;
 };
+// --inflate device: what a segment owns when its records lie on the device.  The inflated members are a blob there, the records' header fields and names came back as a
+// table (floria_hip_blob_records_opt).  The views of such a segment's records hold BLOB OFFSETS in their pointers (cigar.p, seq.packed, qual.p: byte offsets from a null
+// base, as the header comment of floria_hip_blob_records derives them; never dereferenced on the host) and their qnames point into the table's names.
+struct DeviceSegment {
+    floria_hip_ctx* ctx = nullptr;
+    floria_hip_blob* blob = nullptr;
+    floria_blob_records* table = nullptr;
+    std::vector<uint64_t> rec_off, rec_end;            // per record of the segment: its block_size prefix and the byte behind it, in the blob
+    mutable uint64_t bytes_down = 0;                   // record bytes that came down for the host's use (CG-tag records, host-walk contigs)
+    DeviceSegment() = default;
+    DeviceSegment(const DeviceSegment&) = delete;
+    DeviceSegment& operator=(const DeviceSegment&) = delete;
+    ~DeviceSegment() { floria_hip_blob_records_free(table); floria_hip_blob_free(blob); }
+};
 struct BamFile {
-    std::vector<unsigned char> raw;    // the inflated stream (the records point into it: a BamFile may be moved, not copied)
+    std::vector<unsigned char> raw;    // the inflated stream (the records point into it: a BamFile may be moved, not copied); empty for a device segment
+    std::unique_ptr<DeviceSegment> dev;    // --inflate device: the segment's blob and record table (see DeviceSegment)
     std::vector<std::string> target_names;
     std::vector<uint64_t> target_len;
     std::vector<BamRecord> records;    // file order
@@ -330,6 +345,20 @@ public:
     const std::string& index_path() const;             // "" when no index is in use
     struct IndexUse { size_t selected, members_inflated, members_in_file; };
     IndexUse index_use() const;                        // (members_in_file walks the member headers that have not been walked yet)
+    // --inflate device: from here on (once, after the parameter estimate's pass and its rewind()) next() inflates nothing on the host.  It plans a run of ADJACENT
+    // members of the mapped file and the chains to walk in it, has them inflated on the context (floria_hip_inflate_bgzf uploads everything between the first and the
+    // last member, so a segment never spans a gap between selected targets) and reads the record table (floria_hip_blob_records_opt): the segment it hands out is a
+    // BamFile with `dev` and without `raw`.  With an index: one ONE_REF | CUT_TAIL chain per selected target from the index's offset, members up to the index's end
+    // offset plus look-ahead, re-planned with twice the look-ahead where a chain meets the blob's end before another target.  Without: members in file order until
+    // their ISIZEs sum to the window, one CUT_TAIL chain; the targets below the last record's are complete and the next segment begins at the member that holds the
+    // first record of the incomplete one (those members are inflated again: the blob stays one buffer).  A gzip file without BGZF members is refused.
+    void inflate_on_device(floria_hip_ctx* ctx);
+    struct DeviceUse {                                 // members and bytes are totals SENT: a segment re-planned for look-ahead and carried-over members count again
+        size_t segments = 0, members = 0, replanned = 0, carried_members = 0;
+        uint64_t compressed_bytes = 0, inflated_bytes = 0, cg_bytes_down = 0;
+        double inflate_s = 0., table_s = 0.;
+    };
+    DeviceUse device_use() const;
 private:
     struct Impl;
     std::unique_ptr<Impl> p_;
@@ -473,6 +502,7 @@ public:
     // planned[i] (may be null where !on_table(i)) for every contig of the constructor's list; fills planned[i]->handle and re-maps the Frags through the filter
     void assemble(std::vector<HeaderContig*>& planned, bool derive_set_order, bool keep_seq_pos, bool ignore_monomorphic, double epsilon);
     double assemble_s = 0., filter_s = 0.;                   // wall seconds of the assemble and the filter call
+    double sequences_s = 0.;                                 // device segment, --output-reads: wall seconds of the round's floria_hip_blob_sequences call
     double assemble_ms = 0., filter_ms = 0.;                 // their device-event totals
     uint64_t bytes_back = 0;                                 // what the host received: the summary's arrays, the filter's three words per read, its mask and map
     uint64_t removed_snps = 0, dropped_reads = 0;            // --ignore-monomorphic
@@ -483,7 +513,11 @@ private:
     const Options& o_;
     const std::string* contigs_;
     floria_record_summary* summary_ = nullptr;
+    void fetch_sequences(std::vector<HeaderContig*>& planned);   // device segment: the kept sequences of every planned fragment in one floria_hip_blob_sequences call
 };
+// --inflate device: the records of one target of a device segment as a host BamFile (the bytes of its chain in one floria_hip_blob_download, decoded as a host
+// segment's are) for a contig that keeps the host walk; counts the bytes into segment.dev->bytes_down
+BamFile host_copy_of_target(const BamFile& segment, const std::string& contig, size_t threads);
 std::pair<size_t, double> l_epsilon_auto_detect(const BamFile& bam);                   // :749-826
 // The same fed segment by segment (complete targets in header order, as BamStream::next yields them): done() once 1000 columns have been sampled,
 // which is where the reference's pileup loop breaks as well.

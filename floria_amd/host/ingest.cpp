@@ -283,6 +283,12 @@ void frag_sequences(Frag& frag, const BamRecord& rec, bool keep_sequences) {
     }
 }
 
+// the same from the two byte ranges floria_hip_blob_sequences returns for a record (bases already A / C / G / T, qualities already + 33): mate 0 or 1 of the fragment
+void frag_sequences(Frag& frag, int mate, const uint8_t* bases, const uint8_t* quals, size_t n) {
+    frag.seq_string[mate].assign((const char*)bases, n);
+    frag.qual_string[mate].assign(quals, quals + n);
+}
+
 struct Tagged { uint16_t flags; Frag frag; uint32_t rec_ix = 0; };
 
 // global alignment score of two byte strings, affine gaps: a gap of length n costs open + (n - 1) * extend
@@ -434,6 +440,31 @@ void realign(const std::string& ref_gn, Frag& frag, const BamSeqView& read_seq, 
     }
 }
 
+// the CG:B,I array among the tags raw[o, end) of a record: -> the offset of its first word and its count; false: there is none (the placeholder CIGAR stays)
+bool find_cg_tag(const unsigned char* raw, size_t o, size_t end, const std::string& what, size_t& cg_off, uint32_t& cg_cnt) {
+    Cursor d{raw, end, o, what};
+    while (d.o + 3 <= end) {
+        const unsigned char t0c = raw[d.o], t1c = raw[d.o + 1], ty = raw[d.o + 2];
+        d.o += 3;
+        size_t len = 0;
+        if (ty == 'A' || ty == 'c' || ty == 'C') len = 1;
+        else if (ty == 's' || ty == 'S') len = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') len = 4;
+        else if (ty == 'Z' || ty == 'H') { while (d.o + len < end && raw[d.o + len]) ++len; ++len; }
+        else if (ty == 'B') {
+            d.need(5);
+            const unsigned char sub = raw[d.o];
+            uint32_t cnt; memcpy(&cnt, raw + d.o + 1, 4);
+            const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            if (t0c == 'C' && t1c == 'G' && sub == 'I') { d.o += 5; d.need((size_t)4 * cnt); cg_off = d.o; cg_cnt = cnt; return true; }
+            len = 5 + es * cnt;
+        } else break;                                                    // unknown type: stop looking
+        if (d.o + len > end) break;
+        d.o += len;
+    }
+    return false;
+}
+
 // the records of bam.raw[begin, end) (whole records) -> bam.records (views into bam.raw) and bam.by_tid
 void decode_records(BamFile& bam, size_t begin, size_t end, const std::string& path, size_t threads) {
     // record boundaries first (a walk over the block_size fields), then the records are decoded independently
@@ -464,26 +495,8 @@ void decode_records(BamFile& bam, size_t begin, size_t end, const std::string& p
             // An alignment with more than 65 535 CIGAR operations keeps its real CIGAR in the CG:B,I tag and a placeholder `<l_seq>S<ref_len>N` in the
             // CIGAR field (SAM spec 4.2.2); htslib's bam_read1 puts the real one back (bam_tag2cigar), so the reference sees it.  The other tags are skipped.
             if (n_cigar == 2 && (r.cigar[0] & 15u) == 4u && (r.cigar[0] >> 4) == l_seq && (r.cigar[1] & 15u) == 3u) {
-                const size_t end = rec_off[i + 1] - 4;
-                while (d.o + 3 <= end) {
-                    const unsigned char t0c = raw[d.o], t1c = raw[d.o + 1], ty = raw[d.o + 2];
-                    d.o += 3;
-                    size_t len = 0;
-                    if (ty == 'A' || ty == 'c' || ty == 'C') len = 1;
-                    else if (ty == 's' || ty == 'S') len = 2;
-                    else if (ty == 'i' || ty == 'I' || ty == 'f') len = 4;
-                    else if (ty == 'Z' || ty == 'H') { while (d.o + len < end && raw[d.o + len]) ++len; ++len; }
-                    else if (ty == 'B') {
-                        d.need(5);
-                        const unsigned char sub = raw[d.o];
-                        uint32_t cnt; memcpy(&cnt, raw.data() + d.o + 1, 4);
-                        const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-                        if (t0c == 'C' && t1c == 'G' && sub == 'I') { d.o += 5; d.need((size_t)4 * cnt); r.cigar = BamCigarView{raw.data() + d.o, cnt}; break; }
-                        len = 5 + es * cnt;
-                    } else break;                                                    // unknown type: stop looking (the placeholder CIGAR stays)
-                    if (d.o + len > end) break;
-                    d.o += len;
-                }
+                size_t cg; uint32_t cnt;
+                if (find_cg_tag(raw.data(), d.o, rec_off[i + 1] - 4, path, cg, cnt)) r.cigar = BamCigarView{raw.data() + cg, cnt};
             }
         }
     });
@@ -808,6 +821,180 @@ struct BamStream::Impl {
             buf.swap(out);
         }
     }
+
+    // ---- --inflate device (BamStream::inflate_on_device): the same segments planned from member headers, inflated and read on the device
+    floria_hip_ctx* dctx = nullptr;
+    BamStream::DeviceUse duse;
+    size_t dev_skip = 0;                      // without an index: offset of the next segment's first record inside member `bi`
+
+    // the adjacent members bl[b0, b1) -> a blob, and the table of the chains that begin at `begin` and are open to the blob's end
+    std::unique_ptr<DeviceSegment> device_read(const std::vector<BgzfBlock>& bl, size_t b0, size_t b1, const std::vector<uint64_t>& begin, uint32_t flags) {
+        const auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        std::unique_ptr<DeviceSegment> d(new DeviceSegment);
+        d->ctx = dctx;
+        std::vector<uint64_t> off(b1 - b0);
+        std::vector<uint32_t> len(b1 - b0);
+        for (size_t b = b0; b < b1; ++b) { off[b - b0] = bl[b].in_off; len[b - b0] = (uint32_t)bl[b].in_len; }
+        double t0 = now();
+        if (const int rc = floria_hip_inflate_bgzf(dctx, map, map_len, off.data(), len.data(), (uint32_t)(b1 - b0), &d->blob))
+            throw Error(rc, path + ": floria_hip_inflate_bgzf: " + floria_hip_last_error());
+        duse.inflate_s += now() - t0;
+        duse.members += b1 - b0; members_inflated += b1 - b0;
+        duse.compressed_bytes += bl[b1 - 1].in_off + bl[b1 - 1].in_len - bl[b0].in_off;
+        const uint64_t blob_bytes = floria_hip_blob_bytes(d->blob);
+        duse.inflated_bytes += blob_bytes;
+        for (const uint64_t b : begin) if (b > blob_bytes) throw Error(FLORIA_E_INVALID, path + ": a chain of records begins beyond the inflated members");
+        const std::vector<uint64_t> end(begin.size(), blob_bytes);
+        t0 = now();
+        if (const int rc = floria_hip_blob_records_opt(dctx, d->blob, begin.data(), end.data(), (uint32_t)begin.size(), flags, &d->table))
+            throw Error(rc, path + ": floria_hip_blob_records_opt: " + floria_hip_last_error());
+        duse.table_s += now() - t0;
+        return d;
+    }
+    // records [lo, hi) of the table -> seg.records (places as blob offsets, names as views into the table) and seg.by_tid
+    void device_records(BamFile& seg, uint64_t lo, uint64_t hi) {
+        DeviceSegment& d = *seg.dev;
+        const floria_blob_records& T = *d.table;
+        const size_t n = (size_t)(hi - lo);
+        seg.records.resize(n); d.rec_off.resize(n); d.rec_end.resize(n);
+        const auto place = [](uint64_t o) { return (const unsigned char*)(uintptr_t)o; };
+        std::vector<unsigned char> rec;
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t j = lo + i, o = T.offset[j];
+            const size_t l_name = T.l_read_name[j], n_cigar = T.n_cigar_op[j], l_seq = T.l_seq[j], whole = 4 + (size_t)T.block_size[j];
+            const uint64_t cig = o + 36 + l_name, sq = cig + 4 * n_cigar, ql = sq + (l_seq + 1) / 2;
+            if (36 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq > whole) throw Error(FLORIA_E_INVALID, path + ": malformed BAM record");
+            BamRecord& r = seg.records[i];
+            r.tid = T.ref_id[j]; r.pos = T.pos[j]; r.mapq = T.mapq[j]; r.flags = T.flag[j];
+            r.qname = std::string_view((const char*)T.names + T.name_off[j], l_name ? l_name - 1 : 0);
+            r.cigar = BamCigarView{place(cig), n_cigar}; r.seq = BamSeqView{place(sq), l_seq}; r.qual = BamBytesView{place(ql), l_seq};
+            d.rec_off[i] = o; d.rec_end[i] = o + whole;
+            // the kSmN placeholder of a CG-tag record (decode_records): its bytes come down, the tag scan finds the real CIGAR, whose place in the blob goes into the view
+            if (n_cigar == 2 && T.cigar0[j] == ((uint32_t)l_seq << 4 | 4u)) {
+                rec.resize(whole);
+                if (const int rc = floria_hip_blob_download(d.blob, o, rec.data(), whole)) throw Error(rc, path + ": floria_hip_blob_download: " + floria_hip_last_error());
+                duse.cg_bytes_down += whole;
+                uint32_t c1; memcpy(&c1, rec.data() + (size_t)(cig - o) + 4, 4);
+                size_t cg; uint32_t cnt;
+                if ((c1 & 15u) == 3u && find_cg_tag(rec.data(), (size_t)(ql - o) + l_seq, whole, path, cg, cnt)) r.cigar = BamCigarView{place(o + cg), cnt};
+            }
+            if (r.tid >= 0 && (size_t)r.tid < seg.by_tid.size()) seg.by_tid[(size_t)r.tid].push_back((uint32_t)i);
+        }
+    }
+    void device_segment(BamFile& seg, std::unique_ptr<DeviceSegment> d, uint64_t rec_lo, uint64_t rec_hi, int32_t upto) {
+        seg = BamFile();
+        seg.target_names = names; seg.target_len = lens;
+        seg.by_tid.resize(names.size());
+        seg.dev = std::move(d);
+        if (seg.dev->table) device_records(seg, rec_lo, rec_hi);
+        seg.tid_begin = done_upto; seg.tid_end = upto;
+        done_upto = upto;
+        ++duse.segments;
+    }
+    // with an index: the selected targets in header order, as many as the window takes and as lie side by side in the file
+    bool next_device_indexed(BamFile& seg, size_t min_bytes) {
+        if (sel_done) return false;
+        const int32_t n_targets = (int32_t)names.size();
+        int32_t upto = done_upto;
+        bool any = false;
+        std::vector<Stretch> st;
+        size_t planned = 0, run_end = 0;                                           // run_end: file offset behind the last member the index's ends ask for
+        while (sel_pos < sel.size() && (!any || planned < min_bytes)) {
+            const int32_t t = sel[sel_pos];
+            if (bai.targets[(size_t)t].has_records) {
+                Stretch s = plan_stretch(t);
+                const size_t c0 = s.bl[0].in_off;
+                // everything between the first and the last member goes up: the segment ends where the next target begins neither in the run nor in the member behind it
+                if (!st.empty() && (c0 > run_end || c0 < st[0].bl[0].in_off)) break;
+                run_end = std::max(run_end, s.at); planned += s.rlen;
+                st.push_back(std::move(s));
+            }
+            ++sel_pos; upto = t + 1; any = true;
+        }
+        if (sel_pos >= sel.size()) { upto = n_targets; sel_done = true; }
+        std::unique_ptr<DeviceSegment> d(new DeviceSegment);
+        d->ctx = dctx;
+        for (size_t look = 1; !st.empty(); look *= 2) {
+            Stretch run;
+            run.tid = st[0].tid; run.at = st[0].bl[0].in_off;
+            while (run.at < run_end && stretch_more(run)) {}
+            for (size_t k = 0; k < look && stretch_more(run); ++k) {}
+            const bool at_eof = run.at >= map_len;
+            std::vector<uint64_t> begin;
+            for (const Stretch& s : st) {
+                const auto m = std::lower_bound(run.bl.begin(), run.bl.end(), s.bl[0].in_off, [](const BgzfBlock& b, size_t o) { return b.in_off < o; });
+                if (m == run.bl.end() || m->in_off != s.bl[0].in_off) throw bad_index(s.tid, "the offset of the first record does not land on the start of a BGZF member");
+                begin.push_back(m->out_off + s.u0);
+            }
+            d.reset();                                                                // (a re-plan: the blob that fell short goes before the larger one is made)
+            d = device_read(run.bl, 0, run.bl.size(), begin, FLORIA_CHAIN_ONE_REF | FLORIA_CHAIN_CUT_TAIL);
+            const floria_blob_records& T = *d->table;
+            bool short_of_end = false;
+            for (size_t c = 0; c < st.size(); ++c) {
+                const bool has = T.chain_rec_off[c + 1] > T.chain_rec_off[c];
+                if (has && T.ref_id[T.chain_rec_off[c]] != st[c].tid) throw bad_index(st[c].tid, "the record at the offset of the first record belongs to another target");
+                if (T.chain_why[c] == 2) { if (!has) throw bad_index(st[c].tid, "the record at the offset of the first record belongs to another target"); continue; }
+                if (!at_eof) { short_of_end = true; continue; }                       // the blob ended before another target did: look further ahead
+                if (T.chain_stop[c] != floria_hip_blob_bytes(d->blob)) throw Error(FLORIA_E_INVALID, path + " is truncated");
+                if (!has) throw bad_index(st[c].tid, "there is no record at the offset of the first record");
+            }
+            if (!short_of_end) break;
+            ++duse.replanned;
+        }
+        const uint64_t n_records = d->table ? d->table->n_records : 0;
+        device_segment(seg, std::move(d), 0, n_records, upto);
+        return true;
+    }
+    // without an index (or with --no-index): members in file order until their ISIZEs sum to the window, one chain
+    bool next_device_stream(BamFile& seg, size_t min_bytes) {
+        const int32_t n_targets = (int32_t)names.size();
+        if (eof && done_upto >= n_targets) return false;
+        size_t want = std::max<size_t>(min_bytes, 1 << 16);
+        for (;;) {
+            size_t b1 = bi;
+            uint64_t sum = 0;
+            while (have_block(b1) && sum < dev_skip + want) sum += blocks[b1++].out_len;
+            const bool at_end = !have_block(b1);
+            std::unique_ptr<DeviceSegment> d(new DeviceSegment);
+            d->ctx = dctx;
+            if (b1 == bi) {                                                            // no member is left: the targets not handed out yet have no record
+                if (dev_skip) throw Error(FLORIA_E_INVALID, path + " is truncated");
+                eof = true;
+                device_segment(seg, std::move(d), 0, 0, n_targets);
+                return true;
+            }
+            d = device_read(blocks, bi, b1, std::vector<uint64_t>{dev_skip}, FLORIA_CHAIN_CUT_TAIL);
+            const floria_blob_records& T = *d->table;
+            if (at_end && T.chain_why[0] != 0) throw Error(FLORIA_E_INVALID, path + " is truncated");
+            // [0, cut) = the records of targets that are certainly complete (the walk of next() on the table's refIDs)
+            uint64_t first_of_last = 0;
+            int32_t cur_tid = INT32_MIN, prev = last_tid_seen;
+            bool saw_unmapped = false;
+            for (uint64_t i = 0; i < T.n_records; ++i) {
+                const int32_t tid = T.ref_id[i];
+                if (tid < 0) { if (!saw_unmapped) { saw_unmapped = true; first_of_last = i; cur_tid = n_targets; } }
+                else if (saw_unmapped || tid < prev) throw Error(FLORIA_E_INVALID, path + " is not sorted by reference sequence (floria needs a coordinate-sorted, indexed BAM; so does this reader)");
+                else if (tid != cur_tid) { cur_tid = tid; first_of_last = i; prev = tid; }
+            }
+            const bool closing = at_end || saw_unmapped;
+            uint64_t cut; int32_t complete_upto;
+            if (closing) { cut = saw_unmapped ? first_of_last : T.n_records; complete_upto = n_targets; }
+            else { cut = first_of_last; complete_upto = cur_tid == INT32_MIN ? done_upto : std::min(cur_tid, n_targets); }
+            if (!closing && (cut == 0 || complete_upto <= done_upto)) { want = std::max<size_t>(want * 2, (size_t)sum * 2); continue; }      // one target fills the window: read on
+            if (closing) eof = true;
+            else {
+                // the next segment begins at the member that holds the first record of the incomplete target; the members from there on are inflated again
+                const uint64_t o = T.offset[cut], base = blocks[bi].out_off;
+                size_t m = (size_t)(std::upper_bound(blocks.begin() + (ptrdiff_t)bi, blocks.begin() + (ptrdiff_t)b1, base + o,
+                                                     [](uint64_t v, const BgzfBlock& b) { return v < b.out_off; }) - blocks.begin()) - 1;
+                duse.carried_members += b1 - m;
+                dev_skip = (size_t)(base + o - blocks[m].out_off); bi = m;
+            }
+            last_tid_seen = std::max(last_tid_seen, std::min(prev, n_targets));
+            device_segment(seg, std::move(d), 0, cut, complete_upto);
+            return true;
+        }
+    }
 };
 
 BamStream::BamStream(const std::string& path, size_t threads, bool use_index) : p_(new Impl) {
@@ -905,6 +1092,16 @@ BamStream::IndexUse BamStream::index_use() const {
     try { I.have_block(SIZE_MAX); } catch (const Error&) {}            // (a member the reading never reached: counted up to it)
     return {I.sel.size(), I.members_inflated, I.blocks.size()};
 }
+void BamStream::inflate_on_device(floria_hip_ctx* ctx) {
+    Impl& I = *p_;
+    if (!I.bgzf)
+        throw Error(FLORIA_E_UNSUPPORTED, I.path + " is a gzip file without BGZF members: --inflate device inflates member by member and cannot read it; run with --inflate host");
+    I.dctx = ctx;
+    // the pass begins at the first record again, with nothing inflated on the host: the member the header ends in goes to the device with the others
+    I.carry.clear();
+    I.bi = I.first_block; I.dev_skip = I.first_skip;
+}
+BamStream::DeviceUse BamStream::device_use() const { return p_->duse; }
 void BamStream::rewind() {
     Impl& I = *p_;
     if (!I.bgzf) { if (I.whole_given) { I.whole = read_bam(I.path, I.threads); I.whole.tid_begin = 0; I.whole.tid_end = (int32_t)I.names.size(); } I.whole_given = false; return; }
@@ -928,6 +1125,7 @@ bool BamStream::next(BamFile& seg, size_t min_bytes) {
         I.peak = std::max(I.peak, seg.raw.size());
         return true;
     }
+    if (I.dctx) return I.selecting ? I.next_device_indexed(seg, min_bytes) : I.next_device_stream(seg, min_bytes);
     std::vector<unsigned char> buf;
     if (I.selecting) {
         // the selected targets in header order, each from its indexed offset, as many as the window takes; the targets between them have no records here
@@ -1313,15 +1511,20 @@ struct RecordSelection {
         const size_t n = pos.size();
         if (n == 0) return;
         // the stretch of the inflated buffer that holds these records' CIGARs, bases and qualities (a round's contigs are neighbours in a sorted BAM)
-        const unsigned char *lo = cig_p[0], *hi = cig_p[0];
-        for (size_t i = 0; i < n; ++i) {
-            lo = std::min({lo, cig_p[i], seq_p[i], qual_p[i]});
-            hi = std::max({hi, cig_p[i] + 4 * (size_t)n_cigar[i], seq_p[i] + ((size_t)l_seq[i] + 1) / 2, qual_p[i] + l_seq[i]});
+        // (a device segment: the views hold blob offsets already, the blob is the segment's handle and nothing travels)
+        uintptr_t lo = 0, hi = 0;
+        if (bam.dev) hi = (uintptr_t)floria_hip_blob_bytes(bam.dev->blob);
+        else {
+            lo = hi = (uintptr_t)cig_p[0];
+            for (size_t i = 0; i < n; ++i) {
+                lo = std::min({lo, (uintptr_t)cig_p[i], (uintptr_t)seq_p[i], (uintptr_t)qual_p[i]});
+                hi = std::max({hi, (uintptr_t)cig_p[i] + 4 * (size_t)n_cigar[i], (uintptr_t)seq_p[i] + ((size_t)l_seq[i] + 1) / 2, (uintptr_t)qual_p[i] + l_seq[i]});
+            }
         }
         cigar_off.resize(n); seq_off.resize(n); qual_off.resize(n);
-        for (size_t i = 0; i < n; ++i) { cigar_off[i] = (uint64_t)(cig_p[i] - lo); seq_off[i] = (uint64_t)(seq_p[i] - lo); qual_off[i] = (uint64_t)(qual_p[i] - lo); }
+        for (size_t i = 0; i < n; ++i) { cigar_off[i] = (uint64_t)((uintptr_t)cig_p[i] - lo); seq_off[i] = (uint64_t)((uintptr_t)seq_p[i] - lo); qual_off[i] = (uint64_t)((uintptr_t)qual_p[i] - lo); }
         blob_bytes = (size_t)(hi - lo);
-        A.blob = lo; A.blob_bytes = blob_bytes; A.n_records = (uint32_t)n; A.pos = pos.data(); A.flags = flags.data(); A.contig = contig.data();
+        A.blob = bam.dev ? nullptr : (const uint8_t*)lo; A.blob_bytes = blob_bytes; A.n_records = (uint32_t)n; A.pos = pos.data(); A.flags = flags.data(); A.contig = contig.data();
         A.cigar_off = cigar_off.data(); A.n_cigar = n_cigar.data(); A.seq_off = seq_off.data(); A.l_seq = l_seq.data(); A.qual_off = qual_off.data();
         S.n_contigs = (uint32_t)snp_off.size() - 1; S.snp_off = snp_off.data(); S.snp_pos = snp_pos.data(); S.alleles = alleles.data(); S.n_alleles = n_alleles.data();
         F.n_contigs = S.n_contigs; F.seq_off = ref_off.data(); F.seq = ref_bytes.data();
@@ -1482,7 +1685,10 @@ ResidentPileup::ResidentPileup(Session& session, const BamFile& bam, const VcfPr
                                const std::map<std::string, std::string>* ref_seqs)
     : s_(session), bam_(bam), vp_(vp), o_(o), contigs_(contigs) {
     walk(session, bam, vp, o, contigs, n_contigs, ref_seqs, [&](const RecordSelection& sel) {
-        if (const int rc = floria_hip_pileup_records_resident(session.ctx(), &sel.A, &sel.S, ref_seqs ? &sel.F : nullptr, o.realign_walk ? &o.walk : nullptr, &summary_))
+        if (bam.dev) {                                                         // the records lie in the segment's blob: nothing is uploaded
+            if (const int rc = floria_hip_pileup_records_resident_blob(session.ctx(), bam.dev->blob, &sel.A, &sel.S, ref_seqs ? &sel.F : nullptr, o.realign_walk ? &o.walk : nullptr, &summary_))
+                throw Error(rc, std::string("floria_hip_pileup_records_resident_blob: ") + floria_hip_last_error());
+        } else if (const int rc = floria_hip_pileup_records_resident(session.ctx(), &sel.A, &sel.S, ref_seqs ? &sel.F : nullptr, o.realign_walk ? &o.walk : nullptr, &summary_))
             throw Error(rc, std::string("floria_hip_pileup_records_resident: ") + floria_hip_last_error());
         counts = summary_->counts;
         bytes_back += (uint64_t)sel.n() * 24 + 8;                              // cell_off, first_snp, last_snp, ref_end
@@ -1519,7 +1725,7 @@ HeaderContig ResidentPileup::plan(size_t ci) const {
         const BamRecord& rec = bam_.records[r.rec];
         Frag f = frag_without_calls(rec, r.counter_id);
         f.last_pos_base = (GnPosition)summary_->ref_end[slot_[r.rec] - 1];
-        frag_sequences(f, rec, keep_sequences);
+        frag_sequences(f, rec, keep_sequences && !bam_.dev);                   // (a device segment's bases come in one call for the round: fetch_sequences)
         return f;
     };
     const auto merged = [&](const PlannedFrag& pf, bool with_cells) {
@@ -1547,6 +1753,7 @@ HeaderContig ResidentPileup::plan(size_t ci) const {
 
 void ResidentPileup::assemble(std::vector<HeaderContig*>& planned, bool derive_set_order, bool keep_seq_pos, bool ignore_monomorphic, double epsilon) {
     if (!summary_) return;                                                                 // nothing was sent: no contig of the round has a fragment
+    fetch_sequences(planned);                                                              // (before the filter below re-orders the Frags)
     const size_t nt = snp_count_.size();
     std::vector<HeaderContig*> by_table(nt, nullptr);
     for (size_t ci = 0; ci < planned.size(); ++ci) if (table_of_[ci] >= 0) by_table[(size_t)table_of_[ci]] = planned[ci];
@@ -1608,6 +1815,56 @@ void ResidentPileup::assemble(std::vector<HeaderContig*>& planned, bool derive_s
         if (floria_hip_last_timing(s_.ctx(), &tm) == 0) filter_ms += tm.total_ms;
     }
     for (size_t t = 0; t < nt; ++t) if (by_table[t]) by_table[t]->handle = std::move(handles[t]);
+}
+
+// --output-reads on a device segment: the sequences plan() keeps on a host segment — the base of every fragment and its second mate — in ONE call for the round
+void ResidentPileup::fetch_sequences(std::vector<HeaderContig*>& planned) {
+    if (!bam_.dev || !o_.output_reads) return;
+    struct Dst { Frag* f; int mate; };
+    std::vector<Dst> dst;
+    std::vector<uint64_t> seq_off, qual_off;
+    std::vector<uint32_t> l_seq;
+    const auto want = [&](Frag& f, const PlannedFrag& pf) {
+        for (size_t k = 0; k < pf.parts.size(); ++k) {
+            if (k != 0 && !pf.mate[k]) continue;
+            const BamRecord& rec = bam_.records[pf.parts[k].rec];
+            dst.push_back({&f, k == 0 ? 0 : 1});
+            seq_off.push_back((uint64_t)(uintptr_t)rec.seq.packed); qual_off.push_back((uint64_t)(uintptr_t)rec.qual.p); l_seq.push_back((uint32_t)rec.seq.n);
+        }
+    };
+    for (HeaderContig* hc : planned) {
+        if (!hc) continue;
+        for (size_t k = 0; k < hc->all_frags.size(); ++k) want(hc->all_frags[k], hc->plan.frags[k]);
+        for (size_t k = 0; k < hc->frags_without_snps.size(); ++k) want(hc->frags_without_snps[k], hc->plan.snpless[k]);
+    }
+    if (dst.empty()) return;
+    const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    floria_blob_sequences* r = nullptr;
+    if (const int rc = floria_hip_blob_sequences(s_.ctx(), bam_.dev->blob, seq_off.data(), l_seq.data(), qual_off.data(), dst.size(), &r))
+        throw Error(rc, std::string("floria_hip_blob_sequences: ") + floria_hip_last_error());
+    for (size_t i = 0; i < dst.size(); ++i) frag_sequences(*dst[i].f, dst[i].mate, r->bases + r->base_off[i], r->quals + r->base_off[i], (size_t)(r->base_off[i + 1] - r->base_off[i]));
+    bytes_back += 2 * r->base_off[dst.size()] + 8 * (dst.size() + 1);
+    floria_hip_blob_sequences_free(r);
+    sequences_s += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
+}
+
+BamFile host_copy_of_target(const BamFile& seg, const std::string& contig, size_t threads) {
+    BamFile out;
+    out.target_names = seg.target_names; out.target_len = seg.target_len;
+    out.by_tid.resize(seg.target_names.size());
+    out.tid_begin = seg.tid_begin; out.tid_end = seg.tid_end;
+    const auto tid_it = std::find(seg.target_names.begin(), seg.target_names.end(), contig);
+    if (!seg.dev || tid_it == seg.target_names.end()) return out;
+    const std::vector<uint32_t>& recs = seg.by_tid[(size_t)(tid_it - seg.target_names.begin())];
+    if (recs.empty()) return out;
+    // (a target's records are neighbours in the blob: one chain, or one stretch of the segment's only chain)
+    const DeviceSegment& d = *seg.dev;
+    const uint64_t lo = d.rec_off[recs.front()], hi = d.rec_end[recs.back()];
+    out.raw.resize((size_t)(hi - lo));
+    if (const int rc = floria_hip_blob_download(d.blob, lo, out.raw.data(), hi - lo)) throw Error(rc, std::string("floria_hip_blob_download: ") + floria_hip_last_error());
+    d.bytes_down += hi - lo;
+    decode_records(out, 0, out.raw.size(), "the records of contig " + contig, threads);
+    return out;
 }
 
 std::pair<std::vector<Frag>, std::vector<Frag>> get_frags_from_bamvcf_rewrite(const BamFile& bam, const VcfProfile& vp, const Options& o, const std::string& contig,

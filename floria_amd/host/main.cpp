@@ -29,6 +29,11 @@
 // keeps the haplosets there as a handle; the lists come back once (floria_hip_haplosets_download) for the writers and the four calls take the handle (the allele tables and
 // trims of a batch that mixes contigs with and without a handle of their own still go by lists).  Same files.
 // For tests: --dump-plan FILE (with --ingest-only, any route: the fragment plan per contig), --dump-handles FILE (any route: the resident arrays of every contig of every batch).
+// --inflate host | device (with --pileup resident): where the BGZF members are inflated.  host [default]: on the host threads, the inflated records uploaded for the walk.
+// device: BamStream plans runs of adjacent members from their headers (inflate_on_device), floria_hip_inflate_bgzf inflates them into a blob, floria_hip_blob_records_opt
+// returns the header-sized record table, the walk reads the blob (floria_hip_pileup_records_resident_blob); a CG-tag record's and a host-walk contig's bytes come down by
+// floria_hip_blob_download, --output-reads' sequences by one floria_hip_blob_sequences call per ingest round.  The header and the -e / -l estimate stay on the host.  The next
+// segment's inflate does NOT overlap the current batch's phasing (not built).  The log gains one line.  Same files.
 // --no-index: a .bai beside the BAM (X.bam.bai, then X.bai) is used when present - the contigs that -G and --snp-count-filter leave are read through it, each from its
 // indexed offset, and the log gains one line (contigs selected, BGZF members inflated, members in the file); --no-index streams the whole file in order as without one.  Same files.
 // --realign exact | block:STEP,RULE,TIE: how the windows around SNP calls are scored.  exact [default]: the exact affine-gap DP; block:STEP,RULE,TIE (STEP 1 | 2 | 4 | 8,
@@ -125,6 +130,8 @@ struct RunStats {
     std::atomic<uint64_t> n_haplosets_by_handle{0};                          // --haplosets resident
     std::atomic<uint64_t> n_paths_joined{0};                                 // --paths resident
     uint64_t resident_bytes_back = 0, resident_removed_snps = 0, resident_dropped_reads = 0;
+    uint64_t inflate_host_walk_bytes = 0;                                    // --inflate device: record bytes that came down for contigs that keep the host walk
+    double t_blob_sequences = 0.;                                            // ... and the seconds of the rounds' floria_hip_blob_sequences calls
     std::atomic<size_t> lp_contigs{0}, lp_not_unique{0}, lp_edges{0}, lp_movable{0};
 
     // a round's device walk, whichever route made it; says once which contig keeps the host walk
@@ -146,6 +153,7 @@ struct RunStats {
         t_resident_assemble += r.assemble_s; t_resident_filter += r.filter_s;
         t_resident_assemble_ev += r.assemble_ms * 1e-3; t_resident_filter_ev += r.filter_ms * 1e-3;
         resident_bytes_back += r.bytes_back; resident_removed_snps += r.removed_snps; resident_dropped_reads += r.dropped_reads;
+        t_blob_sequences += r.sequences_s;
     }
     // a batch under the reference arithmetic: the fragments whose set order is replayed on the host
     void add_set_orders(const std::vector<ContigWork>& work) {
@@ -180,6 +188,14 @@ struct RunStats {
             if (reference_arith)
                 fprintf(stderr, "Arithmetic: the set orders of %zu fragments merged from several alignments were derived on the device (floria_hip_assemble_contigs_opt), every resident contig "
                                 "phased in the reference's running sums\n", n_resident_merged);
+        }
+        if (cli.inflate_device) {
+            const BamStream::DeviceUse u = stream.device_use();
+            fprintf(stderr, "Inflate on the device: %zu segments, %zu BGZF members sent (%llu compressed bytes up, %llu inflated bytes on the device), %zu segments re-planned for look-ahead, "
+                            "%zu members re-inflated as carry-over, %llu bytes down for host use (%llu for host-walk contigs, %llu for CG records); inflate %.3fs, record table %.3fs, "
+                            "sequences %.3fs\n", u.segments, u.members, (unsigned long long)u.compressed_bytes, (unsigned long long)u.inflated_bytes, u.replanned, u.carried_members,
+                    (unsigned long long)(inflate_host_walk_bytes + u.cg_bytes_down), (unsigned long long)inflate_host_walk_bytes, (unsigned long long)u.cg_bytes_down, u.inflate_s, u.table_s,
+                    t_blob_sequences);
         }
         if (o.haplosets_resident)
             fprintf(stderr, "Haplosets: %llu split, sorted and kept on the device behind S2 (floria_hip_reassign_batch_resident); one download for the writers, COV / ERR, HAPQ, "
@@ -346,16 +362,26 @@ std::vector<ContigWork> ingest_round(Run& run, RunStats& stats, const BamFile& b
         stats.add_walk(resident ? static_cast<const RoundWalk&>(*resident) : *device_cells, now_s() - tw, o.pileup);
     }
     const auto is_resident = [&](size_t i) { return resident && resident->on_table(i); };
+    // a device segment (--inflate device): the records of a contig that keeps the host walk come down, one download per contig, and are decoded as a host segment's
+    std::vector<std::unique_ptr<BamFile>> host_copy(take);
+    if (bam.dev)
+        for (size_t i = 0; i < take; ++i)
+            if (!is_resident(i)) {
+                const uint64_t before = bam.dev->bytes_down;
+                host_copy[i].reset(new BamFile(host_copy_of_target(bam, names[i], run.n_threads)));
+                stats.inflate_host_walk_bytes += bam.dev->bytes_down - before;
+            }
+    const auto records_of = [&](size_t i) -> const BamFile& { return host_copy[i] ? *host_copy[i] : bam; };
     parallel_for(take, run.n_threads, [&](size_t i) {
         const std::string& contig = names[i];
         if (is_resident(i)) { planned[i] = resident->plan(i); return; }
         const auto fa = run.fasta.find(contig);
-        ing[i].reset(new ContigIngest(bam, run.vp, o, contig, (fa != run.fasta.end() && !cli.no_realign) ? &fa->second : nullptr, on_device ? &queues[i] : nullptr, device_cells.get()));
+        ing[i].reset(new ContigIngest(records_of(i), run.vp, o, contig, (fa != run.fasta.end() && !cli.no_realign) ? &fa->second : nullptr, on_device ? &queues[i] : nullptr, device_cells.get()));
     });
     device_cells.reset();
     std::vector<std::string> plan_texts(run.dump_pl.is_open() ? take : 0);
     if (run.dump_pl.is_open())
-        parallel_for(take, run.n_threads, [&](size_t i) { plan_texts[i] = plan_text(names[i], is_resident(i) ? planned[i].plan : ing[i]->plan(), bam); });
+        parallel_for(take, run.n_threads, [&](size_t i) { plan_texts[i] = plan_text(names[i], is_resident(i) ? planned[i].plan : ing[i]->plan(), records_of(i)); });
     for (const std::string& t : plan_texts) run.dump_pl << t;
     if (resident) {
         // combine_frags on the device: one assemble call for the round (and one filter call under --ignore-monomorphic), before the next round's walk
@@ -593,6 +619,7 @@ int main(int argc, char** argv) {
             for (size_t tid = 0; tid < contigs.size(); ++tid) if (run.listed(contigs[tid]) && run.enough_snps(contigs[tid])) tids.push_back((int32_t)tid);
             stream.select(tids);
         }
+        if (cli.inflate_device) stream.inflate_on_device(run.walker().ctx());       // from here on the host inflates nothing: segments are planned from member headers
         BamFile bam;                                  // the current segment: every record of the contigs [tid_begin, tid_end)
         for (;;) {
             { const double ts = now_s(); const bool more = stream.next(bam, cli.bam_window); stats.t_stream += now_s() - ts; if (!more) break; }

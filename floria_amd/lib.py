@@ -35,7 +35,7 @@ SYMBOLS = [
     "floria_hip_reassign_batch_resident", "floria_hip_haplosets_free", "floria_hip_haplosets_download", "floria_hip_haploset_stats_resident", "floria_hip_hapq_batch_resident",
     "floria_hip_haploset_alleles_resident", "floria_hip_read_spans_resident", "floria_hip_join_paths", "floria_hip_reassign_haplosets_resident",
     "floria_hip_inflate_bgzf", "floria_hip_blob_bytes", "floria_hip_blob_download", "floria_hip_blob_free", "floria_hip_blob_records", "floria_hip_blob_records_free",
-    "floria_hip_pileup_records_resident_blob",
+    "floria_hip_pileup_records_resident_blob", "floria_hip_blob_records_opt", "floria_hip_blob_sequences", "floria_hip_blob_sequences_free",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -117,6 +117,10 @@ def load():
         L.floria_hip_blob_free.restype = None
         L.floria_hip_blob_free.argtypes = [C.c_void_p]
         L.floria_hip_blob_records.argtypes = [C.c_void_p, C.c_void_p, capi.u64p, capi.u64p, C.c_uint32, C.POINTER(C.POINTER(capi.CBlobRecords))]
+        L.floria_hip_blob_records_opt.argtypes = [C.c_void_p, C.c_void_p, capi.u64p, capi.u64p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(capi.CBlobRecords))]
+        L.floria_hip_blob_sequences.argtypes = [C.c_void_p, C.c_void_p, capi.u64p, capi.u32p, capi.u64p, C.c_uint64, C.POINTER(C.POINTER(capi.CBlobSequences))]
+        L.floria_hip_blob_sequences_free.restype = None
+        L.floria_hip_blob_sequences_free.argtypes = [C.POINTER(capi.CBlobSequences)]
         L.floria_hip_blob_records_free.restype = None
         L.floria_hip_blob_records_free.argtypes = [C.POINTER(capi.CBlobRecords)]
         L.floria_hip_pileup_records_resident_blob.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(capi.CRefSeqs),
@@ -618,23 +622,46 @@ class FloriaHip:
         _check(load().floria_hip_inflate_bgzf(self._h, fb.ctypes.data_as(C.c_void_p), C.c_uint64(fb.size), capi.ptr(mo, C.c_uint64), capi.ptr(mb, C.c_uint32), C.c_uint32(len(mo)), C.byref(h)))
         return Blob(self, h)
 
-    def blob_records(self, blob, begin, end):
+    def blob_records(self, blob, begin, end, flags=0):
         """floria_hip_blob_records: the record table of a Blob of BAM alignment records, chain c following the block_size prefixes from begin[c] while a whole
         record fits before end[c] -> dict of numpy arrays (chain_rec_off uint64 [n_chains + 1], chain_stop uint64 [n_chains]; per record offset uint64, block_size,
-        ref_id, pos, l_seq, cigar0, flag, n_cigar_op, mapq, l_read_name; name_off uint64 [n + 1] and names uint8, the names as stored, NUL included)."""
+        ref_id, pos, l_seq, cigar0, flag, n_cigar_op, mapq, l_read_name; name_off uint64 [n + 1] and names uint8, the names as stored, NUL included).
+        Always through floria_hip_blob_records_opt (flags = 0 is floria_hip_blob_records; else capi.FLORIA_CHAIN_CUT_TAIL | FLORIA_CHAIN_ONE_REF); chain_why uint32
+        [n_chains] (0 end, 1 cut tail, 2 another reference) is in the dict."""
         b = np.ascontiguousarray(np.atleast_1d(begin), np.uint64); e = np.ascontiguousarray(np.atleast_1d(end), np.uint64)
         if len(b) != len(e):
             raise FloriaHipError(capi.FLORIA_E_INVALID, "blob_records: one end per begin")
         out = C.POINTER(capi.CBlobRecords)()
-        _check(load().floria_hip_blob_records(self._h, blob._h, capi.ptr(b, C.c_uint64), capi.ptr(e, C.c_uint64), C.c_uint32(len(b)), C.byref(out)))
+        _check(load().floria_hip_blob_records_opt(self._h, blob._h, capi.ptr(b, C.c_uint64), capi.ptr(e, C.c_uint64), C.c_uint32(len(b)), C.c_uint32(int(flags)), C.byref(out)))
+        return self._blob_records_result(out)
+
+    @staticmethod
+    def _blob_records_result(out):
+        """the dict of blob_records from the library's floria_blob_records, which it frees"""
         r = out.contents
         n, nch = int(r.n_records), int(r.n_chains)
-        res = dict(chain_rec_off=capi.np_from(r.chain_rec_off, nch + 1, np.uint64), chain_stop=capi.np_from(r.chain_stop, nch, np.uint64), name_off=capi.np_from(r.name_off, n + 1, np.uint64))
+        res = dict(chain_rec_off=capi.np_from(r.chain_rec_off, nch + 1, np.uint64), chain_stop=capi.np_from(r.chain_stop, nch, np.uint64), name_off=capi.np_from(r.name_off, n + 1, np.uint64),
+                   chain_why=capi.np_from(r.chain_why, nch, np.uint32))
         for f, dt in (("offset", np.uint64), ("block_size", np.uint32), ("ref_id", np.int32), ("pos", np.int32), ("l_seq", np.uint32), ("cigar0", np.uint32), ("flag", np.uint16),
                       ("n_cigar_op", np.uint16), ("mapq", np.uint8), ("l_read_name", np.uint8)):
             res[f] = capi.np_from(getattr(r, f), n, dt)
         res["names"] = capi.np_from(r.names, int(res["name_off"][n]), np.uint8)
         load().floria_hip_blob_records_free(out)
+        return res
+
+    def blob_sequences(self, blob, seq_off, l_seq, qual_off):
+        """floria_hip_blob_sequences: the bases ('A' 'C' 'G' 'T' for the codes 1 2 4 8, 'A' otherwise) and qualities (q > 222 ? 255 : q + 33) of n records of a
+        Blob, record i with its packed bases at seq_off[i] and its l_seq[i] quality bytes at qual_off[i] -> (base_off uint64 [n + 1], bases uint8, quals uint8)."""
+        so = np.ascontiguousarray(np.atleast_1d(seq_off), np.uint64); ls = np.ascontiguousarray(np.atleast_1d(l_seq), np.uint32)
+        qo = np.ascontiguousarray(np.atleast_1d(qual_off), np.uint64)
+        if not len(so) == len(ls) == len(qo):
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "blob_sequences: one sequence offset, length and quality offset per record")
+        out = C.POINTER(capi.CBlobSequences)()
+        _check(load().floria_hip_blob_sequences(self._h, blob._h, capi.ptr(so, C.c_uint64), capi.ptr(ls, C.c_uint32), capi.ptr(qo, C.c_uint64), C.c_uint64(len(so)), C.byref(out)))
+        r = out.contents
+        base_off = capi.np_from(r.base_off, int(r.n) + 1, np.uint64)
+        res = (base_off, capi.np_from(r.bases, int(base_off[-1]), np.uint8), capi.np_from(r.quals, int(base_off[-1]), np.uint8))
+        load().floria_hip_blob_sequences_free(out)
         return res
 
     def assemble_contigs_ordered(self, summary, frag_off, part_off, part_rec):

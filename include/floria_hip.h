@@ -470,7 +470,17 @@ void floria_hip_blob_free(floria_hip_blob* blob);
  * A block_size below the 32 fixed bytes of a record, or one that runs past end[c] (or a prefix cut by it), stops the chain: FLORIA_E_INVALID naming chain and offset —
  * a chain that stops exactly at end[c] is complete.  Refused before any launch, FLORIA_E_INVALID: a null argument, a blob of another context, begin[c] > end[c] or
  * end[c] past the blob.  FLORIA_E_UNSUPPORTED: 2^32 and more records.  The call works in buffers of its own and ends no residency; floria_hip_last_timing then reports
- * pileup_ms (the kernels), h2d_ms, d2h_ms, total_ms. */
+ * pileup_ms (the kernels), h2d_ms, d2h_ms, total_ms.
+ * OPEN-ENDED CHAINS (floria_hip_blob_records_opt; flags == 0 is floria_hip_blob_records, which calls it): a tool does not know where a chain ends — a .bai gives the
+ * end of a target as a hint, and a streamed file is cut at member boundaries, inside a record and inside a target.  Two flags, independent of each other:
+ *   FLORIA_CHAIN_CUT_TAIL  a block_size prefix or a record cut by end[c] ends the chain without an error; chain_stop[c] is the offset of that prefix, the first byte
+ *                          not consumed.  A block_size below 32 stays FLORIA_E_INVALID naming chain and offset.
+ *   FLORIA_CHAIN_ONE_REF   the chain ends in front of the first record whose refID differs from that of its first record (chain_stop[c] is that record's offset).
+ *                          The refID is read only after the fit checks have shown the record to lie before end[c]; with both flags a record cut by end[c] therefore
+ *                          ends the chain as a cut tail whatever its refID.
+ * chain_why[c] says how chain c ended: 0 it reached end[c] exactly, 1 cut tail, 2 another reference.  Any other flag bit is FLORIA_E_INVALID. */
+#define FLORIA_CHAIN_CUT_TAIL 1u
+#define FLORIA_CHAIN_ONE_REF  2u
 typedef struct {
     uint32_t  n_chains;
     uint64_t  n_records;
@@ -488,10 +498,31 @@ typedef struct {
     uint8_t*  l_read_name;     /* [n] */
     uint64_t* name_off;        /* [n+1] */
     uint8_t*  names;           /* [name_off[n]] */
+    uint32_t* chain_why;       /* [n_chains] 0 = reached end[c], 1 = cut tail, 2 = another reference (appended: the struct is library-allocated) */
 } floria_blob_records;
 int  floria_hip_blob_records(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* begin /* [n_chains] */, const uint64_t* end /* [n_chains] */,
                              uint32_t n_chains, floria_blob_records** out);
+int  floria_hip_blob_records_opt(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* begin /* [n_chains] */, const uint64_t* end /* [n_chains] */,
+                                 uint32_t n_chains, uint32_t flags /* FLORIA_CHAIN_* */, floria_blob_records** out);
 void floria_hip_blob_records_free(floria_blob_records* r);
+
+/* The bases and qualities of n records of a blob in one call, as the read writers want them: record i has its packed bases, (l_seq[i] + 1) / 2 bytes, at seq_off[i] and
+ * its l_seq[i] quality bytes at qual_off[i] (the offsets floria_hip_blob_records' header comment derives; any alignment, l_seq may be 0 or odd).  Record i owns bytes
+ * [base_off[i], base_off[i + 1]) of `bases` and of `quals`; base_off is the prefix sum of l_seq.  A base is the 4-bit code 1 / 2 / 4 / 8 as 'A' / 'C' / 'G' / 'T' and
+ * 'A' for every other code; the padding nibble of an odd l_seq does not appear.  A quality is q > 222 ? 255 : q + 33.  (csrc/blob_seq_kernel.h: one wavefront per
+ * record, the output written in 8-byte words between a byte-wise head and tail.)
+ * Refused before any launch, FLORIA_E_INVALID: a null argument, a blob of another context, a sequence or quality range that reaches past the blob (the message names
+ * the record).  FLORIA_E_UNSUPPORTED: 2^32 and more records, or bases in total.  The call works in buffers of its own and ends no residency; floria_hip_last_timing then
+ * reports pileup_ms (the kernel), h2d_ms, d2h_ms, total_ms. */
+typedef struct {
+    uint64_t  n;
+    uint64_t* base_off;        /* [n+1] */
+    uint8_t*  bases;           /* [base_off[n]] */
+    uint8_t*  quals;           /* [base_off[n]] */
+} floria_blob_sequences;
+int  floria_hip_blob_sequences(floria_hip_ctx* ctx, const floria_hip_blob* blob, const uint64_t* seq_off /* [n] */, const uint32_t* l_seq /* [n] */,
+                               const uint64_t* qual_off /* [n] */, uint64_t n, floria_blob_sequences** out);
+void floria_hip_blob_sequences_free(floria_blob_sequences* r);
 
 /* floria_hip_pileup_records_resident whose record bytes are a blob handle: alignments->blob must be NULL (FLORIA_E_INVALID otherwise), alignments->blob_bytes is
  * ignored and the offsets index the handle.  The same validation, against the handle's length; the same kernels, pointed at the handle's buffer; the same summary,

@@ -18,6 +18,11 @@ ALTERNATING, of (a) this build on the copy without an index against --parent-exe
 through the index against --no-index, (c) no -G with a VCF thinned to 40 SNPs for every other contig (every contig of this set has the same number of SNPs, so that is
 what lets --snp-count-filter 50 drop half of them) through the index against --no-index; then median and spread of the wall time, of the seconds BamStream spent
 opening the file (the "BAM header" figure) and of its inflate + decode seconds, and the inflated-member counts (profiles/bam_index.md).
+--inflate-compare N [--threads-list 16,1] [--with-index] [--inflate-extra "--no-index"] [--parent-exe PATH]: only the batched flow under --pileup resident,
+--inflate host and --inflate device ALTERNATING, N runs each per thread count, one process per run; then median and spread (min .. max) of the ingest seconds, of
+BamStream's seconds (inflate + decode on the host route; member planning, inflate, record table on the device route) and of the wall time, and the device route's
+report line of its last run.  --with-index writes a .bai beside the BAM; --inflate-extra adds options to every run (e.g. "--no-index" or "--output-reads").  With
+--parent-exe the UNFLAGGED tool (--pileup resident alone) of this build also alternates with the parent commit's on the same file (profiles/inflate_route.md).
 --realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
 
 Writes BAM / VCF / FASTA under $TMPDIR, runs the driver twice and prints its stage-time lines (stderr of floria-hip)."""
@@ -52,6 +57,9 @@ def main():
     ap.add_argument("--pileup-route", default="host", help="with --haplosets-compare / --paths-compare: the --pileup route of every run")
     ap.add_argument("--index-compare", type=int, default=0, help="only: indexed against unindexed reading of the BAM, and this build against --parent-exe, this many runs each")
     ap.add_argument("--parent-exe", default=None, help="with --index-compare: floria-hip of the parent commit (comparison (a); left out when not given)")
+    ap.add_argument("--inflate-compare", type=int, default=0, help="only: --pileup resident with --inflate host and --inflate device alternating, this many runs each")
+    ap.add_argument("--with-index", action="store_true", help="with --inflate-compare: write a .bai beside the BAM")
+    ap.add_argument("--inflate-extra", default="", help="with --inflate-compare: further options of every run, space-separated")
     ap.add_argument("--config", type=int, default=4, help="synth configuration of the contigs (4: long reads, 3: paired short reads)")
     ap.add_argument("--epsilon", default="0.03125", help="-e of every run")
     ap.add_argument("--block-length", default="10000", help="-l of every run")
@@ -63,11 +71,13 @@ def main():
     prefix = os.path.join(tmp, "d")
     t = time.time()
     cs = [synth.make_config_contig(a.config, i, a.scale, keep_layout=True) for i in range(a.contigs)]
-    synth_bam.write_dataset(prefix, cs, seed=1, realign=False, sub_rate=a.sub_rate)
+    synth_bam.write_dataset(prefix, cs, seed=1, realign=False, sub_rate=a.sub_rate, index=a.with_index)
     print(f"data set: {a.contigs} contigs, {sum(c.pileup.n_reads for c in cs)} reads, {sum(len(c.snp_pos) for c in cs)} SNPs, "
           f"BAM {os.path.getsize(prefix + '.bam') >> 20} MiB, written in {time.time() - t:.1f}s; host cores {os.cpu_count()}", flush=True)
     if a.index_compare:
         return index_compare(a, exe, tmp, prefix, cs)
+    if a.inflate_compare:
+        return inflate_compare(a, exe, tmp, prefix)
     base = [exe, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-e", a.epsilon, "-l", a.block_length, "--snp-count-filter", "50"]
     runs = (("batched", ["-t", str(a.threads)]), ("batched, 1 thread", ["-t", "1"]), ("one contig per batch", ["-t", str(a.threads), "--batch-contigs", "1"]),
             ("ingest only: realign DP on the host", ["-t", str(a.threads), "--ingest-only"]), ("ingest only, 1 thread", ["-t", "1", "--ingest-only"]))
@@ -139,6 +149,43 @@ def main():
         if v and v[0]:
             med = lambda xs: sorted(xs)[len(xs) // 2]
             print(f"[{key}] device calls (medians): " + ", ".join(f"{k} {med([d[k] for d in v]):g}" for k in v[0]))
+
+
+def inflate_compare(a, exe, tmp, prefix):
+    threads = [int(x) for x in a.threads_list.split(",")] if a.threads_list else [a.threads]
+    extra = a.inflate_extra.split()
+
+    def cmd(binary, t, more):
+        return [binary, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-e", a.epsilon, "-l", a.block_length, "--snp-count-filter", "50", "-t", str(t),
+                "--pileup", "resident", *extra, *more]
+    for t in threads:
+        settings = [("--inflate host", cmd(exe, t, ["--inflate", "host"])), ("--inflate device", cmd(exe, t, ["--inflate", "device"]))]
+        if a.parent_exe:
+            settings += [("unflagged, this build", cmd(exe, t, [])), ("unflagged, parent build", cmd(a.parent_exe, t, []))]
+        got = {label: [] for label, _ in settings}
+        last_line = None
+        for k in range(a.inflate_compare):
+            for label, c in settings:
+                out = os.path.join(tmp, "o_inflate")
+                t0 = time.time()
+                r = subprocess.run(c + ["-o", out], capture_output=True, text=True)
+                wall = time.time() - t0
+                if r.returncode:
+                    print(r.stderr[-2000:])
+                    raise SystemExit(1)
+                ingest = float(re.search(r"Batches \d+; ingest ([\d.]+)s", r.stderr).group(1))
+                stream = float(re.search(r"BAM: \d+ records in \d+ segments, ([\d.]+)s of inflate", r.stderr).group(1))
+                got[label].append((ingest, stream, ingest + stream, wall))
+                line = next((ln for ln in r.stderr.splitlines() if ln.startswith("Inflate on the device:")), None)
+                print(f"[-t {t}, {label}, run {k + 1}] wall {wall:.2f}s, ingest {ingest:.3f}s, BamStream {stream:.3f}s" + (f" | {line}" if line else ""), flush=True)
+                last_line = line or last_line
+                subprocess.run(["rm", "-rf", out])
+        for label, _ in settings:
+            for k, what in enumerate(("ingest", "BamStream", "BamStream + ingest", "wall")):
+                x = sorted(v[k] for v in got[label])
+                print(f"[-t {t}] [{label}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs", flush=True)
+        if last_line:
+            print(f"[-t {t}] [--inflate device] last run: {last_line}", flush=True)
 
 
 def index_compare(a, exe, tmp, prefix, cs):
