@@ -116,6 +116,18 @@ class CBlobSequences(C.Structure):
     _fields_ = [("n", C.c_uint64), ("base_off", u64p), ("bases", u8p), ("quals", u8p)]
 
 
+class CEstimateRecords(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("pos", i32p), ("cigar_off", u64p), ("n_cigar", u32p), ("seq_off", u64p), ("l_seq", u32p), ("n_groups", C.c_uint32), ("group_off", u64p)]
+
+
+class CEstimateState(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("n_err", C.c_uint32)]
+
+
+class CEstimateResult(C.Structure):
+    _fields_ = [("n_cols", C.c_uint64), ("col_group", u32p), ("col_pos", i32p), ("col_total", u32p), ("col_most", u32p), ("rec_hits", u32p), ("done", C.c_uint32)]
+
+
 class CFragmentPlan(C.Structure):
     _fields_ = [("n_contigs", C.c_uint32), ("frag_off", u64p), ("part_off", u64p), ("part_rec", u32p), ("set_order", u32p)]
 

@@ -54,6 +54,7 @@
 #include "path_kernel.h"
 #include "inflate_kernel.h"
 #include "blob_seq_kernel.h"
+#include "estimate_kernel.h"
 
 static_assert(FLORIA_MAX_PLOIDY == fl::MAX_PLOIDY, "ploidy limits out of sync");
 
@@ -286,6 +287,8 @@ struct floria_hip_ctx {
     DevBuf inf_in;                            // floria_hip_inflate_bgzf: the compressed bytes and the per-member tables (the blob has a buffer of its own)
     DevBuf rec_in, rec_out, rec_names;        // floria_hip_blob_records: the chains' tables, the per-record arrays, the compacted names (buffers of their own: no residency ends)
     DevBuf seq_in, seq_out;                   // floria_hip_blob_sequences: the records' offsets, and the bases and qualities (buffers of their own: no residency ends)
+    DevBuf est_in, est_win, est_cols;         // floria_hip_blob_estimate: the record arrays, one position window's arrays, one window's sampled columns (buffers of their own: no residency ends)
+    uint32_t estimate_window = 0;             // (tests) floria_hip_blob_estimate: positions per window, 0 = 2^22
     uint32_t inflate_slots = 0;               // (tests) floria_hip_inflate_bgzf: members in flight, 0 = two per CU
     uint32_t stage_threads = 8;
 };
@@ -1027,7 +1030,7 @@ void floria_hip_destroy(floria_hip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     sync_all(c);
-    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits, &c->inf_in, &c->rec_in, &c->rec_out, &c->rec_names, &c->seq_in, &c->seq_out}) b->release();
+    for (DevBuf* b : {&c->d_binom, &c->d_hash, &c->d_w24, &c->state_pool, &c->hist_pool, &c->opt_hist, &c->opt_dist, &c->opt_gain, &c->opt_key, &c->opt_moves, &c->misc, &c->misc0, &c->graph_buf, &c->graph_hist, &c->graph_sort, &c->up_tmp, &c->arith_ord, &c->arith_scr, &c->arith_tab, &c->arith_pool, &c->pile_in, &c->pile_out, &c->asm_plan, &c->asm_ord_scr, &c->mono_buf, &c->span_buf, &c->hs_tmp, &c->join_bits, &c->inf_in, &c->rec_in, &c->rec_out, &c->rec_names, &c->seq_in, &c->seq_out, &c->est_in, &c->est_win, &c->est_cols}) b->release();
     for (Arena* a : c->arena_cache) { a->buf.release(); delete a; }
     c->stage.release();
     c->box.release();
@@ -1105,6 +1108,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "trace") K.trace = value != 0;
     else if (k == "reassign_path") { if (value < 0 || value > 2) return fail(FLORIA_E_INVALID, "reassign_path: 0 auto | 1 parallel | 2 chain"); K.reassign_path = (uint32_t)value; }
     else if (k == "inflate_slots") { if (value < 0 || value > (int64_t)0x7fffffff) return fail(FLORIA_E_INVALID, "inflate_slots: 0 = two members per CU | the largest number of members in flight"); ctx->inflate_slots = (uint32_t)value; }
+    else if (k == "estimate_window") { if (value < 0 || value > (int64_t)(1u << 30)) return fail(FLORIA_E_INVALID, "estimate_window: 0 = 2^22 positions | 1 .. 2^30 positions per window"); ctx->estimate_window = (uint32_t)value; }
     else if (k == "slots") ctx->user_slots = (uint32_t)std::max<int64_t>(0, value);
     else if (k == "stage_threads") ctx->stage_threads = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 16));
     else return fail(FLORIA_E_INVALID, "unknown option '" + k + "'");
@@ -3151,6 +3155,182 @@ int floria_hip_blob_sequences(floria_hip_ctx* ctx, const floria_hip_blob* blob, 
     guard.r = nullptr;
     *out = R;
     return 0;
+}
+
+void floria_hip_estimate_result_free(floria_estimate_result* r) {
+    if (!r) return;
+    g_big.put(r->col_group); g_big.put(r->col_pos); g_big.put(r->col_total); g_big.put(r->col_most); g_big.put(r->rec_hits);
+    free(r);
+}
+
+// The -e / -l estimate on a blob (estimate_kernel.h).  The host part checks every range, runs the span pass, then walks each group in position windows that hold
+// covered positions only at their start (a gap between records is jumped, never scanned) and reads the chain's state back after every window: the number of sampled
+// columns sizes the count pass, `done` ends the walk.
+int floria_hip_blob_estimate(floria_hip_ctx* ctx, const floria_hip_blob* blob, const floria_estimate_records* E, uint32_t stop, floria_estimate_state* inout, floria_estimate_result** out) {
+    if (!ctx || !blob || !E || !inout || !out) return fail(FLORIA_E_INVALID, "null argument");
+    *out = nullptr;
+    const uint64_t n = E->n;
+    if ((n && (!E->pos || !E->cigar_off || !E->n_cigar || !E->seq_off || !E->l_seq)) || !E->group_off) return fail(FLORIA_E_INVALID, "null argument");
+    if (blob->ctx != ctx) return fail(FLORIA_E_INVALID, "the blob belongs to another context");
+    if (n >= (1ull << 32)) return fail(FLORIA_E_UNSUPPORTED, "blob_estimate: 2^32 and more records");
+    // the host part: the groups, every position and every range against the blob's length, before anything is uploaded or launched
+    const uint32_t ng = E->n_groups;
+    if (E->group_off[0] != 0) return fail(FLORIA_E_INVALID, "blob_estimate: group_off does not start at 0");
+    for (uint32_t g = 0; g < ng; ++g)
+        if (E->group_off[g] > E->group_off[g + 1]) return fail(FLORIA_E_INVALID, "blob_estimate: group_off descends at group " + std::to_string(g));
+    if (E->group_off[ng] != n) return fail(FLORIA_E_INVALID, "blob_estimate: group_off ends at " + std::to_string(E->group_off[ng]) + ", not at the " + std::to_string(n) + " records");
+    const uint64_t B = blob->bytes;
+    for (uint32_t g = 0; g < ng; ++g)
+        for (uint64_t i = E->group_off[g]; i < E->group_off[g + 1]; ++i) {
+            const std::string rec = "blob_estimate: record " + std::to_string(i);
+            if (E->n_cigar[i] == 0) return fail(FLORIA_E_INVALID, rec + " has no CIGAR operation");
+            if (E->pos[i] < 0) return fail(FLORIA_E_INVALID, rec + " has a negative pos (" + std::to_string(E->pos[i]) + ")");
+            if (i > E->group_off[g] && E->pos[i] < E->pos[i - 1]) return fail(FLORIA_E_INVALID, rec + ": pos descends inside group " + std::to_string(g));
+            const uint64_t cig = 4ull * E->n_cigar[i], packed = ((uint64_t)E->l_seq[i] + 1) / 2;
+            const char* what = E->cigar_off[i] > B || cig > B - E->cigar_off[i] ? "CIGAR" : E->seq_off[i] > B || packed > B - E->seq_off[i] ? "sequence" : nullptr;
+            if (what) return fail(FLORIA_E_INVALID, "blob_estimate: the " + std::string(what) + " bytes of record " + std::to_string(i) + " reach past the blob (" + std::to_string(B) + " bytes)");
+        }
+    floria_estimate_result* R = (floria_estimate_result*)calloc(1, sizeof(floria_estimate_result));
+    if (!R) return fail(FLORIA_E_NOMEM, "calloc");
+    struct Guard { floria_estimate_result* r; hipStream_t st; ~Guard() { if (r) { (void)hipStreamSynchronize(st); floria_hip_estimate_result_free(r); } } } guard{R, ctx->stream};
+    R->rec_hits = (uint32_t*)cells_bytes(4 * n);
+    if (!R->rec_hits) return fail(FLORIA_E_NOMEM, "malloc");
+    memset(R->rec_hits, 0, 4 * n);
+    ctx->timing = floria_timing{};
+    std::vector<uint32_t> col_group, col_total, col_most;
+    std::vector<int32_t> col_pos;
+    auto finish = [&]() -> int {
+        const size_t nc = col_group.size();
+        R->n_cols = nc;
+        R->col_group = (uint32_t*)cells_bytes(4 * nc); R->col_pos = (int32_t*)cells_bytes(4 * nc); R->col_total = (uint32_t*)cells_bytes(4 * nc); R->col_most = (uint32_t*)cells_bytes(4 * nc);
+        if (!R->col_group || !R->col_pos || !R->col_total || !R->col_most) return fail(FLORIA_E_NOMEM, "malloc");
+        if (nc) { memcpy(R->col_group, col_group.data(), 4 * nc); memcpy(R->col_pos, col_pos.data(), 4 * nc); memcpy(R->col_total, col_total.data(), 4 * nc); memcpy(R->col_most, col_most.data(), 4 * nc); }
+        guard.r = nullptr;
+        *out = R;
+        return 0;
+    };
+    if (inout->n_err >= stop) { R->done = 1; return finish(); }
+    if (n == 0) return finish();
+
+    HIPCHK(hipSetDevice(ctx->device));
+    EventTimer T(ctx->stream);
+    Carve C;
+    const Seg s_pos = C.seg(4 * n), s_co = C.seg(8 * n), s_nc = C.seg(4 * n), s_so = C.seg(8 * n), s_ls = C.seg(4 * n), s_end = C.seg(8 * n), s_hits = C.seg(4 * n);
+    if (int rc = C.place(ctx->est_in)) return rc;
+    int t = T.begin(K_H2D);
+    HIPCHK(C.up(s_pos, E->pos, 4 * n, ctx->stream)); HIPCHK(C.up(s_co, E->cigar_off, 8 * n, ctx->stream)); HIPCHK(C.up(s_nc, E->n_cigar, 4 * n, ctx->stream));
+    HIPCHK(C.up(s_so, E->seq_off, 8 * n, ctx->stream)); HIPCHK(C.up(s_ls, E->l_seq, 4 * n, ctx->stream));
+    HIPCHK(hipMemsetAsync(C.at<>(s_hits), 0, 4 * n, ctx->stream));
+    T.end(t);
+    fl::EstRecs recs{};
+    recs.blob = blob->buf.as<const uint8_t>(); recs.pos = C.at<const int32_t>(s_pos); recs.cigar_off = C.at<const uint64_t>(s_co); recs.n_cigar = C.at<const uint32_t>(s_nc);
+    recs.seq_off = C.at<const uint64_t>(s_so); recs.l_seq = C.at<const uint32_t>(s_ls); recs.end = C.at<int64_t>(s_end); recs.rec_hits = C.at<uint32_t>(s_hits);
+    const uint32_t max_wgs = 8u * (uint32_t)ctx->n_cu;
+    auto rec_grid = [&](uint64_t recs_n) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((recs_n + fl::EST_WAVES - 1) / fl::EST_WAVES, max_wgs))); };
+    t = T.begin(K_PILEUP);
+    hipLaunchKernelGGL(fl::est_span_kernel, rec_grid(n), dim3(64 * fl::EST_WAVES), 0, ctx->stream, recs, n);
+    HIPCHK(hipGetLastError());
+    T.end(t);
+    std::vector<int64_t> end(n);
+    t = T.begin(K_D2H);
+    HIPCHK(hipMemcpyAsync(end.data(), recs.end, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    T.end(t);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    int64_t widest = 1;
+    for (uint32_t g = 0; g < ng; ++g) {
+        int64_t top = 0;
+        for (uint64_t i = E->group_off[g]; i < E->group_off[g + 1]; ++i) {
+            if (end[i] > (int64_t)0x7fffffff) return fail(FLORIA_E_UNSUPPORTED, "blob_estimate: record " + std::to_string(i) + " ends at " + std::to_string(end[i]) + ", beyond 2^31 - 1");
+            top = std::max(top, end[i]);
+        }
+        if (E->group_off[g] < E->group_off[g + 1]) widest = std::max(widest, top - (int64_t)E->pos[E->group_off[g]]);
+    }
+    // one window's arrays, sized for the widest window any group needs
+    const uint32_t win = (uint32_t)std::min<int64_t>(ctx->estimate_window ? ctx->estimate_window : (1u << 22), widest);
+    const uint32_t max_chunks = (win + fl::EST_CHUNK - 1) / fl::EST_CHUNK;
+    const size_t padded = (size_t)max_chunks * fl::EST_CHUNK;
+    const uint32_t max_iv = (uint32_t)std::min<uint64_t>((uint64_t)(stop - inout->n_err) + 1, (uint64_t)win / fl::EST_PERIOD + 2);      // starts lie 1000 ordinals apart; all but the last reach a deep column
+    Carve Wc;
+    const Seg w_ord = Wc.seg(4 * padded), w_tot = Wc.seg(4 * padded), w_poo = Wc.seg(4 * padded), w_nd = Wc.seg(4 * padded);
+    const Seg w_sc = Wc.seg(4 * (size_t)max_chunks), w_sd = Wc.seg(4 * (size_t)max_chunks), w_nc = Wc.seg(4 * (size_t)max_chunks), w_fd = Wc.seg(4 * (size_t)max_chunks);
+    const Seg w_iv = Wc.seg(12 * (size_t)max_iv), w_st = Wc.seg(sizeof(fl::EstState));
+    if (int rc = Wc.place(ctx->est_win)) return rc;
+    fl::EstWindow W{};
+    W.ord = Wc.at<uint32_t>(w_ord); W.tot = Wc.at<uint32_t>(w_tot); W.pos_of_ord = Wc.at<uint32_t>(w_poo); W.next_deep = Wc.at<uint32_t>(w_nd);
+    W.sum_cov = Wc.at<int32_t>(w_sc); W.sum_dep = Wc.at<int32_t>(w_sd); W.n_cov = Wc.at<int32_t>(w_nc); W.first_deep = Wc.at<uint32_t>(w_fd);
+    uint32_t* const d_iv = Wc.at<uint32_t>(w_iv);
+    fl::EstState* const d_st = Wc.at<fl::EstState>(w_st);
+    fl::EstState st{};
+    st.count = inout->count; st.n_err = inout->n_err;
+    t = T.begin(K_H2D);
+    HIPCHK(hipMemcpyAsync(d_st, &st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    T.end(t);
+
+    for (uint32_t g = 0; g < ng && !st.done; ++g) {
+        const uint64_t g0 = E->group_off[g], g1 = E->group_off[g + 1];
+        if (g0 == g1) continue;
+        uint64_t lo = g0, hi = g0;                     // records [lo, hi) may meet the window: everything in front of lo ends before it, everything from hi on begins behind it
+        int64_t w0 = E->pos[g0];
+        while (!st.done) {
+            const int64_t w1 = w0 + (int64_t)win;
+            while (lo < g1 && end[lo] <= w0) ++lo;
+            while (hi < g1 && (int64_t)E->pos[hi] < w1) ++hi;
+            W.w0 = w0; W.wn = win; W.n_chunks = max_chunks;
+            const dim3 chunks(std::min<uint32_t>(max_chunks, max_wgs)), threads(fl::EST_THREADS);
+            t = T.begin(K_PILEUP);
+            HIPCHK(hipMemsetAsync(W.ord, 0, 4 * padded, ctx->stream)); HIPCHK(hipMemsetAsync(W.tot, 0, 4 * padded, ctx->stream));
+            hipLaunchKernelGGL(fl::est_mark_kernel, rec_grid(hi - lo), dim3(64 * fl::EST_WAVES), 0, ctx->stream, recs, lo, hi, W);
+            hipLaunchKernelGGL(fl::est_sum_kernel, chunks, threads, 0, ctx->stream, W);
+            hipLaunchKernelGGL(fl::est_tables_kernel, dim3(1), threads, 0, ctx->stream, W.sum_cov, W.sum_dep, (uint32_t*)nullptr, max_chunks, (uint32_t*)nullptr);
+            hipLaunchKernelGGL(fl::est_depth_kernel, chunks, threads, 0, ctx->stream, W);
+            hipLaunchKernelGGL(fl::est_tables_kernel, dim3(1), threads, 0, ctx->stream, W.n_cov, (int32_t*)nullptr, W.first_deep, max_chunks, &d_st->n_cov);
+            hipLaunchKernelGGL(fl::est_ordinal_kernel, chunks, threads, 0, ctx->stream, W);
+            hipLaunchKernelGGL(fl::est_chain_kernel, dim3(1), dim3(64), 0, ctx->stream, d_st, stop, W, d_iv, max_iv);
+            HIPCHK(hipGetLastError());
+            T.end(t);
+            t = T.begin(K_D2H);
+            HIPCHK(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+            T.end(t);
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            if (st.overflow) return fail(FLORIA_E_DEVICE, "blob_estimate: the hop chain met more intervals than its list holds (" + std::to_string(max_iv) + ")");
+            if (st.n_cols) {
+                const uint32_t nc = st.n_cols;
+                Carve Cc;
+                const Seg c_pos = Cc.seg(4 * (size_t)nc), c_cnt = Cc.seg(64 * (size_t)nc), c_tot = Cc.seg(4 * (size_t)nc), c_most = Cc.seg(4 * (size_t)nc);
+                if (int rc = Cc.place(ctx->est_cols)) return rc;
+                t = T.begin(K_PILEUP);
+                HIPCHK(hipMemsetAsync(Cc.at<>(c_cnt), 0, 64 * (size_t)nc, ctx->stream));
+                hipLaunchKernelGGL(fl::est_expand_kernel, dim3(std::min<uint32_t>(std::min(st.n_iv, max_iv), max_wgs)), threads, 0, ctx->stream, d_iv, std::min(st.n_iv, max_iv), W.pos_of_ord, Cc.at<uint32_t>(c_pos));
+                hipLaunchKernelGGL(fl::est_count_kernel, rec_grid(hi - lo), dim3(64 * fl::EST_WAVES), 0, ctx->stream, recs, lo, hi, w0, win, Cc.at<const uint32_t>(c_pos), nc, Cc.at<uint32_t>(c_cnt));
+                hipLaunchKernelGGL(fl::est_reduce_kernel, dim3(std::min<uint32_t>((nc + fl::EST_THREADS - 1) / fl::EST_THREADS, max_wgs)), threads, 0, ctx->stream, Cc.at<const uint32_t>(c_cnt), nc,
+                                   Cc.at<uint32_t>(c_tot), Cc.at<uint32_t>(c_most));
+                HIPCHK(hipGetLastError());
+                T.end(t);
+                const size_t at = col_group.size();
+                col_group.resize(at + nc, g); col_pos.resize(at + nc); col_total.resize(at + nc); col_most.resize(at + nc);
+                t = T.begin(K_D2H);
+                HIPCHK(hipMemcpyAsync(col_pos.data() + at, Cc.at<>(c_pos), 4 * (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(hipMemcpyAsync(col_total.data() + at, Cc.at<>(c_tot), 4 * (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(hipMemcpyAsync(col_most.data() + at, Cc.at<>(c_most), 4 * (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
+                T.end(t);
+                HIPCHK(hipStreamSynchronize(ctx->stream));
+                for (size_t i = at; i < at + nc; ++i) col_pos[i] = (int32_t)(w0 + col_pos[i]);      // (the window's relative positions; every end is <= 2^31 - 1)
+            }
+            // the next window: right behind this one while a record reaches over its end, else at the next record
+            while (lo < hi && end[lo] <= w1) ++lo;
+            if (lo < hi) w0 = w1;
+            else if (hi < g1) w0 = E->pos[hi];
+            else break;
+        }
+    }
+    t = T.begin(K_D2H);
+    HIPCHK(hipMemcpyAsync(R->rec_hits, recs.rec_hits, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+    T.end(t);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    T.publish(ctx->timing);
+    inout->count = st.count; inout->n_err = st.n_err;
+    R->done = st.done;
+    return finish();
 }
 
 int floria_hip_pileup_records_resident_blob(floria_hip_ctx* ctx, const floria_hip_blob* blob, const floria_alignments* A, const floria_snp_table* S, const floria_ref_seqs* F,

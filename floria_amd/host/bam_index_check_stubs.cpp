@@ -7,6 +7,7 @@
 DEVICE_ENTRY(floria_hip_assemble_contigs_opt)
 DEVICE_ENTRY(floria_hip_blob_bytes)
 DEVICE_ENTRY(floria_hip_blob_download)
+DEVICE_ENTRY(floria_hip_blob_estimate)
 DEVICE_ENTRY(floria_hip_blob_free)
 DEVICE_ENTRY(floria_hip_blob_records_free)
 DEVICE_ENTRY(floria_hip_blob_records_opt)
@@ -16,6 +17,7 @@ DEVICE_ENTRY(floria_hip_inflate_bgzf)
 DEVICE_ENTRY(floria_hip_pileup_records_resident_blob)
 DEVICE_ENTRY(floria_hip_contig_free)
 DEVICE_ENTRY(floria_hip_drop_monomorphic)
+DEVICE_ENTRY(floria_hip_estimate_result_free)
 DEVICE_ENTRY(floria_hip_last_timing)
 DEVICE_ENTRY(floria_hip_mono_result_free)
 DEVICE_ENTRY(floria_hip_pileup_records)

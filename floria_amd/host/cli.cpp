@@ -41,7 +41,11 @@ void usage() {
           "                    the compressed members of a segment go up as they lie in the file, are inflated there (floria_hip_inflate_bgzf) and the records are read where\n"
           "                    they are walked: the host sees a header-sized table of them (floria_hip_blob_records_opt), --output-reads' bases come back in one call per\n"
           "                    ingest round (floria_hip_blob_sequences).  Needs --pileup resident (no other route leaves the record bytes unread on the host); the BAM header\n"
-          "                    and the -e / -l estimate are still inflated on the host.  Same files\n"
+          "                    and the -e / -l estimate are still inflated on the host (the estimate unless --estimate device).  Same files\n"
+          "  --estimate host|device   where the -e / -l estimate (made when -e or -l is not given) reads the records: host [default] = the file's first segments are inflated\n"
+          "                    and decoded on the host threads; device = they are inflated on the device as under --inflate device and the sampled pileup columns are\n"
+          "                    counted there (floria_hip_blob_estimate): header-sized data comes back.  Needs --inflate device (the pass reads the blobs of that route);\n"
+          "                    accepted and unused when both -e and -l are given.  Same estimate, same files\n"
           "  --haplosets host|resident   where the haplosets live between S2 and the writers: host [default] = S2 returns the group lists and the four calls behind it\n"
           "                    (COV / ERR, HAPQ, allele tables, read trims) take them up again; resident = S2 splits and sorts on the device and keeps the haplosets there\n"
           "                    (floria_hip_reassign_batch_resident), the lists come back once for the writers and the four calls take the handle.  Any --pileup route.  Same files\n"
@@ -160,6 +164,11 @@ Cli parse_args(int argc, char** argv) {
             if (v != "host" && v != "device") throw Error(FLORIA_E_INVALID, "--inflate takes host or device, not '" + v + "'");
             cli.inflate_device = v == "device";
         }
+        else if (a == "--estimate") {
+            const std::string v = val();
+            if (v != "host" && v != "device") throw Error(FLORIA_E_INVALID, "--estimate takes host or device, not '" + v + "'");
+            cli.estimate_device = v == "device";
+        }
         else if (a == "--haplosets") {
             const std::string v = val();
             if (v != "host" && v != "resident") throw Error(FLORIA_E_INVALID, "--haplosets takes host or resident, not '" + v + "'");
@@ -172,6 +181,7 @@ Cli parse_args(int argc, char** argv) {
         }
         else if (a == "--stitch-paths") cli.stitch_paths = true;      // (tests, with --stitch-graph) also one Q line per path: its nodes
         else if (a == "--dump-plan") cli.dump_plan = val();            // (tests, with --ingest-only) the fragment plan of every contig: needs no GPU under --pileup host
+        else if (a == "--dump-estimate") cli.dump_estimate = val();    // (tests, with --ingest-only) the sampled columns and the state of the -e / -l estimate: needs no GPU under --estimate host
         else if (a == "--dump-handles") cli.dump_handles = val();      // (tests) the resident arrays of every contig of every batch, whichever route made the handle
         else if (a == "--ingest-only") cli.ingest_only = true;          // (tests) stop after ingest: needs no GPU
         else if (a == "--stitch-graph") cli.stitch_graph = val();       // (tests) N / E lines of a hap graph -> F / P lines on stdout: needs no GPU
@@ -200,7 +210,12 @@ void validate(const Cli& cli) {
     if (cli.inflate_device && o.pileup != PileupRoute::Resident)
         throw Error(FLORIA_E_UNSUPPORTED, "--inflate device needs --pileup resident: only that route leaves the record bytes unread on the host (every other route walks or "
                                           "merges the records' CIGARs, bases and qualities there, so they would have to come back down)");
+    if (cli.estimate_device && !cli.inflate_device)
+        throw Error(FLORIA_E_UNSUPPORTED, "--estimate device needs --inflate device: the estimate then reads the blobs that route inflates on the device (under --inflate host "
+                                          "the records are inflated on the host anyway, and its estimate reads them there)");
     if (!cli.dump_plan.empty() && !cli.ingest_only) throw Error(FLORIA_E_INVALID, "--dump-plan needs --ingest-only");
+    if (!cli.dump_estimate.empty() && !cli.ingest_only) throw Error(FLORIA_E_INVALID, "--dump-estimate needs --ingest-only");
+    if (!cli.dump_estimate.empty() && cli.have_e && cli.have_l) throw Error(FLORIA_E_INVALID, "--dump-estimate needs the estimate: leave out -e or -l");
     if (o.bam_file.empty()) throw Error(FLORIA_E_INVALID, "Must input a BAM file.");
     if (o.vcf_file.empty() || o.reference_fasta.empty()) throw Error(FLORIA_E_INVALID, "-v and -r are required");
     if (!(o.ploidy_sensitivity >= 1 && o.ploidy_sensitivity <= 3)) throw Error(FLORIA_E_INVALID, "Ploidy sensitivty option must be between 1 and 3");

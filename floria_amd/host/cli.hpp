@@ -10,7 +10,8 @@ namespace floria {
 struct Cli {
     Options o;
     bool have_e = false, have_l = false;
-    std::string dump_frags, dump_seq_pos, dump_plan, dump_handles;
+    std::string dump_frags, dump_seq_pos, dump_plan, dump_handles, dump_estimate;
+    bool estimate_device = false;                  // --estimate device: the -e / -l estimate reads device segments (floria_hip_blob_estimate)
     size_t batch_contigs = 4096;         // --batch-contigs
     uint64_t batch_cells = 256ull << 20; // --batch-cells (1.5 GB of pinned staging)
     bool ingest_only = false, no_realign = false, have_realign = false;

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <iosfwd>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -345,7 +346,8 @@ public:
     const std::string& index_path() const;             // "" when no index is in use
     struct IndexUse { size_t selected, members_inflated, members_in_file; };
     IndexUse index_use() const;                        // (members_in_file walks the member headers that have not been walked yet)
-    // --inflate device: from here on (once, after the parameter estimate's pass and its rewind()) next() inflates nothing on the host.  It plans a run of ADJACENT
+    // --inflate device: from here on (after the parameter estimate's pass and its rewind(); under --estimate device also in front of that pass, which then reads the
+    // unindexed segments described below, and again behind its rewind()) next() inflates nothing on the host.  Each call begins at the first record.  It plans a run of ADJACENT
     // members of the mapped file and the chains to walk in it, has them inflated on the context (floria_hip_inflate_bgzf uploads everything between the first and the
     // last member, so a segment never spans a gap between selected targets) and reads the record table (floria_hip_blob_records_opt): the segment it hands out is a
     // BamFile with `dev` and without `raw`.  With an index: one ONE_REF | CUT_TAIL chain per selected target from the index's offset, members up to the index's end
@@ -526,8 +528,18 @@ public:
     EpsilonEstimator();
     ~EpsilonEstimator();
     void feed(const BamFile& segment);
+    // The same for a device segment (--estimate device): the records are filtered on the segment's table, grouped by target and handed to one
+    // floria_hip_blob_estimate call with the state carried so far; the sampled columns and the records' hits that come back go through the combine step below.
+    void feed_device(const BamFile& segment);
+    // The combine step both routes end in: a sampled column (with total >= 5 it gives one more error rate), and `hits` more entries of l_seq in the length multiset.
+    void add_column(int32_t tid, int32_t pos, uint32_t total, uint32_t most);
+    void add_length(size_t l_seq, uint64_t hits);
     bool done() const;
     std::pair<size_t, double> result();                // (block length, epsilon)
+    // --dump-estimate: "tid pos total most" per sampled column, then "count N", "n_err N" and one "length L M" per distinct l_seq, ascending
+    void dump(std::ostream& out) const;
+    size_t device_calls = 0;                           // feed_device: calls, and their device events (floria_hip_last_timing)
+    double device_kernel_ms = 0., device_h2d_ms = 0., device_d2h_ms = 0.;
 private:
     struct Impl;
     std::unique_ptr<Impl> p_;

@@ -28,6 +28,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <climits>
@@ -1885,17 +1886,23 @@ void RealignQueue::append(RealignQueue&& o) {
 // passes its default mask (unmapped | secondary | qc-fail | duplicate are dropped), contig by contig in coordinate order.
 struct EpsilonEstimator::Impl {
     size_t count = 0;
-    std::vector<double> err_vec;
-    std::vector<size_t> read_lengths;
+    std::vector<double> err_vec;                           // one per sampled column with total >= 5: n_err is its size
+    std::map<size_t, uint64_t> lengths;                    // the multiset of the read lengths: l_seq -> multiplicity
+    std::vector<std::array<int64_t, 4>> columns;           // every sampled column: tid, pos, total, most (--dump-estimate)
     bool done = false;
+    static constexpr size_t stop = 1000;
 };
 EpsilonEstimator::EpsilonEstimator() : p_(new Impl) {}
 EpsilonEstimator::~EpsilonEstimator() = default;
 bool EpsilonEstimator::done() const { return p_->done; }
+void EpsilonEstimator::add_length(size_t l_seq, uint64_t hits) { if (hits) p_->lengths[l_seq] += hits; }
+void EpsilonEstimator::add_column(int32_t tid, int32_t pos, uint32_t total, uint32_t most) {
+    p_->columns.push_back({tid, pos, total, most});
+    if (total >= 5) p_->err_vec.push_back(((double)total - (double)most) / (double)most);
+}
 void EpsilonEstimator::feed(const BamFile& bam) {
     size_t& count = p_->count;
     std::vector<double>& err_vec = p_->err_vec;
-    std::vector<size_t>& read_lengths = p_->read_lengths;
     bool& done = p_->done;
     if (done) return;
     struct Aln { const BamRecord* r; int64_t beg, end; };
@@ -1904,7 +1911,7 @@ void EpsilonEstimator::feed(const BamFile& bam) {
         if (r.tid < 0 || (size_t)r.tid >= by_tid.size() || (r.flags & F_ERRORS) || r.cigar.empty()) continue;
         by_tid[r.tid].push_back({&r, r.pos, reference_end(r)});
     }
-    const size_t stop = 1000;
+    const size_t stop = Impl::stop;
     auto base_at = [](const BamRecord& r, int64_t pos, char* base) -> bool {          // false: deletion / refskip / not aligned here
         size_t q = 0; int64_t ref = r.pos;
         for (size_t ck = 0; ck < r.cigar.size(); ++ck) {
@@ -1922,7 +1929,8 @@ void EpsilonEstimator::feed(const BamFile& bam) {
         }
         return false;
     };
-    for (auto& alns : by_tid) {
+    for (size_t tid = 0; tid < by_tid.size(); ++tid) {
+        std::vector<Aln>& alns = by_tid[tid];
         if (done) break;
         std::stable_sort(alns.begin(), alns.end(), [](const Aln& a, const Aln& b) { return a.beg < b.beg; });
         size_t next = 0;
@@ -1945,30 +1953,73 @@ void EpsilonEstimator::feed(const BamFile& bam) {
                 count += (size_t)step; pos += step;
                 continue;
             }
-            double most_base = 0., total_c = 0.;
-            double base_cnt[256] = {0};
+            uint32_t most_base = 0, total_c = 0;
+            uint32_t base_cnt[256] = {0};
             for (const Aln& a : active) {
                 char b;
                 if (!base_at(*a.r, pos, &b)) continue;
                 if ((a.r->flags & F_ERRORS) || (a.r->flags & F_SECONDARY) || a.r->seq.empty()) continue;
-                read_lengths.push_back(a.r->seq.size());
-                base_cnt[(unsigned char)b] += 1.;
+                add_length(a.r->seq.size(), 1);
+                base_cnt[(unsigned char)b] += 1;
             }
-            for (double v : base_cnt) { if (v > most_base) most_base = v; total_c += v; }
+            for (uint32_t v : base_cnt) { if (v > most_base) most_base = v; total_c += v; }
+            add_column((int32_t)tid, (int32_t)pos, total_c, most_base);
             ++pos;
-            if (total_c < 5.) continue;                                      // (count is not advanced: the next column is sampled too)
-            err_vec.push_back((total_c - most_base) / most_base);
-            if (err_vec.size() >= stop && !read_lengths.empty()) { done = true; break; }
+            if (total_c < 5) continue;                                       // (count is not advanced: the next column is sampled too)
+            if (err_vec.size() >= stop && !p_->lengths.empty()) { done = true; break; }
             ++count;
         }
     }
 }
+void EpsilonEstimator::feed_device(const BamFile& bam) {
+    if (p_->done) return;
+    if (!bam.dev || !bam.dev->blob) throw Error(FLORIA_E_INVALID, "EpsilonEstimator::feed_device: not a device segment");
+    // the three filters on the table's fields, the records of every target in position order (the order the host pass sorts them into)
+    std::vector<int32_t> pos;
+    std::vector<uint64_t> cigar_off, seq_off, group_off{0};
+    std::vector<uint32_t> n_cigar, l_seq;
+    std::vector<int32_t> group_tid;
+    for (size_t tid = 0; tid < bam.by_tid.size(); ++tid) {
+        std::vector<uint32_t> ix;
+        for (const uint32_t i : bam.by_tid[tid]) { const BamRecord& r = bam.records[i]; if (!(r.flags & F_ERRORS) && !r.cigar.empty()) ix.push_back(i); }
+        if (ix.empty()) continue;
+        std::stable_sort(ix.begin(), ix.end(), [&](uint32_t a, uint32_t b) { return bam.records[a].pos < bam.records[b].pos; });
+        for (const uint32_t i : ix) {
+            const BamRecord& r = bam.records[i];
+            pos.push_back((int32_t)r.pos); cigar_off.push_back((uint64_t)(uintptr_t)r.cigar.p); n_cigar.push_back((uint32_t)r.cigar.n);
+            seq_off.push_back((uint64_t)(uintptr_t)r.seq.packed); l_seq.push_back((uint32_t)r.seq.n);
+        }
+        group_off.push_back(pos.size()); group_tid.push_back((int32_t)tid);
+    }
+    floria_estimate_records recs{};
+    recs.n = pos.size(); recs.pos = pos.data(); recs.cigar_off = cigar_off.data(); recs.n_cigar = n_cigar.data(); recs.seq_off = seq_off.data(); recs.l_seq = l_seq.data();
+    recs.n_groups = (uint32_t)group_tid.size(); recs.group_off = group_off.data();
+    floria_estimate_state st{p_->count, (uint32_t)p_->err_vec.size()};
+    floria_estimate_result* res = nullptr;
+    if (const int rc = floria_hip_blob_estimate(bam.dev->ctx, bam.dev->blob, &recs, (uint32_t)Impl::stop, &st, &res)) throw Error(rc, std::string("floria_hip_blob_estimate: ") + floria_hip_last_error());
+    for (uint64_t c = 0; c < res->n_cols; ++c) add_column(group_tid[res->col_group[c]], res->col_pos[c], res->col_total[c], res->col_most[c]);
+    for (size_t i = 0; i < pos.size(); ++i) add_length(l_seq[i], res->rec_hits[i]);
+    p_->count = (size_t)st.count;
+    p_->done = res->done != 0;
+    floria_hip_estimate_result_free(res);
+    if (p_->err_vec.size() != st.n_err) throw Error(FLORIA_E_DEVICE, "floria_hip_blob_estimate: the columns returned do not add up to the state returned");
+    floria_timing tm{};
+    if (floria_hip_last_timing(bam.dev->ctx, &tm) == 0) { device_kernel_ms += tm.pileup_ms; device_h2d_ms += tm.h2d_ms; device_d2h_ms += tm.d2h_ms; }
+    ++device_calls;
+}
+void EpsilonEstimator::dump(std::ostream& out) const {
+    for (const auto& c : p_->columns) out << c[0] << " " << c[1] << " " << c[2] << " " << c[3] << "\n";
+    out << "count " << p_->count << "\nn_err " << p_->err_vec.size() << "\n";
+    for (const auto& kv : p_->lengths) out << "length " << kv.first << " " << kv.second << "\n";
+}
 std::pair<size_t, double> EpsilonEstimator::result() {
-    std::vector<size_t>& read_lengths = p_->read_lengths;
     std::vector<double>& err_vec = p_->err_vec;
-    std::sort(read_lengths.begin(), read_lengths.end());
-    if (read_lengths.empty()) return {500, 0.01};
-    const size_t q_66 = read_lengths[read_lengths.size() * 66 / 100];
+    uint64_t n = 0;
+    for (const auto& kv : p_->lengths) n += kv.second;
+    if (n == 0) return {500, 0.01};
+    uint64_t at = n * 66 / 100;                                              // read_lengths[len * 66 / 100] of the sorted multiset
+    size_t q_66 = 0;
+    for (const auto& kv : p_->lengths) { if (at < kv.second) { q_66 = kv.first; break; } at -= kv.second; }
     std::sort(err_vec.begin(), err_vec.end());
     const double med66 = err_vec.empty() ? 0.0 : err_vec[err_vec.size() * 66 / 100];
     return {std::max<size_t>(q_66, 500), std::max(med66, 0.01)};             // constants::MINIMUM_BLOCK_SIZE = 500

@@ -28,11 +28,13 @@
 // lists and COV / ERR, HAPQ, the allele tables and the read trims take them up again.  resident: floria_hip_reassign_batch_resident splits and sorts on the device and
 // keeps the haplosets there as a handle; the lists come back once (floria_hip_haplosets_download) for the writers and the four calls take the handle (the allele tables and
 // trims of a batch that mixes contigs with and without a handle of their own still go by lists).  Same files.
-// For tests: --dump-plan FILE (with --ingest-only, any route: the fragment plan per contig), --dump-handles FILE (any route: the resident arrays of every contig of every batch).
+// For tests: --dump-plan FILE (with --ingest-only, any route: the fragment plan per contig), --dump-estimate FILE (with --ingest-only, either --estimate route: the sampled columns and the state of the -e / -l
+// estimate), --dump-handles FILE (any route: the resident arrays of every contig of every batch).
 // --inflate host | device (with --pileup resident): where the BGZF members are inflated.  host [default]: on the host threads, the inflated records uploaded for the walk.
 // device: BamStream plans runs of adjacent members from their headers (inflate_on_device), floria_hip_inflate_bgzf inflates them into a blob, floria_hip_blob_records_opt
 // returns the header-sized record table, the walk reads the blob (floria_hip_pileup_records_resident_blob); a CG-tag record's and a host-walk contig's bytes come down by
-// floria_hip_blob_download, --output-reads' sequences by one floria_hip_blob_sequences call per ingest round.  The header and the -e / -l estimate stay on the host.  The next
+// floria_hip_blob_download, --output-reads' sequences by one floria_hip_blob_sequences call per ingest round.  The header and the -e / -l estimate stay on the host
+// (the estimate unless --estimate device: its pass then reads device segments of the stream in file order and one floria_hip_blob_estimate call per segment).  The next
 // segment's inflate does NOT overlap the current batch's phasing (not built).  The log gains one line.  Same files.
 // --no-index: a .bai beside the BAM (X.bam.bai, then X.bai) is used when present - the contigs that -G and --snp-count-filter leave are read through it, each from its
 // indexed offset, and the log gains one line (contigs selected, BGZF members inflated, members in the file); --no-index streams the whole file in order as without one.  Same files.
@@ -132,6 +134,9 @@ struct RunStats {
     uint64_t resident_bytes_back = 0, resident_removed_snps = 0, resident_dropped_reads = 0;
     uint64_t inflate_host_walk_bytes = 0;                                    // --inflate device: record bytes that came down for contigs that keep the host walk
     double t_blob_sequences = 0.;                                            // ... and the seconds of the rounds' floria_hip_blob_sequences calls
+    // --estimate device: the segments the estimate's pass read (they are inside the stream's totals), its wall seconds and the device events of its calls
+    size_t estimate_segments = 0, estimate_calls = 0;
+    double t_estimate = 0., t_estimate_kernels = 0., t_estimate_h2d = 0., t_estimate_d2h = 0.;
     std::atomic<size_t> lp_contigs{0}, lp_not_unique{0}, lp_edges{0}, lp_movable{0};
 
     // a round's device walk, whichever route made it; says once which contig keeps the host walk
@@ -196,6 +201,9 @@ struct RunStats {
                             "sequences %.3fs\n", u.segments, u.members, (unsigned long long)u.compressed_bytes, (unsigned long long)u.inflated_bytes, u.replanned, u.carried_members,
                     (unsigned long long)(inflate_host_walk_bytes + u.cg_bytes_down), (unsigned long long)inflate_host_walk_bytes, (unsigned long long)u.cg_bytes_down, u.inflate_s, u.table_s,
                     t_blob_sequences);
+            if (estimate_calls)
+                fprintf(stderr, "Estimate on the device: %zu of those segments read by the -e / -l estimate in %.3fs (%zu floria_hip_blob_estimate calls; device events: upload %.3fs, "
+                                "kernels %.3fs, download %.3fs)\n", estimate_segments, t_estimate, estimate_calls, t_estimate_h2d, t_estimate_kernels, t_estimate_d2h);
         }
         if (o.haplosets_resident)
             fprintf(stderr, "Haplosets: %llu split, sorted and kept on the device behind S2 (floria_hip_reassign_batch_resident); one download for the writers, COV / ERR, HAPQ, "
@@ -262,17 +270,34 @@ struct Arithmetic { bool reference_arith; std::string run_note; };           // 
 // and records both values on a second line of cmd.log.  Whatever its origin, an epsilon that is not such a multiple gets one warning on stderr:
 // results are then an equally good solution, but may differ from the Rust binary's where scores tie in exact arithmetic.
 // Fills o.block_length / o.epsilon where they were not given (the seconds of that first pass go to t_bam).
-Arithmetic epsilon_policy(Cli& cli, BamStream& stream, double& t_bam) {
+// `estimate_ctx` (--estimate device): the pass reads device segments - file order from the first record on, complete targets, as the host pass does - and the
+// stream is rewound behind it as behind the host pass.
+Arithmetic epsilon_policy(Cli& cli, BamStream& stream, double& t_bam, floria_hip_ctx* estimate_ctx, RunStats& stats) {
     Options& o = cli.o;
     std::string run_note;
     auto dyadic10 = [](double e) { const double k = e * 1024.0; return k == std::floor(k); };
     if (!cli.have_e || !cli.have_l) {                                             // parse_cmd_line.rs:72-90
         const double tp = now_s();
         EpsilonEstimator estimator;                                               // (a first pass over as much of the file as 1000 sampled columns need)
-        { BamFile seg; while (!estimator.done() && stream.next(seg, cli.bam_window)) estimator.feed(seg); }
+        if (estimate_ctx) {
+            stream.inflate_on_device(estimate_ctx);
+            BamFile seg;
+            while (!estimator.done() && stream.next(seg, cli.bam_window)) { estimator.feed_device(seg); ++stats.estimate_segments; }
+            stats.estimate_calls = estimator.device_calls;
+            stats.t_estimate_kernels = estimator.device_kernel_ms * 1e-3; stats.t_estimate_h2d = estimator.device_h2d_ms * 1e-3; stats.t_estimate_d2h = estimator.device_d2h_ms * 1e-3;
+        } else {
+            BamFile seg;
+            while (!estimator.done() && stream.next(seg, cli.bam_window)) estimator.feed(seg);
+        }
         stream.rewind();
         const auto est = estimator.result();
+        stats.t_estimate = now_s() - tp;
         t_bam += now_s() - tp;
+        if (!cli.dump_estimate.empty()) {
+            std::ofstream out(cli.dump_estimate, std::ios::trunc);
+            if (!out) throw Error(FLORIA_E_INVALID, "cannot write " + cli.dump_estimate);
+            estimator.dump(out);
+        }
         if (!cli.have_l) o.block_length = est.first;
         if (!cli.have_e) {
             o.epsilon = est.second;
@@ -305,12 +330,11 @@ Arithmetic epsilon_policy(Cli& cli, BamStream& stream, double& t_bam) {
 }
 
 // one context per device of --devices (default: the one --device); every one throws without a usable MI355X: no CPU fallback
-std::vector<std::unique_ptr<Session>> open_sessions(const Cli& cli, bool reference_arith) {
+std::vector<std::unique_ptr<Session>> open_sessions(const Cli& cli) {
     std::vector<int> devices = cli.devices;
     if (devices.empty()) devices.push_back(cli.o.device);
     std::vector<std::unique_ptr<Session>> sessions;
     if (needs_session(cli.o.pileup, cli.ingest_only)) for (int d : devices) sessions.emplace_back(new Session(d));     // (--ingest-only --pileup device | resident needs a device for the walk)
-    for (auto& s : sessions) if (floria_hip_set_option(s->ctx(), "arith", reference_arith ? 1 : 0) != 0) throw Error(FLORIA_E_INVALID, floria_hip_last_error());
     return sessions;
 }
 
@@ -601,7 +625,12 @@ int main(int argc, char** argv) {
         // with an index beside it (unless --no-index) only the contigs that will be phased are read, each from its indexed offset
         BamStream stream(o.bam_file, std::max<size_t>(1, o.num_threads), !cli.no_index);
         double t_bam = now_s() - tp;
-        const Arithmetic arith = epsilon_policy(cli, stream, t_bam);
+        // --estimate device: the estimate's pass needs the context, so the sessions are opened in front of it (their "arith" is set behind it, as always)
+        const bool estimate_on_device = cli.estimate_device && (!cli.have_e || !cli.have_l);
+        std::vector<std::unique_ptr<Session>> sessions;
+        double t_device = 0.;
+        if (estimate_on_device) { tp = now_s(); sessions = open_sessions(cli); t_device = now_s() - tp; }
+        const Arithmetic arith = epsilon_policy(cli, stream, t_bam, estimate_on_device ? sessions[0]->ctx() : nullptr, stats);
         if (!cli.ingest_only) write_run_files(o, argc, argv, arith.run_note);
         const std::vector<std::string> contigs = stream.target_names();                 // get_contigs_to_phase (file_reader.rs:738-746)
         tp = now_s();
@@ -609,8 +638,10 @@ int main(int argc, char** argv) {
         const std::map<std::string, std::string> fasta = get_fasta_seqs(o.reference_fasta);
         const double t_vcf = now_s() - tp;
         tp = now_s();
-        std::vector<std::unique_ptr<Session>> sessions = open_sessions(cli, arith.reference_arith);
-        fprintf(stderr, "Preprocessing: BAM header%s %.3fs, VCF + FASTA %.3fs, device %.3fs\n", (!cli.have_e || !cli.have_l) ? " + parameter estimate" : "", t_bam, t_vcf, now_s() - tp);
+        if (!estimate_on_device) sessions = open_sessions(cli);
+        for (auto& s : sessions) if (floria_hip_set_option(s->ctx(), "arith", arith.reference_arith ? 1 : 0) != 0) throw Error(FLORIA_E_INVALID, floria_hip_last_error());
+        fprintf(stderr, "Preprocessing: BAM header%s %.3fs, VCF + FASTA %.3fs, device %.3fs\n", (!cli.have_e || !cli.have_l) ? " + parameter estimate" : "", t_bam, t_vcf,
+                t_device + now_s() - tp);
 
         Run run(cli, vp, fasta, contigs, sessions, arith.reference_arith);
         if (!cli.ingest_only) check_contigs_in_fasta(run);

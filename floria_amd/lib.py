@@ -36,6 +36,7 @@ SYMBOLS = [
     "floria_hip_haploset_alleles_resident", "floria_hip_read_spans_resident", "floria_hip_join_paths", "floria_hip_reassign_haplosets_resident",
     "floria_hip_inflate_bgzf", "floria_hip_blob_bytes", "floria_hip_blob_download", "floria_hip_blob_free", "floria_hip_blob_records", "floria_hip_blob_records_free",
     "floria_hip_pileup_records_resident_blob", "floria_hip_blob_records_opt", "floria_hip_blob_sequences", "floria_hip_blob_sequences_free",
+    "floria_hip_blob_estimate", "floria_hip_estimate_result_free",
     "floria_hip_pack_bytes", "floria_hip_pack_pileup", "floria_hip_pack_bytes_batch", "floria_hip_pack_pileups_batch", "floria_hip_contig_upload_batch_packed", "floria_hip_phase_pileups_batch_packed",
 ]
 
@@ -121,6 +122,9 @@ def load():
         L.floria_hip_blob_sequences.argtypes = [C.c_void_p, C.c_void_p, capi.u64p, capi.u32p, capi.u64p, C.c_uint64, C.POINTER(C.POINTER(capi.CBlobSequences))]
         L.floria_hip_blob_sequences_free.restype = None
         L.floria_hip_blob_sequences_free.argtypes = [C.POINTER(capi.CBlobSequences)]
+        L.floria_hip_blob_estimate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.CEstimateRecords), C.c_uint32, C.POINTER(capi.CEstimateState), C.POINTER(C.POINTER(capi.CEstimateResult))]
+        L.floria_hip_estimate_result_free.restype = None
+        L.floria_hip_estimate_result_free.argtypes = [C.POINTER(capi.CEstimateResult)]
         L.floria_hip_blob_records_free.restype = None
         L.floria_hip_blob_records_free.argtypes = [C.POINTER(capi.CBlobRecords)]
         L.floria_hip_pileup_records_resident_blob.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(capi.CAlignments), C.POINTER(capi.CSnpTable), C.POINTER(capi.CRefSeqs),
@@ -662,6 +666,26 @@ class FloriaHip:
         base_off = capi.np_from(r.base_off, int(r.n) + 1, np.uint64)
         res = (base_off, capi.np_from(r.bases, int(base_off[-1]), np.uint8), capi.np_from(r.quals, int(base_off[-1]), np.uint8))
         load().floria_hip_blob_sequences_free(out)
+        return res
+
+    def blob_estimate(self, blob, pos, cigar_off, n_cigar, seq_off, l_seq, group_off, stop=1000, count=0, n_err=0):
+        """floria_hip_blob_estimate: the -e / -l estimate's sampled pileup columns over the (already filtered) records of a Blob, one group per contig (group_off
+        uint64 [n_groups + 1]), ascending by pos inside a group; (count, n_err) is the state carried in from the records in front.  -> dict(col_group uint32,
+        col_pos int32, col_total uint32, col_most uint32: every sampled column in order; rec_hits uint32 [n]; done bool; count, n_err: the state carried out)."""
+        ps = np.ascontiguousarray(np.atleast_1d(pos), np.int32); co = np.ascontiguousarray(np.atleast_1d(cigar_off), np.uint64); nc = np.ascontiguousarray(np.atleast_1d(n_cigar), np.uint32)
+        so = np.ascontiguousarray(np.atleast_1d(seq_off), np.uint64); ls = np.ascontiguousarray(np.atleast_1d(l_seq), np.uint32); go = np.ascontiguousarray(np.atleast_1d(group_off), np.uint64)
+        if not len(ps) == len(co) == len(nc) == len(so) == len(ls) or len(go) < 1:
+            raise FloriaHipError(capi.FLORIA_E_INVALID, "blob_estimate: one pos, CIGAR offset and count, sequence offset and length per record, and n_groups + 1 group offsets")
+        recs = capi.CEstimateRecords(len(ps), capi.ptr(ps, C.c_int32), capi.ptr(co, C.c_uint64), capi.ptr(nc, C.c_uint32), capi.ptr(so, C.c_uint64), capi.ptr(ls, C.c_uint32),
+                                     len(go) - 1, capi.ptr(go, C.c_uint64))
+        state = capi.CEstimateState(int(count), int(n_err))
+        out = C.POINTER(capi.CEstimateResult)()
+        _check(load().floria_hip_blob_estimate(self._h, blob._h, C.byref(recs), C.c_uint32(int(stop)), C.byref(state), C.byref(out)))
+        r = out.contents
+        k = int(r.n_cols)
+        res = dict(col_group=capi.np_from(r.col_group, k, np.uint32), col_pos=capi.np_from(r.col_pos, k, np.int32), col_total=capi.np_from(r.col_total, k, np.uint32),
+                   col_most=capi.np_from(r.col_most, k, np.uint32), rec_hits=capi.np_from(r.rec_hits, len(ps), np.uint32), done=bool(r.done), count=int(state.count), n_err=int(state.n_err))
+        load().floria_hip_estimate_result_free(out)
         return res
 
     def assemble_contigs_ordered(self, summary, frag_off, part_off, part_rec):

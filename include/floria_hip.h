@@ -524,6 +524,48 @@ int  floria_hip_blob_sequences(floria_hip_ctx* ctx, const floria_hip_blob* blob,
                                const uint64_t* qual_off /* [n] */, uint64_t n, floria_blob_sequences** out);
 void floria_hip_blob_sequences_free(floria_blob_sequences* r);
 
+/* The -e / -l estimate (file_reader.rs:749-826) on records of a blob (csrc/estimate_kernel.h).  The caller has filtered the records (refID >= 0, (flag & 1796) == 0,
+ * at least one CIGAR operation) and gives them in groups, one group per contig in header order, ascending by pos inside a group; record i has its n_cigar[i] CIGAR
+ * words at cigar_off[i] (a CG:B,I array's for a record with the kSmN placeholder) and its packed bases, (l_seq[i] + 1) / 2 bytes, at seq_off[i].
+ * THE FUNCTION: record i spans [pos, end), end = pos + (sum of the lengths of its M D N = X operations), pos + 1 where that sum is 0.  Every position of a group that
+ * lies in a span is a column; the columns of all groups, ascending inside a group, are one sequence.  `count` and `n_err` run through it: a column met with
+ * count % 1000 != 0 only advances count; otherwise it is SAMPLED: every record whose span holds it and whose operation there is M, = or X gives the 4-bit code at its
+ * query offset, if that offset is below l_seq; total = the bases given, most = the largest number of equal codes.  total < 5: count stays (the next column is sampled
+ * too); else n_err advances, the call is `done` where n_err reaches `stop`, and count advances otherwise.
+ * WHAT COMES BACK: every sampled column in order — its group, position, total and most, those with total < 5 too — and rec_hits[i], the number of sampled columns
+ * (up to the one that reached stop) record i gave a base to; the state after the last column in *inout, so that a second call over the records that follow
+ * continues the sequence.  The host forms (total - most) / most of the columns with total >= 5, the multiset of l_seq by rec_hits, and the percentiles.
+ * inout->n_err >= stop on entry: an empty result with done = 1, nothing launched.
+ * Memory is linear in a position window: a group is walked in windows of at most 2^22 positions (test option "estimate_window" = N, 1 .. 2^30), every window
+ * over the records whose span meets it, the state carried from one to the next; the split changes no result.
+ * Refused before any launch, FLORIA_E_INVALID, the message naming the record or group: a null argument, a blob of another context, group_off not starting at 0, descending
+ * or not ending at n, n_cigar == 0, a negative pos, pos descending inside a group, a CIGAR or sequence range that reaches past the blob.  FLORIA_E_UNSUPPORTED: 2^32 and
+ * more records; after the span pass, an end beyond 2^31 - 1.  The call works in buffers of its own and ends no residency; floria_hip_last_timing then reports pileup_ms
+ * (all kernels), h2d_ms, d2h_ms, total_ms. */
+typedef struct {
+    uint64_t n;
+    const int32_t*  pos;        /* [n] */
+    const uint64_t* cigar_off;  /* [n] */
+    const uint32_t* n_cigar;    /* [n] */
+    const uint64_t* seq_off;    /* [n] */
+    const uint32_t* l_seq;      /* [n] */
+    uint32_t n_groups;
+    const uint64_t* group_off;  /* [n_groups+1] */
+} floria_estimate_records;
+typedef struct { uint64_t count; uint32_t n_err; } floria_estimate_state;
+typedef struct {               /* library-owned */
+    uint64_t  n_cols;
+    uint32_t* col_group;       /* [n_cols] every sampled column in order, the discarded ones (total < 5) too */
+    int32_t*  col_pos;
+    uint32_t* col_total;
+    uint32_t* col_most;
+    uint32_t* rec_hits;        /* [n] sampled columns record i gave a base to */
+    uint32_t  done;            /* n_err reached stop */
+} floria_estimate_result;
+int  floria_hip_blob_estimate(floria_hip_ctx* ctx, const floria_hip_blob* blob, const floria_estimate_records* records, uint32_t stop, floria_estimate_state* inout,
+                              floria_estimate_result** out);
+void floria_hip_estimate_result_free(floria_estimate_result* r);
+
 /* floria_hip_pileup_records_resident whose record bytes are a blob handle: alignments->blob must be NULL (FLORIA_E_INVALID otherwise), alignments->blob_bytes is
  * ignored and the offsets index the handle.  The same validation, against the handle's length; the same kernels, pointed at the handle's buffer; the same summary,
  * token and RESIDENCY rule; no record byte is uploaded.  A blob of another context is FLORIA_E_INVALID.  The blob must stay alive while the call runs; the residency
@@ -794,7 +836,7 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
  * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
  * assemble and its set orders, the FILL and ORDER passes of floria_hip_drop_monomorphic, the epilogue of floria_hip_reassign_batch_resident, floria_hip_join_paths, the device prologue of floria_hip_reassign_haplosets_resident — uses at most N workgroups, and the one-thread order kernel at most N threads,
- * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "inflate_slots" (tests: N >= 1 = floria_hip_inflate_bgzf keeps at most N members in flight, so that a wavefront of its persistent grid meets a second member; 0 = default, two per CU), "hw_queues" (tests: override the number of
+ * so that a wavefront meets a second fragment, record or read at small inputs; 0 = default, the grids as they are; negative values are refused; results do not change), "inflate_slots" (tests: N >= 1 = floria_hip_inflate_bgzf keeps at most N members in flight, so that a wavefront of its persistent grid meets a second member; 0 = default, two per CU), "estimate_window" (tests: N = floria_hip_blob_estimate walks a group in windows of at most N positions, 1 .. 2^30; 0 = default, 2^22; results do not change), "hw_queues" (tests: override the number of
  * concurrently running streams floria_hip_create measured — 6 on an MI355X whose host set GPU_MAX_HW_QUEUES=12 before HIP initialised, 4 or fewer
  * with the runtime's default; below 5 the launch plans stay within two job groups and do not speculate). */
 int  floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value);

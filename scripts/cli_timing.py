@@ -23,6 +23,12 @@ opening the file (the "BAM header" figure) and of its inflate + decode seconds, 
 BamStream's seconds (inflate + decode on the host route; member planning, inflate, record table on the device route) and of the wall time, and the device route's
 report line of its last run.  --with-index writes a .bai beside the BAM; --inflate-extra adds options to every run (e.g. "--no-index" or "--output-reads").  With
 --parent-exe the UNFLAGGED tool (--pileup resident alone) of this build also alternates with the parent commit's on the same file (profiles/inflate_route.md).
+--estimate-compare N [--threads-list 16,1] [--parent-tree DIR]: only the batched flow under --pileup resident --inflate device WITHOUT -e / -l, --estimate host and
+--estimate device ALTERNATING, N runs each per thread count, one process per run; then median and spread (min .. max) of the seconds of the estimate's pass on both
+routes (the "BAM header + parameter estimate" figure: opening the file and the pass), of the ingest seconds and of the wall time, and the device route's report line of
+its last run (segments, calls, the calls' upload / kernel / download seconds from floria_hip_last_timing).  The run's `Estimated` line must be the same on both routes.
+With --parent-tree (the parent commit's tree with library and driver built) the UNFLAGGED tool (--pileup resident alone, -e / -l given) of this build also alternates
+with the parent's, and so does bench.py --steps 5 --warmup 2 of the two trees (profiles/estimate_device.md).
 --realign exact: the noisy-reads run's realignment under the exact DP beside a fixed-block walk's.  --exe: another build's floria-hip (a previous commit's, for an A/B).
 
 Writes BAM / VCF / FASTA under $TMPDIR, runs the driver twice and prints its stage-time lines (stderr of floria-hip)."""
@@ -60,6 +66,8 @@ def main():
     ap.add_argument("--inflate-compare", type=int, default=0, help="only: --pileup resident with --inflate host and --inflate device alternating, this many runs each")
     ap.add_argument("--with-index", action="store_true", help="with --inflate-compare: write a .bai beside the BAM")
     ap.add_argument("--inflate-extra", default="", help="with --inflate-compare: further options of every run, space-separated")
+    ap.add_argument("--estimate-compare", type=int, default=0, help="only: --pileup resident --inflate device without -e / -l, --estimate host and device alternating, this many runs each")
+    ap.add_argument("--parent-tree", default=None, help="with --estimate-compare: the parent commit's tree, built (the unflagged tool and bench.py alternate with this tree's)")
     ap.add_argument("--config", type=int, default=4, help="synth configuration of the contigs (4: long reads, 3: paired short reads)")
     ap.add_argument("--epsilon", default="0.03125", help="-e of every run")
     ap.add_argument("--block-length", default="10000", help="-l of every run")
@@ -78,6 +86,8 @@ def main():
         return index_compare(a, exe, tmp, prefix, cs)
     if a.inflate_compare:
         return inflate_compare(a, exe, tmp, prefix)
+    if a.estimate_compare:
+        return estimate_compare(a, exe, tmp, prefix)
     base = [exe, "-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "-e", a.epsilon, "-l", a.block_length, "--snp-count-filter", "50"]
     runs = (("batched", ["-t", str(a.threads)]), ("batched, 1 thread", ["-t", "1"]), ("one contig per batch", ["-t", str(a.threads), "--batch-contigs", "1"]),
             ("ingest only: realign DP on the host", ["-t", str(a.threads), "--ingest-only"]), ("ingest only, 1 thread", ["-t", "1", "--ingest-only"]))
@@ -186,6 +196,63 @@ def inflate_compare(a, exe, tmp, prefix):
                 print(f"[-t {t}] [{label}] {what}: median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}s, min {x[0]:.3f}s, max {x[-1]:.3f}s over {len(x)} runs", flush=True)
         if last_line:
             print(f"[-t {t}] [--inflate device] last run: {last_line}", flush=True)
+
+
+def spread(x):
+    x = sorted(x)
+    return f"median {x[len(x) // 2] if len(x) % 2 else (x[len(x) // 2 - 1] + x[len(x) // 2]) / 2:.3f}, min {x[0]:.3f}, max {x[-1]:.3f} over {len(x)} runs"
+
+
+def estimate_compare(a, exe, tmp, prefix):
+    import json
+    threads = [int(x) for x in a.threads_list.split(",")] if a.threads_list else [a.threads]
+    files = ["-b", prefix + ".bam", "-v", prefix + ".vcf", "-r", prefix + ".fa", "--snp-count-filter", "50"]
+    parent_exe = os.path.join(a.parent_tree, "floria_amd", "host", "floria-hip") if a.parent_tree else None
+    for t in threads:
+        settings = [(f"--estimate {e}", [exe, *files, "-t", str(t), "--pileup", "resident", "--inflate", "device", "--estimate", e]) for e in ("host", "device")]
+        if parent_exe:
+            settings += [(f"unflagged, {which} build", [binary, *files, "-e", a.epsilon, "-l", a.block_length, "-t", str(t), "--pileup", "resident"])
+                         for which, binary in (("this", exe), ("parent", parent_exe))]
+        got = {label: [] for label, _ in settings}
+        estimated, last_line = {}, None
+        for k in range(a.estimate_compare):
+            for label, c in settings:
+                out = os.path.join(tmp, "o_estimate")
+                t0 = time.time()
+                r = subprocess.run(c + ["-o", out], capture_output=True, text=True)
+                wall = time.time() - t0
+                if r.returncode:
+                    print(r.stderr[-2000:])
+                    raise SystemExit(1)
+                ingest = float(re.search(r"Batches \d+; ingest ([\d.]+)s", r.stderr).group(1))
+                opened = float(re.search(r"Preprocessing: BAM header[^,]*? ([\d.]+)s,", r.stderr).group(1))
+                got[label].append((opened, ingest, wall))
+                m = re.search(r"Estimated -l \d+, -e \S+", r.stderr)
+                if m:
+                    estimated[label] = m.group(0)
+                line = next((ln for ln in r.stderr.splitlines() if ln.startswith("Estimate on the device:")), None)
+                print(f"[-t {t}, {label}, run {k + 1}] wall {wall:.2f}s, BAM header (+ estimate) {opened:.3f}s, ingest {ingest:.3f}s" + (f" | {line}" if line else ""), flush=True)
+                last_line = line or last_line
+                subprocess.run(["rm", "-rf", out])
+        for label, _ in settings:
+            for k, what in enumerate(("BAM header (+ estimate) s", "ingest s", "wall s")):
+                print(f"[-t {t}] [{label}] {what}: " + spread([v[k] for v in got[label]]), flush=True)
+        print(f"[-t {t}] estimates: {estimated}" + ("" if len(set(estimated.values())) == 1 else "  <-- THE ROUTES DISAGREE"), flush=True)
+        if last_line:
+            print(f"[-t {t}] [--estimate device] last run: {last_line}", flush=True)
+    if a.parent_tree:
+        rates = {"this": [], "parent": []}
+        for k in range(a.estimate_compare):
+            for which, tree in (("this", ROOT), ("parent", os.path.abspath(a.parent_tree))):
+                r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"], cwd=tree, capture_output=True, text=True)
+                if r.returncode:
+                    print(r.stdout[-2000:], r.stderr[-3000:])
+                    raise SystemExit(1)
+                j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+                print(f"[bench, {which} tree, run {k + 1}] {j['value']} {j['unit']}", flush=True)
+                rates[which].append(float(j["value"]))
+        for which, v in rates.items():
+            print(f"[bench, {which} tree] " + spread(v), flush=True)
 
 
 def index_compare(a, exe, tmp, prefix, cs):
