@@ -70,7 +70,8 @@ class CTiming(C.Structure):
                 ("streams", C.c_uint32), ("stage_width", C.c_uint32), ("phase_ms", C.c_double),
                 ("upload_pinned_bytes", C.c_uint64), ("upload_staged_bytes", C.c_uint64),
                 ("upload_chunks", C.c_uint32), ("optimize_packed_launches", C.c_uint32),
-                ("beam_union_ms", C.c_double), ("optimize_union_ms", C.c_double), ("pileup_ms", C.c_double)]
+                ("beam_union_ms", C.c_double), ("optimize_union_ms", C.c_double), ("pileup_ms", C.c_double),
+                ("optimize_delta_passes", C.c_uint32), ("optimize_delta_fallbacks", C.c_uint32)]
 
 
 class CRealignWalk(C.Structure):

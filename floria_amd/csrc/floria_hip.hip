@@ -212,6 +212,8 @@ struct Knobs {
     uint32_t tail_waves = 2;      // ... with this many waves per CU
     uint32_t opt_packed = 1;      // optimise: the build / distance passes stream the 4-byte packed cells (ContigDev::cell_pk) with 16-byte loads where every contig of the call has
                                   // them and the plan takes a 512-thread ploidy-specialised instance (plan_ploidies); 0 = the 8-byte cells (cell_snp + cell_aw)
+    uint32_t opt_delta = 1;       // optimise, canonical ploidy-specialised instances of 512 threads: distances kept as exact packed integers, and behind an accepted round only the terms at the flipped
+                                  // (position, partition) code bytes are exchanged (optimize_kernel.h: the delta pass); 0 = f64 slots and the interval pass every time
     int32_t  fuse_p1 = -1;        // one ploidy per stage, canonical arithmetic, max_ploidy >= 2, ploidy-1 shortcut on: ploidy 1 has no launch of its own, the ploidy-2 optimise job
                                   // computes it from its own histogram (optimize_kernel.h, with_p1): -1 auto (on where eligible) | 0 off | 1 on where eligible
 };
@@ -858,6 +860,7 @@ int run_phase(floria_hip_ctx* ctx, const floria_params* prm, const PhaseShape& S
                     a.with_p1 = p1_fused && p == 2 ? 1u : 0u;
                     a.pm_lds_off = q.pm_lds_off;
                     a.w24 = ctx->d_w24.as<uint32_t>();
+                    a.opt_delta = K.opt_delta; a.delta_stat = D.diag + 2;          // (diag[2], diag[3]: delta passes run / passes with flips that took the interval pass)
                     // (a plan with ANY speculative stage publishes ready bits and stop_at from every stage: a later stage's stop rule compares with these MEC values)
                     if (K.arith) {
                         a.cell_ord = ctx->cur_ord; a.cell_ord_off = ctx->cur_ord_off;
@@ -1004,6 +1007,7 @@ int floria_hip_create(int device, floria_hip_ctx** out) {
         K.opt_global = getenv("FLORIA_HIP_OPT_GLOBAL") != nullptr;
         K.opt_block_order = getenv("FLORIA_HIP_OPT_BLOCK_ORDER") != nullptr;
         if (const char* v = getenv("FLORIA_HIP_OPT_PACKED")) K.opt_packed = atoi(v) != 0;
+        if (const char* v = getenv("FLORIA_HIP_OPT_DELTA")) K.opt_delta = atoi(v) != 0;
         if (const char* v = getenv("FLORIA_HIP_SPECULATE")) K.speculate = std::max(-1, std::min(3, atoi(v)));
         K.trace = getenv("FLORIA_HIP_TRACE") != nullptr;
         if (const char* v = getenv("FLORIA_HIP_TAIL_OVERLAP")) K.tail_overlap = std::max(-1, std::min(1, atoi(v)));
@@ -1091,6 +1095,7 @@ int floria_hip_set_option(floria_hip_ctx* ctx, const char* key, int64_t value) {
     else if (k == "no_bulk") K.no_bulk = value != 0;
     else if (k == "opt_block_order") K.opt_block_order = value != 0;
     else if (k == "opt_packed") K.opt_packed = value != 0;
+    else if (k == "opt_delta") K.opt_delta = value != 0;
     else if (k == "tail_overlap") { if (value < -1 || value > 1) return fail(FLORIA_E_INVALID, "tail_overlap: 0 | 1"); K.tail_overlap = (int32_t)value; }
     else if (k == "fuse_p1") { if (value < -1 || value > 1) return fail(FLORIA_E_INVALID, "fuse_p1: -1 auto | 0 | 1"); K.fuse_p1 = (int32_t)value; }
     else if (k == "tail_waves") K.tail_waves = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 16));
@@ -2139,6 +2144,7 @@ int s1_core(floria_hip_ctx* ctx, const S1Contigs& SC, const uint32_t* blk_contig
     ctx->timing.beam_union_ms = T.union_ms(K_BEAM); ctx->timing.optimize_union_ms = T.union_ms(K_OPT);
     ctx->timing.h2d_ms = T.sum(K_H2D); ctx->timing.d2h_ms = T.sum(K_D2H); ctx->timing.total_ms = T.span(); ctx->timing.phase_ms = T.sum(K_PHASE);
     ctx->timing.algorithmic_bytes = algo_bytes; ctx->timing.beam_steps = steps;
+    ctx->timing.optimize_delta_passes = diag[2]; ctx->timing.optimize_delta_fallbacks = diag[3];
     std::vector<uint32_t> stage_first(P + 2, 0);       // first ploidy of the stage that holds ploidy p
     for (auto& st : stages) for (uint32_t p : st) stage_first[p] = st.front();
     for (uint32_t b = 0; b < n_blocks; ++b) {          // a beam launch for ploidy p phases the blocks still active when p's stage starts (ploidy 1 needs no launch)

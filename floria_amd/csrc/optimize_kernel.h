@@ -82,7 +82,36 @@ struct OptArgs {
     uint32_t  fk_lds_off;        // != 0: the first-insertion keys as 32-bit words (read << 12 | cell rank: reads < 2^20, cells per read < 2^12) in LDS at this offset ([ploidy*span_max])
     // packed-cell instances (PK = true): the 256-entry Q24 weight table (what flatten_kernel folds into cell_aw), which the workgroup stages in LDS
     const uint32_t* w24;
+    // canonical ploidy-specialised instances: != 0 = a read's distances are kept as the exact packed integers (diff Q24 << 16 | #empty) and, behind an accepted round, only the terms
+    // at the (position, partition) pairs whose code byte flipped are exchanged (the delta pass below); delta_stat[0] / [1] count the delta passes run / the passes that had flips and
+    // took the interval pass instead
+    uint32_t  opt_delta;
+    uint32_t* delta_stat;
 };
+// The delta pass's list of flipped code bytes lives in the candidate sort's s_key, idle from the serial application of a round's moves to the next round's sort: entries
+// position << 12 | partition << 8 | old code << 4 | new code, then the number of flips seen (which may exceed the capacity: the overflow flag), then the reads that reach into
+// the interval of flipped positions and their cells (what the interval pass would stream)
+constexpr uint32_t OPT_FLIP_CAP = 64;
+// the delta pass runs when flips * (reads in the interval) * OPT_DELTA_DIV <= cells in the interval: a thread looks a read's cell up once per flip inside the read's span, two to four
+// dependent loads, where the interval pass streams the read's cells 64 per trip (profiles/opt_delta.md)
+#ifndef OPT_DELTA_DIV
+#define OPT_DELTA_DIV 4
+#endif
+// A read's cell at delta d = position - first position of the read, or -1: delta_at(j) is strictly ascending in j with delta_at(j) >= j, so the cell sits at j <= d, and
+// delta_at(j) - j, the positions the read skips before cell j, is non-decreasing: a probe at j bounds the answer from both sides.  First the guess j = d (long reads are nearly
+// dense), then the lower bound that probe gave, then bisection; every probe stays inside [0, len).
+template <class F> __host__ __device__ __forceinline__ int32_t opt_find_cell(int32_t len, int32_t d, F&& delta_at) {
+    int32_t lo = 0, hi = d < len - 1 ? d : len - 1;
+    for (int step = 0; lo <= hi; ++step) {
+        const int32_t j = step == 0 ? hi : (step == 1 ? lo : (lo + hi) >> 1);
+        const int32_t dj = (int32_t)delta_at(j);
+        if (dj == d) return j;
+        const int32_t b = d - (dj - j);          // the cell at delta d, if there is one, has as many skipped positions before it as cell j (dj < d: at least; dj > d: at most)
+        if (dj > d) { hi = j - 1; lo = b > lo ? b : lo; }
+        else { lo = j + 1; hi = b < hi ? b : hi; }
+    }
+    return -1;
+}
 // fired(q): the reference's loop breaks at ploidy q (graph_processing.rs:196-251); needs mec[q-1] (q > 1) and mec[q], num_alleles[q]
 __device__ inline bool stop_rule_fires(const OptArgs& g, uint32_t b, uint32_t q) {
     const double mec_q = __hip_atomic_load(&g.mec[(uint64_t)b * g.max_ploidy + q - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -183,6 +212,8 @@ void optimize_kernel(OptArgs g) {
     __shared__ uint32_t s_errm[MAX_PLOIDY];
     __shared__ uint32_t s_size[MAX_PLOIDY];
     __shared__ uint32_t s_ncand, s_nmoves, s_job, s_skip, s_dq, s_p1stop;
+    // s_dq has one meaning per instance, never both: ARITH — the work counter of dist_arith; DELTA (which excludes ARITH, below) — s_idist, != 0 while the job at hand keeps integer distances
+    uint32_t& s_idist = s_dq;
     __shared__ uint32_t s_chg_lo, s_chg_hi;          // positions whose code byte changed in the last batch of moves (HL)
     __shared__ uint32_t s_bkt[OPT_BUCKETS];          // visiting order: reads per bucket of ceil(#cells / 64), then the buckets' write cursors
     __shared__ double s_score;
@@ -199,6 +230,10 @@ void optimize_kernel(OptArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t p = TP ? (uint32_t)TP : g.ploidy, PA = p * A;
     constexpr int KMAX = TP ? TP : MAX_PLOIDY;
+    // integer distances + delta passes: the canonical ploidy-specialised instances of 512 threads (the plans of long-read blocks).  The 1024-thread instances keep the f64 slots and the
+    // interval pass: with the delta pass compiled in, ploidy 2 / 3 take 84 / 85 VGPRs instead of 78 / 80 and lose a wave per SIMD.
+    constexpr bool DELTA = HL && !ARITH && TP != 0 && OPT_THREADS == 512;
+    static_assert(!DELTA || A == 2, "a flip's old and new code byte take four bits each; the ploidy-specialised instances are biallelic");
     const uint32_t moved_bytes = (((g.n_max + 31) / 32) * 4 + 15) & ~15u;
     const uint32_t meta_n = g.n_max <= (uint32_t)OPT_META_MAX ? g.n_max : 0;            // 0 = read the metadata from HBM every time
     const uint32_t meta_bytes = (meta_n * 12 + 15) & ~15u;
@@ -257,11 +292,15 @@ void optimize_kernel(OptArgs g) {
             for (uint32_t x = tq; x < ncell; x += OPT_THREADS) hist[x] = 0;
             if (tq < (uint32_t)MAX_PLOIDY) s_size[tq] = 0;
             if (tq < (uint32_t)OPT_BUCKETS) s_bkt[tq] = 0;
+            if (DELTA && tq == 0) s_idist = (meta_n != 0 && span <= 65535u && g.opt_delta != 0) ? 1u : 0u;
         }
         stage_weights();
         __syncthreads();
         // stage (first cell, #cells, partition) of every read once: the chain reads[i] -> read_off[r] -> cells is then one hop
         const bool meta = meta_n != 0;
+        // idist: this job keeps integer distances and runs delta passes ("opt_delta", metadata in LDS, positions in 16 bits)
+        // (the flag sits in LDS — s_idist — and is read where it is needed: a register kept for the whole job is one too many in the 80-VGPR instances)
+        auto idist_now = [&]() -> bool { if constexpr (DELTA) return s_idist != 0; else return false; };
         for (uint32_t i = tid; i < n; i += OPT_THREADS) {
             const uint32_t r = reads[i], k = pin[i];
             part[i] = (uint8_t)k;
@@ -283,9 +322,11 @@ void optimize_kernel(OptArgs g) {
         };
         // `track`: record the interval of positions whose code changed — a read's distances depend on the codes at its positions only,
         // so after a batch of moves only the reads that reach into that interval are re-evaluated (moves rarely flip a consensus)
+        // idist (canonical ploidy-specialised instances, "opt_delta"): the flips are also written down one by one (OPT_FLIP_CAP), for the delta pass of the next round
         auto refresh_codes = [&](bool track) {
             if (!HL) return;
-            if (track) { if (tid == 0) { s_chg_lo = 0xffffffffu; s_chg_hi = 0; } __syncthreads(); }
+            if (track) { if (tid == 0) { s_chg_lo = 0xffffffffu; s_chg_hi = 0; if (idist_now()) { s_key[OPT_FLIP_CAP] = 0; s_key[OPT_FLIP_CAP + 1] = 0; s_key[OPT_FLIP_CAP + 2] = 0; } } __syncthreads(); }
+            const bool idist = track && idist_now();
             for (uint32_t x = tid; x < span * p; x += OPT_THREADS) {            // x = position * p + partition
                 const uint64_t* cp = hist + (uint64_t)x * A;
                 uint64_t q[A], mx = 0;
@@ -295,7 +336,10 @@ void optimize_kernel(OptArgs g) {
 #pragma unroll
                 for (int a = 0; a < A; ++a) c |= (mx != 0 && q[a] == mx) ? (1u << a) : 0u;
                 if (!track) codes[x] = (uint8_t)c;
-                else if (codes[x] != (uint8_t)c) { codes[x] = (uint8_t)c; const uint32_t pr = x / p; atomicMin(&s_chg_lo, pr); atomicMax(&s_chg_hi, pr); }
+                else if (const uint32_t co = codes[x]; co != c) {
+                    codes[x] = (uint8_t)c; const uint32_t pr = x / p; atomicMin(&s_chg_lo, pr); atomicMax(&s_chg_hi, pr);
+                    if (idist) { const uint32_t at = atomicAdd(&s_key[OPT_FLIP_CAP], 1u); if (at < OPT_FLIP_CAP) s_key[at] = (pr << 12) | ((x - pr * p) << 8) | (co << 4) | c; }
+                }
             }
             __syncthreads();
         };
@@ -842,7 +886,67 @@ void optimize_kernel(OptArgs g) {
                 // packed partial (diff Q24 << 16 | #eps) per partition, DPP row all-reduce, lane k of the row stores
                 const bool incremental = HL && meta && it > 0 && span <= 65535u;
                 const uint32_t chg_lo = incremental ? s_chg_lo : 0u, chg_hi = incremental ? s_chg_hi : 0xffffffffu;
-                if constexpr (ARITH) { /* the distances of this round were computed beside the last statistics call (dist_arith) */                } else
+                // idist, behind an accepted round: 0 = the interval pass after all (more flips than the list holds, or so many that looking the cells up costs more than
+                // streaming the interval's reads), 1 = the delta pass, 2 = no code byte flipped, every distance stands
+                uint32_t dmode = 0;
+                const bool idist = idist_now();
+                if constexpr (DELTA) { if (idist && it > 0) {
+                    const uint32_t nf = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_key[OPT_FLIP_CAP]);
+                    if (nf == 0) dmode = 2;
+                    else {
+                        bool ok = nf <= OPT_FLIP_CAP;
+                        if (ok) {
+                            uint64_t rc = 0;                                   // reads << 40 | cells of the reads that reach into [chg_lo, chg_hi]
+                            for (uint32_t i = opt_opaque((uint32_t)tid); i < n; i += OPT_THREADS) { const uint32_t fl = m_fl[i]; if (!((fl >> 16) < chg_lo || (fl & 0xffffu) > chg_hi)) rc += (1ull << 40) | (m_lk[i] & 0xffffffu); }
+                            rc = opt_wave_sum_u64(rc);
+                            if (lane == 0) { atomicAdd(&s_key[OPT_FLIP_CAP + 1], (uint32_t)(rc >> 40)); atomicAdd(&s_key[OPT_FLIP_CAP + 2], (uint32_t)rc); }
+                            __syncthreads();
+                            ok = (uint64_t)nf * (uint32_t)__builtin_amdgcn_readfirstlane((int)s_key[OPT_FLIP_CAP + 1]) * OPT_DELTA_DIV <= (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)s_key[OPT_FLIP_CAP + 2]);
+                        }
+                        dmode = ok ? 1u : 0u;
+                        if (tid == 0) atomicAdd(&g.delta_stat[ok ? 0 : 1], 1u);
+                    }
+                } }
+                if constexpr (ARITH) { /* the distances of this round were computed beside the last statistics call (dist_arith) */ }
+                else if (dmode == 1) {
+                    // ---- the delta pass: one thread per read.  A distance is the sum over the read's cells of a term fixed by (code byte at the cell's position, allele, weight):
+                    // for every flip inside the read's span the read's cell at that position, if it has one, exchanges term(old code) for term(new code) in that partition's
+                    // packed sum — the integers a full re-evaluation gives.  One store per (read, partition), no atomics.
+                    if constexpr (DELTA) {
+                        const uint32_t nf = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_key[OPT_FLIP_CAP]);
+                        for (uint32_t i = opt_opaque((uint32_t)tid); i < n; i += OPT_THREADS) {          // (addresses that are not kept across the job loop, see opt_opaque)
+                            const uint32_t fl = m_fl[i], f0 = fl & 0xffffu, l0 = fl >> 16, cb = m_cb[i], len = m_lk[i] & 0xffffffu;
+                            if (len == 0 || l0 < chg_lo || f0 > chg_hi) continue;
+                            uint64_t acc[KMAX];
+#pragma unroll
+                            for (int k = 0; k < KMAX; ++k) acc[k] = 0;
+                            for (uint32_t f = 0; f < nf; ++f) {
+                                const uint32_t e = s_key[f], pr = e >> 12;
+                                if (pr < f0 || pr > l0) continue;
+                                uint32_t al, w;
+                                if constexpr (PK) {
+                                    uint32_t pk = 0;                              // (the last cell probed: the one found)
+                                    const int32_t j = opt_find_cell((int32_t)len, (int32_t)(pr - f0), [&](int32_t jj) { pk = G(cd.cell_pk)[cb + jj]; return pk_delta(pk); });
+                                    if (j < 0) continue;
+                                    al = pk_allele(pk); w = wt[pk_qual(pk)];
+                                } else {
+                                    const int32_t j = opt_find_cell((int32_t)len, (int32_t)(pr - f0), [&](int32_t jj) { return G(cd.cell_snp)[cb + jj] - pos0 - f0; });
+                                    if (j < 0) continue;
+                                    const uint32_t aq = G(cd.cell_aw)[cb + j];
+                                    al = aq >> 28; w = aq & 0x0fffffffu;
+                                }
+                                const uint32_t kf = (e >> 8) & 15u, co = (e >> 4) & 15u, cn = e & 15u;
+                                const uint64_t miss = (uint64_t)w << 16;
+                                const uint64_t dt = (cn == 0 ? 1ull : (((cn >> al) & 1u) ? 0ull : miss)) - (co == 0 ? 1ull : (((co >> al) & 1u) ? 0ull : miss));
+#pragma unroll
+                                for (int k = 0; k < KMAX; ++k) acc[k] += kf == (uint32_t)k ? dt : 0ull;
+                            }
+#pragma unroll
+                            for (int k = 0; k < KMAX; ++k)
+                                if (acc[k]) dist[i * p + k] = __longlong_as_double((long long)((uint64_t)__double_as_longlong(dist[i * p + k]) + acc[k]));
+                        }
+                    }
+                } else if (dmode == 0) {          // the full pass (round 0), or the interval pass
                 for (uint32_t iv = grp; iv < n16; iv += OPT_THREADS / LPR) {
                     const uint32_t i = visit(iv);
                     uint32_t cb = 0, len = 0, kk = 0;
@@ -919,9 +1023,10 @@ void optimize_kernel(OptArgs g) {
                     for (int k = 0; k < KMAX; ++k) {
                         if ((uint32_t)k < p) {
                             const uint64_t t = rowL_sum_u64<LPR>(acc[k]);
-                            if (sub == (uint32_t)k && i < n && len != 0) dist[i * p + k] = qm_to_f64(t >> 16, t & 0xffff, g.eps);
+                            if (sub == (uint32_t)k && i < n && len != 0) dist[i * p + k] = idist ? __longlong_as_double((long long)t) : qm_to_f64(t >> 16, t & 0xffff, g.eps);      // (idist: the packed sum itself, bit for bit)
                         }
                     }
+                }
                 }
                 OPT_TICK(2);     // dist
                 if (tid == 0) { s_ncand = 0; s_nmoves = 0; }
@@ -931,7 +1036,12 @@ void optimize_kernel(OptArgs g) {
                     const uint32_t i = pair / p, j = pair - i * p;
                     const uint32_t pi = part[i];
                     if (j == pi || s_size[pi] <= 1) continue;                   // :300-302, :309-311
-                    const double diff_score = dist[i * p + pi] - dist[pair];    // :320
+                    double d_own = dist[i * p + pi], d_to = dist[pair];
+                    if (idist) {                                                // the slots hold the packed sums: the conversion the distance pass would have made
+                        const uint64_t ta = (uint64_t)__double_as_longlong(d_own), tb = (uint64_t)__double_as_longlong(d_to);
+                        d_own = qm_to_f64(ta >> 16, ta & 0xffff, g.eps); d_to = qm_to_f64(tb >> 16, tb & 0xffff, g.eps);
+                    }
+                    const double diff_score = d_own - d_to;                     // :320
                     if (diff_score > 0.0) {
                         const uint32_t idx = atomicAdd(&s_ncand, 1u);
                         cgain[idx] = (uint64_t)__double_as_longlong(diff_score);
@@ -982,9 +1092,10 @@ void optimize_kernel(OptArgs g) {
                         const uint32_t mvv = moves[x], rl = mvv >> 8;
                         uint32_t from = (mvv >> 4) & 15, to = mvv & 15;
                         if (undo) { uint32_t t = from; from = to; to = t; }
-                        const uint32_t r = reads[rl];
                         if (ARITH && lane == 0 && meta) m_lk[rl] = (m_lk[rl] & 0xffffffu) | (to << 24);      // (the staged partition follows the moves: read_meta's k stays current)
-                        const uint32_t cb = G(cd.read_off)[r], ce = G(cd.read_off)[r + 1];
+                        uint32_t cb, ce;                     // (the staged offset and length where there are: reads[rl] -> read_off[r], read_off[r + 1] are two round trips before the cells)
+                        if (!ARITH && meta) { cb = m_cb[rl]; ce = cb + (m_lk[rl] & 0xffffffu); }
+                        else { const uint32_t r = reads[rl]; cb = G(cd.read_off)[r]; ce = G(cd.read_off)[r + 1]; }
                         for (uint32_t c = cb + lane; c < ce; c += 64) {
                             const uint32_t aq = G(cd.cell_aw)[c];
                             const unsigned long long d = (1ull << CNT_SHIFT) | (aq & 0x0fffffffu);

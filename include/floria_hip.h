@@ -172,6 +172,8 @@ typedef struct {
     double   optimize_union_ms;/* ... with at least one optimise launch in flight */
     double   pileup_ms;        /* floria_hip_pileup_records: sum over the call's launches (count pass, offset scan, fill pass).  Appended with that entry point:
                                 * floria_hip_last_timing writes the whole struct, so callers built against the shorter layout must be rebuilt */
+    uint32_t optimize_delta_passes;    /* last S1 call, "opt_delta": distance passes behind an accepted round that exchanged only the terms at the flipped code bytes */
+    uint32_t optimize_delta_fallbacks; /* ... that had flips and streamed the interval's reads instead (more flips than the list holds, or too many to pay).  Appended as pileup_ms was */
 } floria_timing;
 
 typedef struct floria_hip_ctx floria_hip_ctx;
@@ -831,7 +833,10 @@ int  floria_hip_set_slots(floria_hip_ctx* ctx, uint32_t beam_slots);
  * (0|128|512|1024), "opt_global", "opt_block_order" (tests / A/B: the optimise kernel's passes visit a block's reads in block order instead of longest first),
  * "opt_packed" (1 = default: the optimise kernel's build and distance passes stream one 4-byte packed cell per cell — SNP delta, allele, quality byte, weights from a table
  * in LDS — with 16-byte loads, where every contig of the call was uploaded through the library's flatten launch and the kernel is a ploidy-specialised instance; 0 = the
- * 8-byte cells everywhere; FLORIA_HIP_OPT_PACKED in the environment), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
+ * 8-byte cells everywhere; FLORIA_HIP_OPT_PACKED in the environment), "opt_delta" (1 = default: the 512-thread ploidy-specialised canonical instances of the optimise kernel keep a
+ * read's distances as exact packed integers and, behind an accepted round, exchange only the terms at the code bytes that flipped, falling back to the interval pass
+ * when more than 64 flipped or looking the cells up would cost more; 0 = f64 slots and the interval pass; FLORIA_HIP_OPT_DELTA in the environment; results are
+ * bit for bit the same, floria_timing.optimize_delta_passes / optimize_delta_fallbacks say which pass ran), "slots", "stage_threads" (host threads that fill the pinned staging ring of a pageable upload),
  * "upload_chunks" (chunks of floria_hip_phase_pileups_batch, 0 = auto), "trace" (host-side timestamps of an S1 call on stderr), "reassign_path", "arith_hbm" (tests: the reference-arithmetic mode's tables in HBM scratch even where they fit into LDS), "arith_replay" (tests: that mode replays every position map insertion by insertion instead of listing it by the home-bucket rule where that applies), "fx_tags" / "arith_ow6" (A/B: size of the replay's claim table, the six-wave optimise instance at every ploidy), "no_bulk" (tests: every beam step through the general
  * insert path with its duplicate test), "asm_order_general" (tests: floria_hip_assemble_contigs_ordered sends every fragment through its one-thread-per-fragment
  * kernel; results do not change), "chain_wgs" (tests: N >= 1 = every grid-stride launch of the resident chain — the CIGAR walk, the realignment's gather and scatter,
