@@ -97,13 +97,13 @@ class Job:
                     t[i][k] += _term(int(codes[int(s[x]) - self.pos0, k]), int(a[x]), int(w[x]))
         return t
 
-    def delta_update(self, t, flips):
+    def delta_update(self, t, flips, limit=None):
         """the delta pass: exchange the terms at the flipped (position, partition) pairs; returns the number of cells found and what the pass met: "first" / "last" (a flip
         at a read's first / last position), "gap" (a read spans the position and has no cell there), "to0" / "from0" (a code byte that becomes / was 0: the #empty field),
         "two_same" / "two_diff" (two cells of one read exchanged in the same / in different partitions), "long" (a read of more than 256 cells), "bisect" (a search that
-        took more than two probes)"""
+        took more than two probes).  limit: only the first `limit` reads are visited (run's delta_reads)"""
         found, met = 0, set()
-        for i, (s, a, w) in enumerate(self.reads):
+        for i, (s, a, w) in enumerate(self.reads[:limit]):
             f0, l0 = int(s[0]) - self.pos0, int(s[-1]) - self.pos0
             hit = []
             for pr, k, co, cn in flips:
@@ -140,9 +140,12 @@ class Job:
         return "delta" if len(flips) * len(inside) * DELTA_DIV <= sum(inside) else "interval"
 
 
-def run(pileup, read_ids, part, ploidy, eps, w24, alleles=2):
+def run(pileup, read_ids, part, ploidy, eps, w24, alleles=2, delta_reads=None):
     """-> (optimised partition, rounds run, [per round with moves: {"flips": [(position, partition, old, new)], "accepted": bool, "pass": what the NEXT round's distance
-    pass is, "cells": cells the delta update touched, "met": the cases it met (Job.delta_update)}])"""
+    pass is, "cells": cells the delta update touched, "met": the cases it met (Job.delta_update), "M": the round's candidate moves, "M2": the power of two the kernel
+    sorts them in (optimize_kernel.h: in LDS up to OPT_SORT_LDS, in the global pools beyond)}])
+    delta_reads (sensitivity checks only; None = the kernel): a BROKEN kernel whose delta pass visits only the first delta_reads reads of the block — behind a delta pass the
+    other reads keep their stale distances, the interval pass stays whole.  A test that must notice such a kernel picks inputs on which this run leaves the oracle."""
     J = Job(pileup, read_ids, part, ploidy, eps, w24, alleles)
     n, p = len(J.reads), ploidy
     rounds, iters = [], 0
@@ -189,14 +192,20 @@ def run(pileup, read_ids, part, ploidy, eps, w24, alleles=2):
         new_codes = J.codes()
         flips = [(int(pr), int(k), int(codes[pr, k]), int(new_codes[pr, k])) for pr, k in zip(*np.nonzero(codes != new_codes))]
         new = J.score()
-        info = {"flips": flips, "accepted": new > prev, "pass": "none", "cells": 0, "met": set()}
+        M2 = 1
+        while M2 < M:
+            M2 <<= 1
+        info = {"flips": flips, "accepted": new > prev, "pass": "none", "cells": 0, "met": set(), "M": M, "M2": M2}
         rounds.append(info)
         if new > prev:
             prev = new
             info["pass"] = J.pass_taken(flips) if it + 1 < NUM_ITER_OPTIMIZE else "none"          # (the pass opens the next round)
-            info["cells"], info["met"] = J.delta_update(t, flips)
+            info["cells"], info["met"] = J.delta_update(t, flips, delta_reads)
             full = J.distances(new_codes)
-            assert t == full, ("the per-position update differs from the full recomputation", it, flips)
+            if delta_reads is None:
+                assert t == full, ("the per-position update differs from the full recomputation", it, flips)
+            elif info["pass"] != "delta":
+                t = full
             codes = new_codes
         else:
             for rl, i, j in moves:
